@@ -22,7 +22,7 @@ driver's 1/2/4/8 curve built from `value` divides like quantities.
 started before anything touches the GPU) when it is not already under a
 launcher; every rank checks that its world size equals --gpus.
 
-`scaling_leg` (every N, N = 1 included): BASELINE config 4 (64 views 4K,
+`scaling_leg` (`--full`; every N, N = 1 included): BASELINE config 4 (64 views 4K,
 "reference-cell shard across 8 x MI355X with RCCL all-gather of accepted
 patches").  One step = one whole densify (PMVS::Run minus matching,
 pmvs.cpp:22-43) with every BFS generation partitioned by reference-view
@@ -31,6 +31,13 @@ refine of the rank's items, ONE RCCL all-gather of the accepted candidates,
 replicated organizer commit); rate = every candidate refined (seed stage +
 expansions) over the max-over-ranks wall time -- strong scaling, the same
 densify at every N, under the same key at every N.
+
+A plain run (`bench.py --gpus N --steps K --warmup W`) does only what `value`
+needs: set-up, W warm-up steps, K timed steps, the result line with the
+figures derived from those K steps (`--dump-outputs DIR` also writes what the
+last timed step computed).  Every other leg -- perf_mode, densify_e2e[_fast],
+scaling_leg, seed_generation, cpu_baseline -- takes runs of its own and is
+behind `--full`, where the --no-* switches still drop single legs.
 
 Prints ONE JSON line (rank 0).
 """
@@ -65,6 +72,13 @@ def parse():
     ap.add_argument("--cpu-parents-1thread", type=int, default=5000,
                     help="single-thread CPU baseline sample (a prefix of the same sample)")
     ap.add_argument("--cpu-threads", type=int, default=0, help="0 = every usable host core")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the informational legs (perf_mode, densify_e2e[_fast], scaling_leg, "
+                         "seed_generation) and the CPU baseline with its bit-exact check; the --no-* switches drop "
+                         "single legs of a --full run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (the children's record fields "
+                         "and accept flags, as a caller of expand_device reads them back) to DIR/<name>.npy")
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-densify", action="store_true", help="skip the informational end-to-end densify")
     ap.add_argument("--no-seeds", action="store_true", help="skip the informational seed generation")
@@ -85,10 +99,16 @@ def parse():
                          "value (keys n*_mv<k>, headline parents)")
     ap.add_argument("--no-fast", action="store_true", help="skip the perf_mode sub-object")
     ap.add_argument("--seed-stride", type=float, default=32.0, help="synthetic seed grid stride (px)")
-    ap.add_argument("--detail", default=os.path.join(ROOT, "gpurun_out", "bench_detail.json"),
+    ap.add_argument("--detail", default=None,
                     help="side file for the full result (event arrays, every perf_mode run, partition probes, seed "
-                         "generation); stdout carries only the compact line (compact())")
-    return ap.parse_args()
+                         "generation); stdout carries only the compact line (compact()).  Default: none for a "
+                         "plain run, bench_out/bench_detail.json with --full")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.detail is None and args.full:
+        args.detail = os.path.join(ROOT, "bench_out", "bench_detail.json")
+    return args
 
 
 STDOUT_LIMIT = 4096  # the driver parses the last stdout line; r05's 18,962-byte line was not parsed
@@ -382,9 +402,11 @@ def main():
         result["fast_stats"] = {k: int(v) for k, v in fst.items()}
         result["roofline"]["bytes_per_launch_compulsory"] = float(fst["staged_bytes"] + 128 * B)
         result["quality"] = quality(cfg, out, acc)
-    # the informational legs and the CPU baseline run at N = 1 only (at N > 1 the
-    # partitioned densify legs below are the report)
-    solo = world == 1
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out, acc)
+    # the informational legs and the CPU baseline: --full only, and at N = 1 only
+    # (at N > 1 the partitioned densify legs below are the report)
+    solo = args.full and world == 1
     if solo and not fast and not args.no_fast:
         result["perf_mode"] = perf_mode(eng, args, cfg, stream, d_parents, NP, work, accept, out, acc, parents, P,
                                         planes, raw_seed_p)
@@ -417,7 +439,7 @@ def main():
     result["scaling_curve"] = ("value: weak scaling of the config-3 refine batch (%d candidates per rank, no "
                                "data-path collective); scaling_leg.<mode>.Mpatches_per_s: strong scaling of the "
                                "config-4 partitioned densify (the same densify at every N)" % B)
-    if not args.no_densify and not fast:
+    if args.full and not args.no_densify and not fast:
         result["scaling_leg"] = scaling_leg(args, stream, dist, coll_dev, torch.device("cuda", local))
     if solo and not args.no_seeds:
         result["seed_generation"] = seed_generation(eng, args)
@@ -442,6 +464,35 @@ def main():
         dist.barrier()
         dist.destroy_process_group()
     eng.close()
+
+
+DUMP_LIMIT = 60 * 1000 * 1000  # bytes of .npy payload per --dump-outputs directory
+DUMP_SEED = 20240611
+
+
+def dump_outputs(path: str, kids: np.ndarray, acc: np.ndarray) -> None:
+    """--dump-outputs: what the last timed step left in the caller's buffers,
+    one <field>.npy per record field of the children plus accept.npy, row i of
+    every file the same candidate.  float32 where that is exact (f32 and 8-bit
+    fields), float64 for the u32 fields; the 64-bit masks (vis, cand) as their
+    four 32-bit words, low word first, in float64.  A batch over DUMP_LIMIT
+    bytes is cut to a fixed seeded row sample (rows.npy holds the row numbers)."""
+    os.makedirs(path, exist_ok=True)
+    cols = {"pos": kids["pos"], "normal": kids["normal"], "score": kids["score"],
+            "rgb": kids["rgb"].astype(np.float32), "flags": kids["flags"].astype(np.float32),
+            "accept": acc.astype(np.float32)}
+    for k in ("ref", "seq", "evals", "parent"):
+        cols[k] = kids[k].astype(np.float64)
+    for k in ("vis", "cand"):
+        cols[k] = np.ascontiguousarray(kids[k]).view("<u4").reshape(len(kids), 4).astype(np.float64)
+    n = len(kids)
+    row_bytes = 8 + sum(a.dtype.itemsize * int(np.prod(a.shape[1:], dtype=np.int64)) for a in cols.values())
+    rows = np.arange(n)
+    if n * row_bytes > DUMP_LIMIT:
+        rows = np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_LIMIT // row_bytes, replace=False))
+    np.save(os.path.join(path, "rows.npy"), rows.astype(np.float64))
+    for k, a in cols.items():
+        np.save(os.path.join(path, k + ".npy"), np.ascontiguousarray(a[rows]))
 
 
 def partitioned_leg(eng, seeds, dist, coll_dev, dev, steps, warmup, fast, exchange=False, probe_worlds=(2, 8),

@@ -5,7 +5,7 @@
 set -u
 cd "$(dirname "$0")/.."
 mkdir -p gpurun_out
-ARGS=${BENCH_ARGS:-"--no-cpu --no-densify --no-seeds --steps 2 --warmup 1"}
+ARGS=${BENCH_ARGS:-"--full --no-cpu --no-densify --no-seeds --steps 2 --warmup 1"}
 for v in ${VARIANTS:-libdensepoints.so}; do
   if [ -n "${TESTS:-}" ]; then
     DP_LIB_VARIANT=$v timeout -k 10 300 python -u -m pytest $TESTS -m gpu -q --timeout 200 --timeout-method thread > gpurun_out/ab_test_$v.log 2>&1

@@ -6,6 +6,8 @@ cd "$(dirname "$0")/.."
 mkdir -p gpurun_out
 export TMPDIR=/tmp
 ok_rc() { [ "$1" -eq 0 ] || [ "$1" -eq 1 ]; }
+# the short bench keeps every leg and the CPU baseline (bench.py --full) unless BENCH_ARGS says otherwise
+BENCH_ARGS=${BENCH_ARGS:---full}
 python -c "import __graft_entry__ as g; g.build()" > gpurun_out/build.log 2>&1 || { echo "build failed"; exit 3; }
 timeout -k 10 ${PYTEST_TIMEOUT:-900} python -u -m pytest tests -q -m gpu -x --timeout 300 --timeout-method thread ${PYTEST_ARGS:-} > gpurun_out/pytest_gpu.log 2>&1
 rc=$?; echo "pytest rc=$rc"; tail -5 gpurun_out/pytest_gpu.log

@@ -12,7 +12,7 @@ if [ "${TESTS:-1}" = 1 ]; then
 fi
 for i in $(seq 1 ${REPS:-2}); do
   for lib in libdensepoints.so ${VARIANT:?}; do
-    DP_LIB_VARIANT=$lib timeout -k 10 300 python -u bench.py --steps 3 --warmup 1 --no-cpu --no-densify --no-seeds \
+    DP_LIB_VARIANT=$lib timeout -k 10 300 python -u bench.py --full --steps 3 --warmup 1 --no-cpu --no-densify --no-seeds \
       --detail gpurun_out/ab_${lib}_$i.json > gpurun_out/ab_${lib}_$i.log 2>&1
     rc=$?; [ $rc -eq 0 ] || { echo "bench $lib rc=$rc"; tail -5 gpurun_out/ab_${lib}_$i.log; exit $rc; }
     python3 -c "
