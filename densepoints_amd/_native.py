@@ -265,6 +265,8 @@ SIGNATURES = [
     ("dp_probe_grad_q24_device", _I, [_P, _I, _P]),
     ("dp_probe_lds_unaligned_device", _I, [_P]),
     ("dp_debug_stamps", _I, [_P]),
+    ("dp_probe_akaze_plane", _I, [_P, _I, _I, _I, _P, ctypes.c_int64, _P]),
+    ("dp_probe_orb_level", _I, [_P, _I, _I, _I, _D, _P, ctypes.c_int64, _P]),
 ]
 
 

@@ -91,8 +91,16 @@ hipError_t launch_akz_emit(const AkArgs &a, int level, const unsigned long long 
 
 // candidate list (sorted global Ldet indices) -> keypoints (OpenCV's
 // sequential suppression + subpixel refinement, one workgroup per view),
-// keep flags; a view with more candidates than the LDS list holds sets *err
-// (its candidate count) and keeps none
+// keep flags.  A view's suppression list lives in LDS when its candidates fit
+// kAkListCap entries, else in its own [beg, end) slice of spill (n entries,
+// needed only when n > kAkListCap): no view is too dense.
+struct AkEntry {
+    float px, py, r;
+    uint32_t key; // level << 28 | y << 14 | x (the level's pixel; sides <= kAkMaxSide)
+};
+constexpr int kAkKeyLevelShift = 28;
+constexpr int kAkMaxSide = 16383;  // 14 bits of x and of y in AkEntry.key
+constexpr int kAkListCap = 9216;   // 147,456 B of LDS: one view's list
 struct AkCandArgs {
     const AkPlane *planes;
     const float *pool;
@@ -103,7 +111,7 @@ struct AkCandArgs {
     dp_keypoint *kp;
     int32_t *kv;
     uint8_t *keep;
-    uint32_t *err;
+    AkEntry *spill;
 };
 hipError_t launch_akz_candidates(const AkCandArgs &a, hipStream_t s);
 

@@ -48,7 +48,9 @@ __device__ __forceinline__ int ak_r101(int i, int n)
         i = -i;
     if (i >= n)
         i = 2 * (n - 1) - i;
-    return i;
+    // a tile that overhangs a plane narrower than itself asks for i > 2 (n - 1)
+    // (values no output uses): keep the read inside the plane
+    return max(i, 0);
 }
 
 } // namespace
@@ -897,37 +899,16 @@ __device__ __forceinline__ int64_t ak_lower(const int64_t *c, int64_t lo, int64_
     return lo;
 }
 
-struct AkEntry {
-    float px, py, r;
-    uint32_t key; // level << 27 | y << 14 | x (the level's pixel)
-};
-constexpr int kAkListCap = 9216; // 147,456 B of LDS: one view's list
-
-__global__ __launch_bounds__(64) void akz_seq_kernel(AkCandArgs a)
+// One view's walk over its candidates [beg, end) with the list at L: the LDS
+// array (kSpill = false) or the view's slice of the global spill buffer
+// (kSpill = true: four 64-entry blocks in flight per step, to hide the
+// latency of global loads).  One wave writes and reads the list, and the
+// barrier after each update orders the writes before the next reads in
+// either memory.
+template <bool kSpill>
+__device__ __forceinline__ void akz_seq_view(const AkCandArgs &a, int z, int lane, int64_t beg, int64_t end, AkEntry *L)
 {
-    __shared__ AkEntry L[kAkListCap];
-    const int z = blockIdx.x;
-    const int lane = threadIdx.x;
-    // the view's candidates: global Ldet indices of its planes (view-major)
-    int64_t vlo = -1, vhi = -1;
-    for (int i = 0; i < kAkLevels; ++i) {
-        const AkPlane &P = a.planes[z * kAkLevels + i];
-        if (P.w == 0)
-            continue;
-        if (vlo < 0)
-            vlo = P.det_base;
-        vhi = P.det_base + (int64_t)P.w * P.h;
-    }
-    if (vlo < 0)
-        return;
-    const int64_t beg = ak_lower(a.cand, 0, a.n, vlo), end = ak_lower(a.cand, beg, a.n, vhi);
-    if (end - beg > kAkListCap) {
-        if (lane == 0)
-            atomicMax(a.err, (uint32_t)(end - beg));
-        for (int64_t ci = beg + lane; ci < end; ci += 64)
-            a.keep[ci] = 0;
-        return;
-    }
+    constexpr int kB = kSpill ? 4 : 1;
     int na = 0;
     for (int64_t ci = beg; ci < end; ++ci) {
         const int64_t g = a.cand[ci];
@@ -945,22 +926,29 @@ __global__ __launch_bounds__(64) void akz_seq_kernel(AkCandArgs a)
         const float S = P.esigma * 1.5f, S2 = S * S;
         const float px = (float)cx * ra, py = (float)cy * ra;
         int hit = -1;
-        for (int b0 = 0; b0 < na && hit < 0; b0 += 64) {
-            const int e = b0 + lane;
-            bool m = false;
-            if (e < na) {
-                const AkEntry q = L[e];
-                const int ql = (int)(q.key >> 27);
-                if (ql == lev - 1 || ql == lev) {
-                    const float dx = px - q.px, dy = py - q.py;
-                    m = dx * dx + dy * dy <= S2;
+        for (int b0 = 0; b0 < na && hit < 0; b0 += 64 * kB) {
+            bool m[kB];
+#pragma unroll
+            for (int u = 0; u < kB; ++u) {
+                const int e = b0 + u * 64 + lane;
+                m[u] = false;
+                if (e < na) {
+                    const AkEntry q = L[e];
+                    const int ql = (int)(q.key >> kAkKeyLevelShift);
+                    if (ql == lev - 1 || ql == lev) {
+                        const float dx = px - q.px, dy = py - q.py;
+                        m[u] = dx * dx + dy * dy <= S2;
+                    }
                 }
             }
-            const unsigned long long bal = __ballot(m);
-            if (bal)
-                hit = b0 + __builtin_ctzll(bal);
+#pragma unroll
+            for (int u = 0; u < kB; ++u) {
+                const unsigned long long bal = __ballot(m[u]);
+                if (bal && hit < 0)
+                    hit = b0 + u * 64 + __builtin_ctzll(bal);
+            }
         }
-        const AkEntry ne{px, py, r, (uint32_t)lev << 27 | (uint32_t)cy << 14 | (uint32_t)cx};
+        const AkEntry ne{px, py, r, (uint32_t)lev << kAkKeyLevelShift | (uint32_t)cy << 14 | (uint32_t)cx};
         if (hit < 0) {
             if (lane == 0)
                 L[na] = ne;
@@ -973,13 +961,14 @@ __global__ __launch_bounds__(64) void akz_seq_kernel(AkCandArgs a)
     // the upper-level pass and the subpixel refinement, one lane per entry
     for (int i = lane; i < na; i += 64) {
         const AkEntry q = L[i];
-        const int lev = (int)(q.key >> 27), cy = (int)((q.key >> 14) & 0x1fffu), cx = (int)(q.key & 0x3fffu);
+        const int lev = (int)(q.key >> kAkKeyLevelShift), cy = (int)((q.key >> 14) & 0x3fffu),
+                  cx = (int)(q.key & 0x3fffu);
         const AkPlane &P = a.planes[z * kAkLevels + lev];
         const float S = P.esigma * 1.5f, S2 = S * S;
         bool drop = false;
         for (int j = i + 1; j < na && !drop; ++j) {
             const AkEntry t = L[j];
-            if ((int)(t.key >> 27) != lev + 1)
+            if ((int)(t.key >> kAkKeyLevelShift) != lev + 1)
                 continue;
             const float dx = q.px - t.px, dy = q.py - t.py;
             drop = dx * dx + dy * dy <= S2 && q.r < t.r;
@@ -1014,6 +1003,33 @@ __global__ __launch_bounds__(64) void akz_seq_kernel(AkCandArgs a)
     }
     for (int64_t ci = beg + na + lane; ci < end; ci += 64)
         a.keep[ci] = 0;
+}
+
+__global__ __launch_bounds__(64) void akz_seq_kernel(AkCandArgs a)
+{
+    __shared__ AkEntry L[kAkListCap];
+    const int z = blockIdx.x;
+    const int lane = threadIdx.x;
+    // the view's candidates: global Ldet indices of its planes (view-major)
+    int64_t vlo = -1, vhi = -1;
+    for (int i = 0; i < kAkLevels; ++i) {
+        const AkPlane &P = a.planes[z * kAkLevels + i];
+        if (P.w == 0)
+            continue;
+        if (vlo < 0)
+            vlo = P.det_base;
+        vhi = P.det_base + (int64_t)P.w * P.h;
+    }
+    if (vlo < 0)
+        return;
+    const int64_t beg = ak_lower(a.cand, 0, a.n, vlo), end = ak_lower(a.cand, beg, a.n, vhi);
+    // the list never grows past the candidate count, so a view within the cap
+    // fits in LDS; a larger one keeps its list in spill[beg, end), which no
+    // other view's slice overlaps
+    if (end - beg > kAkListCap)
+        akz_seq_view<true>(a, z, lane, beg, end, a.spill + beg);
+    else
+        akz_seq_view<false>(a, z, lane, beg, end, L);
 }
 
 hipError_t launch_akz_candidates(const AkCandArgs &a, hipStream_t s)

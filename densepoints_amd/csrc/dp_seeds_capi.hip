@@ -58,7 +58,7 @@ struct dp_seedgen {
     DevBuf<uint32_t> akz_seg;
     DevBuf<int64_t> akz_cand;
     DevBuf<int32_t> akz_vids;
-    DevBuf<uint32_t> akz_err; // a view's candidates overflowed the suppression list
+    DevBuf<dpk::AkEntry> akz_spill; // suppression lists of views above the LDS cap
     int desc_words = 8; // 8 (ORB) or 16 (AKAZE) dwords per descriptor
     std::vector<dpk::SeedPair> h_pairs;
     std::vector<dpk::KnnJob> h_jobs;
@@ -123,7 +123,7 @@ void dp_seedgen_free(dp_seedgen *s)
     s->akz_seg.release();
     s->akz_cand.release();
     s->akz_vids.release();
-    s->akz_err.release();
+    s->akz_spill.release();
     delete s;
 }
 
@@ -477,6 +477,15 @@ static int cell_filter(dp_ctx *c, dp_seedgen *s, const dp_matcher_options &mo, c
 // (view, level, y, x) order, cells filtered as for ORB.  Leaves s->kp_b /
 // kv_b / desc (16 dwords per keypoint) and the host keypoints.
 // ---------------------------------------------------------------------------
+// dp_probe_akaze_plane / dp_probe_orb_level: seed generation stops after the
+// image stage and hands out one plane (include/densepoints_probe.h)
+struct SeedProbe {
+    int view, level, which;
+    void *out;        // host; null asks for the size only
+    int64_t cap;      // elements out holds
+    int32_t w = 0, h = 0;
+};
+
 struct AkGeom {
     int n = 0;
     int w[dpk::kAkLevels], h[dpk::kAkLevels], octave[dpk::kAkLevels], ss[dpk::kAkLevels];
@@ -504,7 +513,7 @@ static AkGeom akaze_geom(int W, int H)
 
 static int akaze_stage(dp_ctx *c, dp_seedgen *s, const dp_matcher_options &mo, const std::vector<int32_t> &vw,
                        const std::vector<int32_t> &vh, hipEvent_t e0, hipEvent_t e1, hipEvent_t e2, dp_seed_stats &S,
-                       int64_t *n_out, std::vector<int32_t> &h_kv)
+                       int64_t *n_out, std::vector<int32_t> &h_kv, SeedProbe *probe = nullptr)
 {
     using namespace dpk;
     hipStream_t st = c->stream;
@@ -512,9 +521,22 @@ static int akaze_stage(dp_ctx *c, dp_seedgen *s, const dp_matcher_options &mo, c
     for (int v = 0; v < V; ++v)
         if (vw[v] < 16 || vh[v] < 16)
             return fail(c, DP_E_ARG, "dp_generate_seeds: AKAZE needs views of at least 16 x 16 px");
+    for (int v = 0; v < V; ++v) // a suppression-list key packs 14 bits of x and of y
+        if (vw[v] > kAkMaxSide || vh[v] > kAkMaxSide)
+            return fail(c, DP_E_ARG, "dp_generate_seeds: AKAZE takes views of at most 16383 x 16383 px");
     std::vector<AkGeom> geo(V);
     for (int v = 0; v < V; ++v)
         geo[v] = akaze_geom(vw[v], vh[v]);
+    if (probe) {
+        if (probe->level < 0 || probe->level >= geo[probe->view].n || probe->which < 0 || probe->which > 3)
+            return fail(c, DP_E_ARG, "dp_probe_akaze_plane: no such level or plane");
+        probe->w = geo[probe->view].w[probe->level];
+        probe->h = geo[probe->view].h[probe->level];
+        if (!probe->out)
+            return DP_OK;
+        if (probe->cap < (int64_t)probe->w * probe->h)
+            return fail(c, DP_E_ARG, "dp_probe_akaze_plane: output too small");
+    }
     // FED time steps per level (the same esigma sequence for every view)
     const AkGeom full = akaze_geom(1 << 20, 1 << 20);
     std::vector<std::vector<float>> tau(kAkLevels);
@@ -682,6 +704,18 @@ static int akaze_stage(dp_ctx *c, dp_seedgen *s, const dp_matcher_options &mo, c
                 DP_HIP(c, launch_akz_copy(a, i, src, kLt, nv, mw[i], mh[i], st));
             DP_HIP(c, deriv(i, kT3));
         }
+        if (probe) {
+            if (probe->view < v0 || probe->view >= v1) {
+                v0 = v1;
+                continue;
+            }
+            const AkPlane &P = planes[(size_t)(probe->view - v0) * kAkLevels + probe->level];
+            const int64_t n = (int64_t)P.w * P.h;
+            DP_HIP(c, hipMemcpyAsync(probe->out, s->akz_pool.p + P.off + probe->which * n, n * sizeof(float),
+                                     hipMemcpyDeviceToHost, st));
+            DP_HIP(c, hipStreamSynchronize(st));
+            return DP_OK;
+        }
         // extrema candidates in (view, level, y, x) order: counts per
         // (row, 256-px segment), their exclusive scan, the indices
         uint32_t *seg_cnt = s->akz_seg.p, *seg_off = s->akz_seg.p + segs + 1;
@@ -701,8 +735,8 @@ static int akaze_stage(dp_ctx *c, dp_seedgen *s, const dp_matcher_options &mo, c
         for (int z = 0; z < nv; ++z)
             vids[z] = v0 + z;
         DP_HIP(c, s->akz_vids.reserve(nv));
-        DP_HIP(c, s->akz_err.reserve(1));
-        DP_HIP(c, hipMemsetAsync(s->akz_err.p, 0, sizeof(uint32_t), st));
+        if (n_cand > kAkListCap) // only then can a view's list outgrow LDS
+            DP_HIP(c, s->akz_spill.reserve(n_cand));
         DP_HIP(c, hipMemcpyAsync(s->akz_vids.p, vids.data(), nv * 4, hipMemcpyHostToDevice, st));
         DP_HIP(c, s->kp_a.reserve(n_cand + 1));
         DP_HIP(c, s->kv_a.reserve(n_cand + 1));
@@ -711,7 +745,7 @@ static int akaze_stage(dp_ctx *c, dp_seedgen *s, const dp_matcher_options &mo, c
         DP_HIP(c, s->flag.reserve(n_cand + 1));
         DP_HIP(c, s->idx_a.reserve(n_cand + 1));
         AkCandArgs ca{s->akz_planes.p, s->akz_pool.p, s->akz_cand.p, n_cand, nv, s->akz_vids.p, s->kp_b.p,
-                      s->kv_b.p, s->flag.p, s->akz_err.p};
+                      s->kv_b.p, s->flag.p, s->akz_spill.p};
         DP_HIP(c, launch_akz_candidates(ca, st));
         {
             hipcub::CountingInputIterator<int32_t> iota(0);
@@ -719,13 +753,8 @@ static int akaze_stage(dp_ctx *c, dp_seedgen *s, const dp_matcher_options &mo, c
                                                         (int)n_cand, st));
         }
         int64_t n_det = 0;
-        uint32_t akz_err = 0;
         DP_HIP(c, hipMemcpyAsync(&n_det, s->n_sel.p, sizeof(int64_t), hipMemcpyDeviceToHost, st));
-        DP_HIP(c, hipMemcpyAsync(&akz_err, s->akz_err.p, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
         DP_HIP(c, hipStreamSynchronize(st));
-        if (akz_err)
-            return fail(c, DP_E_OOM, "AKAZE: a view has " + std::to_string(akz_err) +
-                                         " extrema candidates, more than the suppression list holds (9216)");
         DP_HIP(c, dpk::launch_gather_kp(s->kp_b.p, s->kv_b.p, s->idx_a.p, n_det, s->kp_a.p, s->kv_a.p, st));
         n_det_total += n_det;
         int64_t n_f = 0;
@@ -771,8 +800,59 @@ static int akaze_stage(dp_ctx *c, dp_seedgen *s, const dp_matcher_options &mo, c
     return DP_OK;
 }
 
+static int generate_seeds(dp_ctx *c, const dp_matcher_options *mo_in, const double **xyz_out, int64_t *n_out,
+                          dp_seed_stats *stats, SeedProbe *probe);
+
 extern "C" int dp_generate_seeds(dp_ctx *c, const dp_matcher_options *mo_in, const double **xyz_out, int64_t *n_out,
                                  dp_seed_stats *stats)
+{
+    return generate_seeds(c, mo_in, xyz_out, n_out, stats, nullptr);
+}
+
+// The probes run seed generation's own launch sequence up to the planes they
+// return (no second copy of it), with the options' defaults but for the
+// detector and, for ORB, the pyramid's shape.
+extern "C" int dp_probe_akaze_plane(dp_ctx *c, int view, int level, int which, float *out, int64_t cap, int32_t *wh)
+{
+    if (!c)
+        return DP_E_ARG;
+    if (!wh || view < 0 || view >= c->V)
+        return fail(c, DP_E_ARG, "dp_probe_akaze_plane: bad view or null size");
+    dp_matcher_options mo;
+    dp_default_matcher_options(&mo);
+    mo.detector_type = DP_DETECTOR_AKAZE;
+    SeedProbe pr{view, level, which, out, cap};
+    const double *xyz = nullptr;
+    int64_t n = 0;
+    const int rc = generate_seeds(c, &mo, &xyz, &n, nullptr, &pr);
+    wh[0] = pr.w;
+    wh[1] = pr.h;
+    return rc;
+}
+
+extern "C" int dp_probe_orb_level(dp_ctx *c, int view, int level, int n_levels, double scale_factor, uint8_t *out,
+                                  int64_t cap, int32_t *wh)
+{
+    if (!c)
+        return DP_E_ARG;
+    if (!wh || view < 0 || view >= c->V || level < 0 || level >= n_levels)
+        return fail(c, DP_E_ARG, "dp_probe_orb_level: bad view or level, or null size");
+    dp_matcher_options mo;
+    dp_default_matcher_options(&mo);
+    mo.detector_type = DP_DETECTOR_ORB;
+    mo.n_levels = n_levels;
+    mo.scale_factor = scale_factor;
+    SeedProbe pr{view, level, 0, out, cap};
+    const double *xyz = nullptr;
+    int64_t n = 0;
+    const int rc = generate_seeds(c, &mo, &xyz, &n, nullptr, &pr);
+    wh[0] = pr.w;
+    wh[1] = pr.h;
+    return rc;
+}
+
+static int generate_seeds(dp_ctx *c, const dp_matcher_options *mo_in, const double **xyz_out, int64_t *n_out,
+                          dp_seed_stats *stats, SeedProbe *probe)
 {
     if (!c)
         return DP_E_ARG;
@@ -810,8 +890,8 @@ extern "C" int dp_generate_seeds(dp_ctx *c, const dp_matcher_options *mo_in, con
     DP_HIP(c, s->n_sel.reserve(1));
     if (mo.detector_type == DP_DETECTOR_AKAZE) {
         s->desc_words = dpk::kAkDescWords;
-        rc = akaze_stage(c, s, mo, vw, vh, t0.e, t1.e, t2.e, S, &n5, h_kv);
-        if (rc != DP_OK)
+        rc = akaze_stage(c, s, mo, vw, vh, t0.e, t1.e, t2.e, S, &n5, h_kv, probe);
+        if (rc != DP_OK || probe)
             return rc;
     } else {
     s->desc_words = 8;
@@ -862,6 +942,18 @@ extern "C" int dp_generate_seeds(dp_ctx *c, const dp_matcher_options *mo_in, con
     DP_HIP(c, dpk::launch_orb_gray(s->planes0.p, g, lv[0].w > 0 ? max_w : 0, max_h, st));
     for (int l = 1; l < L; ++l)
         DP_HIP(c, dpk::launch_orb_resize(g, l, lw[l], lh[l], st));
+    if (probe) {
+        const dpk::OrbLevel &o = lv[(size_t)probe->view * L + probe->level];
+        probe->w = o.w;
+        probe->h = o.h;
+        if (!probe->out)
+            return DP_OK;
+        if (probe->cap < (int64_t)o.w * o.h)
+            return fail(c, DP_E_ARG, "dp_probe_orb_level: output too small");
+        DP_HIP(c, hipMemcpyAsync(probe->out, s->gray.p + o.off, (size_t)o.w * o.h, hipMemcpyDeviceToHost, st));
+        DP_HIP(c, hipStreamSynchronize(st));
+        return DP_OK;
+    }
     for (int l = 0; l < L; ++l)
         DP_HIP(c, dpk::launch_orb_fast(g, l, mo.fast_threshold, s->score.p, lw[l], lh[l], st));
     DP_HIP(c, hipMemsetAsync(s->row_cnt.p, 0, (size_t)(rows + 1) * sizeof(int64_t), st));

@@ -324,6 +324,24 @@ class Engine:
         self._check(lib.dp_read_gray(self._ctx, view, ptr(out)))
         return out
 
+    def probe_akaze_plane(self, view: int, level: int, which: int) -> np.ndarray:
+        """One fp32 plane (0 Lt, 1 Lx, 2 Ly, 3 Ldet) of the AKAZE scale space
+        seed generation builds of the views set (dp_probe_akaze_plane)."""
+        wh = np.zeros(2, dtype=np.int32)
+        self._check(lib.dp_probe_akaze_plane(self._ctx, view, level, which, None, 0, ptr(wh)))
+        out = np.zeros((int(wh[1]), int(wh[0])), dtype=np.float32)
+        self._check(lib.dp_probe_akaze_plane(self._ctx, view, level, which, ptr(out), out.size, ptr(wh)))
+        return out
+
+    def probe_orb_level(self, view: int, level: int, n_levels: int, scale_factor: float = 1.2) -> np.ndarray:
+        """One u8 level of the gray pyramid ORB detection builds (dp_probe_orb_level)."""
+        wh = np.zeros(2, dtype=np.int32)
+        self._check(lib.dp_probe_orb_level(self._ctx, view, level, n_levels, scale_factor, None, 0, ptr(wh)))
+        out = np.zeros((int(wh[1]), int(wh[0])), dtype=np.uint8)
+        self._check(lib.dp_probe_orb_level(self._ctx, view, level, n_levels, scale_factor, ptr(out), out.size,
+                                           ptr(wh)))
+        return out
+
     def fast_refine(self, patches: np.ndarray, cell: int, mode: int = N.MODE_FAST_REFINE) -> np.ndarray:
         """Performance-mode refine (or one fast evaluation) in place; accept flags."""
         return self.refine(patches, cell, mode)

@@ -37,6 +37,17 @@ int dp_probe_recip_f32_device(const float *x, int n, float *out);
 int dp_probe_grad_q24_device(const double *dncc, int n, int32_t *out);
 /* 32-bit LDS reads at 2-byte alignment on the device (out: 4 x 64 words) */
 int dp_probe_lds_unaligned_device(uint32_t *out256);
+/* Whole planes of seed generation's image stage on the views set on the
+ * context, borders included (keypoints lie well inside and cannot show them).
+ * Both run dp_generate_seeds' own launch sequence and stop after the planes.
+ * out = NULL asks for the size only; wh receives (w, h); cap = elements of out.
+ * AKAZE scale space: view v, evolution level l, which = 0 Lt, 1 Lx, 2 Ly,
+ * 3 Ldet (fp32); DP_E_ARG where the view has no such level. */
+int dp_probe_akaze_plane(dp_ctx *c, int view, int level, int which, float *out, int64_t cap, int32_t wh[2]);
+/* ORB's gray pyramid (u8) of n_levels levels at scale_factor: cvtColor at
+ * level 0, then the INTER_LINEAR resizes level to level */
+int dp_probe_orb_level(dp_ctx *c, int view, int level, int n_levels, double scale_factor, uint8_t *out,
+                       int64_t cap, int32_t wh[2]);
 /* diagnostic builds (-DDP_STAMPS) only: per-phase s_memtime cycle sums of the
  * refine kernel since the last call (0 maps, 1 texture 0, 2 other views,
  * 3 NCC finish, 6 patches, 7 whole patch); DP_E_STATE otherwise */

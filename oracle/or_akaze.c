@@ -487,6 +487,16 @@ static int ak_inside(const AkLevel *L, int x, int y)
     return lx >= 0 && rx < L->w && uy >= 0 && dy < L->h;
 }
 
+/* the candidate rule of Find_Scale_Space_Extrema at an interior pixel */
+static int ak_is_cand(const AkLevel *L, int x, int y, float thr)
+{
+    const int w = L->w;
+    const float *p = L->Ldet + (size_t)y * w + x;
+    const float v = p[0];
+    return v > thr && v >= 0.00001f && v > p[-1] && v > p[1] && v > p[-w - 1] && v > p[-w] && v > p[-w + 1] &&
+           v > p[w - 1] && v > p[w] && v > p[w + 1] && ak_inside(L, x, y);
+}
+
 static int ak_extrema(const AkLevel *lv, int n, float thr, or_keypoint **out)
 {
     int cap = 4096, m = 0;
@@ -496,10 +506,7 @@ static int ak_extrema(const AkLevel *lv, int n, float thr, or_keypoint **out)
         const int w = L->w;
         for (int y = 1; y < L->h - 1; ++y)
             for (int x = 1; x < w - 1; ++x) {
-                const float *p = L->Ldet + (size_t)y * w + x;
-                const float v = p[0];
-                if (v > thr && v >= 0.00001f && v > p[-1] && v > p[1] && v > p[-w - 1] && v > p[-w] && v > p[-w + 1] &&
-                    v > p[w - 1] && v > p[w] && v > p[w + 1] && ak_inside(L, x, y)) {
+                if (ak_is_cand(L, x, y, thr)) {
                     if (m == cap) {
                         cap *= 2;
                         c = (AkCand *)realloc(c, sizeof(AkCand) * (size_t)cap);
@@ -507,7 +514,7 @@ static int ak_extrema(const AkLevel *lv, int n, float thr, or_keypoint **out)
                     c[m].level = i;
                     c[m].x = x;
                     c[m].y = y;
-                    c[m].r = v;
+                    c[m].r = L->Ldet[(size_t)y * w + x];
                     ++m;
                 }
             }
@@ -784,6 +791,28 @@ int or_akaze_plane(const uint8_t *bgr, int W, int H, int level, int which, float
     memcpy(out, src, sizeof(float) * (size_t)lv[level].w * lv[level].h);
     ak_free(lv, n);
     return 0;
+}
+
+/* test access: the extrema candidates of a view before the sequential
+ * suppression (ak_extrema's rule), counted per level; returns their sum */
+int64_t or_akaze_candidates(const uint8_t *bgr, int W, int H, float thr, int64_t *per_level)
+{
+    AkLevel lv[AK_MAX_LEVELS];
+    const int n = ak_scale_space(bgr, W, H, lv, NULL);
+    if (n <= 0)
+        return -1;
+    int64_t total = 0;
+    for (int i = 0; i < n; ++i) {
+        int64_t m = 0;
+        for (int y = 1; y < lv[i].h - 1; ++y)
+            for (int x = 1; x < lv[i].w - 1; ++x)
+                m += ak_is_cand(&lv[i], x, y, thr);
+        if (per_level)
+            per_level[i] = m;
+        total += m;
+    }
+    ak_free(lv, n);
+    return total;
 }
 
 /* test access: the halfsample (cv::resize INTER_AREA) of one fp32 plane */

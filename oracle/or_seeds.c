@@ -912,3 +912,33 @@ int64_t or_seeds_pair(const or_seeds *r, int p, int32_t *first_second, int32_t *
 }
 
 void or_seeds_points(const or_seeds *r, double *xyz) { memcpy(xyz, r->xyz, sizeof(double) * 3 * (size_t)r->n_points); }
+
+/* test access: the gray plane of ORB pyramid level `level` of one BGR8 view
+ * (cvtColor, then INTER_LINEAR resizes level to level); wh = its (w, h).
+ * out may be NULL to ask for the size only.  Returns 0, or -1 when a level
+ * would be smaller than 4 px. */
+int or_orb_level(const uint8_t *bgr, int W, int H, double scale_factor, int n_levels, int level, uint8_t *out,
+                 int32_t *wh)
+{
+    if (n_levels < 1 || n_levels > 16 || level < 0 || level >= n_levels)
+        return -1;
+    or_matcher_options mo;
+    memset(&mo, 0, sizeof(mo));
+    mo.n_features = 1;
+    mo.n_levels = n_levels;
+    mo.scale_factor = scale_factor;
+    Level lv[16];
+    memset(lv, 0, sizeof(lv));
+    const int rc = build_levels(bgr, W, H, &mo, lv);
+    if (rc == 0) {
+        wh[0] = lv[level].w;
+        wh[1] = lv[level].h;
+        if (out)
+            memcpy(out, lv[level].img, (size_t)lv[level].w * lv[level].h);
+    }
+    for (int l = 0; l < n_levels; ++l) {
+        free(lv[l].img);
+        free(lv[l].blur);
+    }
+    return rc;
+}

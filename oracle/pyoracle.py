@@ -131,6 +131,8 @@ def _load():
         "or_akaze_levels": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, P, P]),
         "or_akaze_plane": (ctypes.c_int, [P, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, P, P]),
         "or_akaze_halfsample": (ctypes.c_int, [P, ctypes.c_int, ctypes.c_int, P, ctypes.c_int, ctypes.c_int]),
+        "or_akaze_candidates": (ctypes.c_int64, [P, ctypes.c_int, ctypes.c_int, ctypes.c_float, P]),
+        "or_orb_level": (ctypes.c_int, [P, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_int, P, P]),
     }
     for k, (r, a) in sig.items():
         f = getattr(L, k)
@@ -583,6 +585,30 @@ def akaze_plane(img_bgr: np.ndarray, level: int, which: int):
     if lib.or_akaze_plane(_p(img), W, H, level, which, _p(out), _p(kc)) != 0:
         raise ValueError("or_akaze_plane failed")
     return out, kc[: len(info)]
+
+
+def akaze_candidates(img_bgr: np.ndarray, threshold: float) -> np.ndarray:
+    """extrema candidates of a BGR8 view per level, before the sequential
+    suppression (ak_extrema's rule, the descriptor border included)"""
+    img = np.ascontiguousarray(img_bgr, dtype=np.uint8)
+    H, W = img.shape[:2]
+    info, _ = akaze_levels(W, H)
+    per = np.zeros(16, dtype=np.int64)
+    if lib.or_akaze_candidates(_p(img), W, H, threshold, _p(per)) < 0:
+        raise ValueError("or_akaze_candidates failed")
+    return per[: len(info)]
+
+
+def orb_level(img_bgr: np.ndarray, level: int, n_levels: int, scale_factor: float = 1.2) -> np.ndarray:
+    """the gray plane of ORB pyramid level `level` of a BGR8 view (u8)"""
+    img = np.ascontiguousarray(img_bgr, dtype=np.uint8)
+    H, W = img.shape[:2]
+    wh = np.zeros(2, dtype=np.int32)
+    if lib.or_orb_level(_p(img), W, H, scale_factor, n_levels, level, None, _p(wh)) != 0:
+        raise ValueError("or_orb_level: a level is smaller than 4 px")
+    out = np.zeros((int(wh[1]), int(wh[0])), dtype=np.uint8)
+    lib.or_orb_level(_p(img), W, H, scale_factor, n_levels, level, _p(out), _p(wh))
+    return out
 
 
 def fundamental_matrix(P1, P2) -> np.ndarray:
