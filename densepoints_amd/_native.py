@@ -104,6 +104,23 @@ class DpGeneration(ctypes.Structure):
     ]
 
 
+class DpIterateStats(ctypes.Structure):
+    """dp_iterate_stats: one expand-filter round of dp_densify_iterate."""
+    _fields_ = [
+        ("offered", ctypes.c_int64),
+        ("reinserted", ctypes.c_int64),
+        ("patches", ctypes.c_int64),
+        ("filtered_out", ctypes.c_int64),
+        ("candidates", ctypes.c_int64),
+        ("evals", ctypes.c_int64),
+        ("generations", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
+        ("refine_ms", ctypes.c_double),
+        ("filter_ms", ctypes.c_double),
+        ("total_ms", ctypes.c_double),
+    ]
+
+
 class DpFilterOptions(ctypes.Structure):
     _fields_ = [
         ("passes", ctypes.c_int32),
@@ -228,6 +245,10 @@ SIGNATURES = [
     ("dp_densify_partition_async", _I, [_P, _P, _I, _I, _P, _P, _P]),
     ("dp_densify_refine_share_async", _I, [_P, _P, _P, ctypes.c_int64, _P, ctypes.c_int64, _P]),
     ("dp_densify_commit_gathered_device", _I, [_P, _P, _P, ctypes.c_int64, _I, _P, _P]),
+    ("dp_densify_resume", _I, [_P, _P, ctypes.c_int64, _P, _P]),
+    ("dp_densify_resume_device", _I, [_P, _P, ctypes.c_int64, _P, _P, _P]),
+    ("dp_densify_store_device", _I, [_P, _P, _P]),
+    ("dp_densify_iterate", _I, [_P, _P, _I, _I, _P, _P, _P, _P, _P]),
     ("dp_default_filter_options", None, [_P]),
     ("dp_filter_patches", _I, [_P, _P, ctypes.c_int64, _P, _P]),
     ("dp_filter_patches_device", _I, [_P, _P, ctypes.c_int64, _P, _P, _P]),
@@ -265,6 +286,7 @@ SIGNATURES = [
     ("dp_probe_grad_q24_device", _I, [_P, _I, _P]),
     ("dp_probe_lds_unaligned_device", _I, [_P]),
     ("dp_debug_stamps", _I, [_P]),
+    ("dp_probe_keep_gather", _I, [_P, _P, ctypes.c_int64, _P, _P, _P]),
     ("dp_probe_akaze_plane", _I, [_P, _I, _I, _I, _P, ctypes.c_int64, _P]),
     ("dp_probe_orb_level", _I, [_P, _I, _I, _I, _D, _P, ctypes.c_int64, _P]),
 ]

@@ -392,6 +392,91 @@ __global__ void scatter_slots_kernel(const dp_patch *recs, int64_t stride, int w
     }
 }
 
+// -- survivors of a filtered store (dp_densify_iterate): the resolve / scan /
+// append scheme over host-sized chunks.  keep_count_kernel: chunk b's count of
+// nonzero flags; keep_scan_kernel (one block): counts -> exclusive offsets and
+// the total; keep_gather_kernel: the kept records, unchanged, in index order.
+__global__ __launch_bounds__(256) void keep_count_kernel(const uint8_t *keep, int64_t n, uint32_t *bsum)
+{
+    __shared__ uint32_t wc[4];
+    const int64_t C = bfs_chunk(n);
+    const int64_t lo = (int64_t)blockIdx.x * C;
+    const int64_t hi = lo + C < n ? lo + C : n;
+    uint32_t total = 0;
+    for (int64_t base = lo; base < hi; base += 256) {
+        const int64_t i = base + threadIdx.x;
+        const int flag = i < hi && keep[i];
+        total += (uint32_t)__popcll(__ballot(flag));
+    }
+    if ((threadIdx.x & 63) == 0)
+        wc[threadIdx.x >> 6] = total;
+    __syncthreads();
+    if (threadIdx.x == 0)
+        bsum[blockIdx.x] = wc[0] + wc[1] + wc[2] + wc[3];
+}
+
+__global__ __launch_bounds__(kBfsBlocks) void keep_scan_kernel(uint32_t *bsum, unsigned long long *total_out)
+{
+    __shared__ uint32_t ws[kBfsBlocks / 64];
+    const int t = threadIdx.x;
+    const uint32_t v = bsum[t];
+    uint32_t x = v;
+    for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t y = __shfl_up(x, o);
+        if ((t & 63) >= o)
+            x += y;
+    }
+    if ((t & 63) == 63)
+        ws[t >> 6] = x;
+    __syncthreads();
+    if (t < 64) {
+        uint32_t z = t < kBfsBlocks / 64 ? ws[t] : 0u;
+        for (int o = 1; o < 64; o <<= 1) {
+            const uint32_t y = __shfl_up(z, o);
+            if (t >= o)
+                z += y;
+        }
+        if (t < kBfsBlocks / 64)
+            ws[t] = z; // inclusive over waves
+    }
+    __syncthreads();
+    const uint32_t before = (t >> 6) ? ws[(t >> 6) - 1] : 0u;
+    bsum[t] = before + x - v; // exclusive offset of chunk t
+    if (t == 0)
+        *total_out = (unsigned long long)ws[kBfsBlocks / 64 - 1];
+}
+
+__global__ __launch_bounds__(256) void keep_gather_kernel(const dp_patch *src, const uint8_t *keep, int64_t n,
+                                                          const uint32_t *bsum, dp_patch *dst, int64_t dst_cap)
+{
+    __shared__ uint32_t wc[4];
+    const int64_t C = bfs_chunk(n);
+    const int64_t lo = (int64_t)blockIdx.x * C;
+    const int64_t hi = lo + C < n ? lo + C : n;
+    if (lo >= hi)
+        return;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    int64_t at = (int64_t)bsum[blockIdx.x];
+    for (int64_t step = lo; step < hi; step += 256) {
+        const int64_t i = step + threadIdx.x;
+        const bool f = i < hi && keep[i];
+        const uint64_t m = __ballot(f);
+        if (lane == 0)
+            wc[wv] = (uint32_t)__popcll(m);
+        __syncthreads();
+        uint32_t below = 0, cnt = 0;
+        for (int w = 0; w < 4; ++w) {
+            below += w < wv ? wc[w] : 0u;
+            cnt += wc[w];
+        }
+        const int64_t pos = at + below + lanes_below(m);
+        if (f && pos < dst_cap)
+            dst[pos] = src[i];
+        at += cnt;
+        __syncthreads();
+    }
+}
+
 __global__ void bfs_set_state_kernel(GenDev *dst, GenDev v)
 {
     if (threadIdx.x == 0)
@@ -426,6 +511,23 @@ hipError_t launch_bfs_organize(const BfsArgs &a, hipStream_t s)
     hipLaunchKernelGGL(bfs_resolve_kernel, dim3(kBfsBlocks), b, 0, s, a);
     hipLaunchKernelGGL(bfs_scan_kernel, dim3(1), dim3(kBfsBlocks), 0, s, a);
     hipLaunchKernelGGL(bfs_append_kernel, dim3(kBfsBlocks), b, 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_keep_count(const uint8_t *keep, int64_t n, uint32_t *bsum, unsigned long long *total_out,
+                             hipStream_t s)
+{
+    hipLaunchKernelGGL(keep_count_kernel, dim3(kBfsBlocks), dim3(256), 0, s, keep, n, bsum);
+    hipLaunchKernelGGL(keep_scan_kernel, dim3(1), dim3(kBfsBlocks), 0, s, bsum, total_out);
+    return hipGetLastError();
+}
+
+hipError_t launch_keep_gather(const dp_patch *src, const uint8_t *keep, int64_t n, const uint32_t *bsum, dp_patch *dst,
+                              int64_t dst_cap, hipStream_t s)
+{
+    if (n <= 0)
+        return hipSuccess;
+    hipLaunchKernelGGL(keep_gather_kernel, dim3(kBfsBlocks), dim3(256), 0, s, src, keep, n, bsum, dst, dst_cap);
     return hipGetLastError();
 }
 

@@ -254,6 +254,11 @@ extern "C" int dp_ctx_destroy(dp_ctx *c)
             hipEventDestroy(e);
     c->gev.clear();
     c->mbox.release();
+    c->itw.release();
+    for (hipEvent_t e : c->fev)
+        if (e)
+            hipEventDestroy(e);
+    c->fev.clear();
     c->result.release();
     c->items.release();
     c->seedp.release();
@@ -1196,19 +1201,52 @@ static int result_impl(dp_ctx *c, hipStream_t s, const dp_patch **out, int64_t *
     return DP_OK;
 }
 
-extern "C" int dp_densify(dp_ctx *c, const double *seeds, int n, const dp_patch **out, int64_t *n_out,
-                          dp_densify_stats *stats)
+// every expansion generation from the state in c->g_slot to the end of the
+// BFS: device-resident (run_generations), or one host wait per generation for
+// the analytic-gradient refine.  known: the state in c->g_slot when the
+// caller has just read it (saves that loop's first status read)
+static int expand_all(dp_ctx *c, int64_t cap, hipStream_t s, dpk::GenDev *last, const dpk::GenDev *known = nullptr)
 {
-    if (!c || n < 0 || (n > 0 && !seeds) || !out || !n_out)
-        return fail(c, DP_E_ARG, "dp_densify: bad arguments");
-    if (!c->V)
-        return fail(c, DP_E_STATE, "dp_densify: no views");
-    hipSetDevice(c->device);
+    if (device_loop_ok(c))
+        return run_generations(c, INT64_MAX, cap, s, last);
+    const dp_options &o = c->opt;
+    dpk::GenDev g{};
+    unsigned long long mb[8];
+    int rc = DP_OK;
+    if (known)
+        g = *known;
+    else
+        rc = read_state(c, c->g_slot, s, &g, mb);
+    while (rc == DP_OK && g.items > 0) {
+        const int32_t nc = (int32_t)(4 * g.items);
+        DP_HIP(c, c->cand.reserve(nc));
+        DP_HIP(c, c->ok.reserve(nc));
+        if ((rc = reserve_organizer(c, nc)) != DP_OK)
+            break;
+        rc = take_refine_ms(c, &c->g_st.refine_ms);
+        if (rc == DP_OK)
+            rc = dp_fast_launch(c, c->cand.p, nc, o.expand_cell_size, DP_MODE_FAST_REFINE, c->ok.p, c->store.p, s,
+                                g.head, nullptr, o.max_pops, nullptr, densify_epi(c), g.seq0);
+        c->g_time_pending = true;
+        if (rc == DP_OK)
+            rc = organize_gen(c, c->cand.p, c->ok.p, c->g_slot, INT64_MAX, s, densify_epi(c));
+        if (rc == DP_OK)
+            rc = read_state(c, c->g_slot ^ 1, s, &g, mb);
+        c->g_slot ^= 1;
+    }
+    // the last generation's refine events (completed by its status read)
+    if (rc == DP_OK)
+        rc = take_refine_ms(c, &c->g_st.refine_ms);
+    *last = g;
+    return rc;
+}
+
+// dp_densify up to its result: the finished store stays on the device
+static int densify_core(dp_ctx *c, const double *seeds, int n)
+{
     hipStream_t s = c->stream;
     const dp_options &o = c->opt;
     const bool fast = c->fopt.densify != 0;
-    *out = nullptr;
-    *n_out = 0;
     // every buffer of the first expansion generation (<= 4 per seed patch)
     // before anything is queued on them
     const int64_t cap = std::min<int64_t>(std::max<int64_t>(4 * (int64_t)n, 1024), INT32_MAX);
@@ -1244,30 +1282,7 @@ extern "C" int dp_densify(dp_ctx *c, const double *seeds, int n, const dp_patch 
             return rc;
         c->g_slot = 1;
         dpk::GenDev g{};
-        if (device_loop_ok(c)) {
-            rc = run_generations(c, INT64_MAX, cap, s, &g);
-        } else {
-            // the analytic-gradient refine: one host wait per generation
-            unsigned long long mb[8];
-            rc = read_state(c, 1, s, &g, mb);
-            while (rc == DP_OK && g.items > 0) {
-                const int32_t nc = (int32_t)(4 * g.items);
-                DP_HIP(c, c->cand.reserve(nc));
-                DP_HIP(c, c->ok.reserve(nc));
-                if ((rc = reserve_organizer(c, nc)) != DP_OK)
-                    break;
-                rc = take_refine_ms(c, &c->g_st.refine_ms);
-                if (rc == DP_OK)
-                    rc = dp_fast_launch(c, c->cand.p, nc, o.expand_cell_size, DP_MODE_FAST_REFINE, c->ok.p, c->store.p,
-                                        s, g.head, nullptr, o.max_pops, nullptr, densify_epi(c), g.seq0);
-                c->g_time_pending = true;
-                if (rc == DP_OK)
-                    rc = organize_gen(c, c->cand.p, c->ok.p, c->g_slot, INT64_MAX, s, densify_epi(c));
-                if (rc == DP_OK)
-                    rc = read_state(c, c->g_slot ^ 1, s, &g, mb);
-                c->g_slot ^= 1;
-            }
-        }
+        rc = expand_all(c, cap, s, &g);
         if (rc != DP_OK)
             return rc;
         float f = 0.f;
@@ -1275,7 +1290,23 @@ extern "C" int dp_densify(dp_ctx *c, const double *seeds, int n, const dp_patch 
         c->g_st.refine_ms += f;
         take_state(c, g, nullptr);
     }
-    return result_impl(c, s, out, n_out, stats);
+    return DP_OK;
+}
+
+extern "C" int dp_densify(dp_ctx *c, const double *seeds, int n, const dp_patch **out, int64_t *n_out,
+                          dp_densify_stats *stats)
+{
+    if (!c || n < 0 || (n > 0 && !seeds) || !out || !n_out)
+        return fail(c, DP_E_ARG, "dp_densify: bad arguments");
+    if (!c->V)
+        return fail(c, DP_E_STATE, "dp_densify: no views");
+    hipSetDevice(c->device);
+    *out = nullptr;
+    *n_out = 0;
+    const int rc = densify_core(c, seeds, n);
+    if (rc != DP_OK)
+        return rc;
+    return result_impl(c, c->stream, out, n_out, stats);
 }
 
 // ---------------------------------------------------------------------------
@@ -1660,6 +1691,253 @@ extern "C" int dp_densify_result(dp_ctx *c, const dp_patch **out, int64_t *n_out
         return fail(c, DP_E_STATE, "dp_densify_result: no generation run");
     hipSetDevice(c->device);
     return result_impl(c, c->stream, out, n_out, stats);
+}
+
+// ---------------------------------------------------------------------------
+// resume: the BFS restarted from an existing patch set (PatchOrganizer::
+// SetSeeds, patch_organizer.cpp:70-75, on patches instead of refined seeds),
+// and the expand-filter iteration built on it (PMVS alternates expansion and
+// filtering; DESIGN.md "Iterated expand-filter").
+// ---------------------------------------------------------------------------
+
+// The offered patches are staged in c->cand with the keep flags as the
+// organizer's accept flags c->ok (sequence number = index in the input, so the
+// kept patches reach TryInsert in index order whatever the launch geometry),
+// then a per_item = 1 generation is organized without a refine: claims,
+// resolve, append (seq, parent, ACCEPTED, ComputeColor).  d_patches may be the
+// context's own store: it is only read by the staging copy, which is ordered
+// before the reset and the append on s; d_patches == c->cand.p / d_keep ==
+// c->ok.p mean "already staged" (the host form).  One host wait: the status read.
+static int resume_impl(dp_ctx *c, const dp_patch *d_patches, const uint8_t *d_keep, int64_t n, hipStream_t s,
+                       dp_generation *gen, dpk::GenDev *state = nullptr)
+{
+    if (n > 0x7fffffffll)
+        return fail(c, DP_E_OOM, "dp_densify_resume: too many patches");
+    const size_t cap = (size_t)std::max<int64_t>(n, 1);
+    // every buffer before anything is queued on it
+    if (!d_patches || d_patches != c->cand.p)
+        DP_HIP(c, c->cand.reserve(cap));
+    if (!d_keep || d_keep != c->ok.p)
+        DP_HIP(c, c->ok.reserve(cap));
+    int rc = join_streams(c, c->stream, s);
+    if (rc != DP_OK)
+        return rc;
+    if (n > 0) {
+        if (d_patches != c->cand.p)
+            DP_HIP(c, hipMemcpyAsync(c->cand.p, d_patches, sizeof(dp_patch) * (size_t)n, hipMemcpyDeviceToDevice, s));
+        if (!d_keep)
+            DP_HIP(c, hipMemsetAsync(c->ok.p, 1, (size_t)n, s));
+        else if (d_keep != c->ok.p)
+            DP_HIP(c, hipMemcpyAsync(c->ok.p, d_keep, (size_t)n, hipMemcpyDeviceToDevice, s));
+    }
+    // a store that has to grow is freed by its reserve, and it may be the
+    // source: the staging copy completes first (the only case with a second wait)
+    if ((size_t)store_capacity(c, n) > c->store.cap)
+        DP_HIP(c, hipStreamSynchronize(s));
+    rc = begin_impl(c, (int)n, s);
+    if (rc != DP_OK)
+        return rc;
+    c->g_expected = -1;
+    c->g_lpt_scratch = nullptr;
+    // host-sized follow-up (dp_densify_run reserves for the state it finds): no stall bound
+    rc = organize_gen(c, c->cand.p, c->ok.p, 0, INT64_MAX, s, 0);
+    dpk::GenDev g{};
+    unsigned long long mb[8];
+    if (rc != DP_OK || (rc = read_state(c, 1, s, &g, mb)) != DP_OK)
+        return rc;
+    c->g_slot = 1;
+    take_state(c, g, gen);
+    gen->seq0 = (uint32_t)n;
+    if (state)
+        *state = g;
+    return DP_OK;
+}
+
+extern "C" int dp_densify_resume_device(dp_ctx *c, const dp_patch *d_patches, int64_t n, const uint8_t *d_keep,
+                                        dp_generation *gen, void *stream)
+{
+    if (!c || n < 0 || (n > 0 && !d_patches) || !gen)
+        return fail(c, DP_E_ARG, "dp_densify_resume_device: bad arguments");
+    if (!c->V)
+        return fail(c, DP_E_STATE, "dp_densify_resume_device: no views");
+    hipSetDevice(c->device);
+    return resume_impl(c, d_patches, d_keep, n, stream ? (hipStream_t)stream : c->stream, gen);
+}
+
+extern "C" int dp_densify_resume(dp_ctx *c, const dp_patch *patches, int64_t n, const uint8_t *keep, dp_generation *gen)
+{
+    if (!c || n < 0 || (n > 0 && !patches) || !gen)
+        return fail(c, DP_E_ARG, "dp_densify_resume: bad arguments");
+    if (!c->V)
+        return fail(c, DP_E_STATE, "dp_densify_resume: no views");
+    if (n > 0x7fffffffll)
+        return fail(c, DP_E_OOM, "dp_densify_resume: too many patches");
+    hipSetDevice(c->device);
+    hipStream_t s = c->stream;
+    const size_t cap = (size_t)std::max<int64_t>(n, 1);
+    DP_HIP(c, c->cand.reserve(cap));
+    DP_HIP(c, c->ok.reserve(cap));
+    if (n > 0) {
+        DP_HIP(c, hipMemcpyAsync(c->cand.p, patches, sizeof(dp_patch) * (size_t)n, hipMemcpyHostToDevice, s));
+        if (keep)
+            DP_HIP(c, hipMemcpyAsync(c->ok.p, keep, (size_t)n, hipMemcpyHostToDevice, s));
+    }
+    return resume_impl(c, c->cand.p, keep ? c->ok.p : nullptr, n, s, gen);
+}
+
+// dp_probe_keep_gather (densepoints_probe.h): the survivor compaction of
+// dp_densify_iterate on host arrays
+extern "C" int dp_probe_keep_gather(dp_ctx *c, const dp_patch *patches, int64_t n, const uint8_t *keep, dp_patch *out,
+                                    int64_t *n_out)
+{
+    if (!c || n < 0 || n > 0x7fffffffll || (n > 0 && (!patches || !keep || !out)) || !n_out)
+        return fail(c, DP_E_ARG, "dp_probe_keep_gather: bad arguments");
+    *n_out = 0;
+    if (n == 0)
+        return DP_OK;
+    hipSetDevice(c->device);
+    hipStream_t s = c->stream;
+    DP_HIP(c, c->f_pat.reserve((size_t)n));
+    DP_HIP(c, c->f_keep.reserve((size_t)n));
+    DP_HIP(c, c->cand.reserve((size_t)n));
+    DP_HIP(c, c->bsum.reserve(dpk::kBfsBlocks));
+    DP_HIP(c, c->itw.reserve(2 * 16));
+    DP_HIP(c, hipMemcpyAsync(c->f_pat.p, patches, sizeof(dp_patch) * (size_t)n, hipMemcpyHostToDevice, s));
+    DP_HIP(c, hipMemcpyAsync(c->f_keep.p, keep, (size_t)n, hipMemcpyHostToDevice, s));
+    DP_HIP(c, dpk::launch_keep_count(c->f_keep.p, n, c->bsum.p, c->itw.p, s));
+    DP_HIP(c, dpk::launch_keep_gather(c->f_pat.p, c->f_keep.p, n, c->bsum.p, c->cand.p, (int64_t)c->cand.cap, s));
+    unsigned long long kept = 0;
+    DP_HIP(c, hipMemcpyAsync(&kept, c->itw.p, sizeof(kept), hipMemcpyDeviceToHost, s));
+    DP_HIP(c, hipStreamSynchronize(s));
+    if (kept)
+        DP_HIP(c, hipMemcpy(out, c->cand.p, sizeof(dp_patch) * (size_t)kept, hipMemcpyDeviceToHost));
+    *n_out = (int64_t)kept;
+    return DP_OK;
+}
+
+extern "C" int dp_densify_store_device(dp_ctx *c, const dp_patch **d_store, int64_t *n)
+{
+    if (!c || !d_store || !n)
+        return fail(c, DP_E_ARG, "dp_densify_store_device: bad arguments");
+    *d_store = c->g_np > 0 ? c->store.p : nullptr;
+    *n = c->g_np;
+    return DP_OK;
+}
+
+extern "C" int dp_densify_iterate(dp_ctx *c, const double *seeds, int n, int iterations, const dp_filter_options *fo,
+                                  const dp_patch **out, int64_t *n_out, dp_densify_stats *stats,
+                                  dp_iterate_stats *per_iter)
+{
+    if (!c || n < 0 || (n > 0 && !seeds) || !out || !n_out || iterations < 1 || iterations > 16)
+        return fail(c, DP_E_ARG, "dp_densify_iterate: bad arguments (1 <= iterations <= 16)");
+    if (!c->V)
+        return fail(c, DP_E_STATE, "dp_densify_iterate: no views");
+    hipSetDevice(c->device);
+    hipStream_t s = c->stream;
+    const auto t0 = std::chrono::steady_clock::now();
+    auto ms_since = [](std::chrono::steady_clock::time_point t) {
+        return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count();
+    };
+    *out = nullptr;
+    *n_out = 0;
+    dp_filter_options o;
+    dp_default_filter_options(&o);
+    if (fo)
+        o = *fo;
+    // per iteration two device words read once at the end: [2k] the objective
+    // evaluations, [2k + 1] the filter's survivors
+    DP_HIP(c, c->itw.reserve(2 * 16));
+    if (c->fev.empty()) {
+        c->fev.assign(2 * 16, nullptr);
+        for (auto &e : c->fev)
+            DP_HIP(c, hipEventCreate(&e));
+    }
+    std::vector<dp_iterate_stats> it((size_t)iterations, dp_iterate_stats{});
+    dp_densify_stats tot{};
+    tot.seeds_in = n;
+    int64_t np = 0;
+    auto tk = t0;
+    for (int k = 0; k < iterations; ++k) {
+        tk = std::chrono::steady_clock::now();
+        int rc;
+        if (k == 0) {
+            rc = densify_core(c, seeds, n);
+            it[0].offered = n;
+        } else {
+            // the previous store and its keep flags, both on the device
+            dp_generation g{};
+            dpk::GenDev first{};
+            rc = resume_impl(c, c->store.p, c->f_keep.p, np, s, &g, &first);
+            if (rc == DP_OK && g.items > 0) {
+                dpk::GenDev last{};
+                rc = expand_all(c, std::max<int64_t>(4 * g.items + 4096, (int64_t)c->cand.cap), s, &last, &first);
+                if (rc == DP_OK)
+                    take_state(c, last, nullptr);
+            }
+        }
+        if (rc != DP_OK)
+            return rc;
+        c->g_expected = -1;
+        np = c->g_np;
+        dp_iterate_stats &st = it[(size_t)k];
+        st.reinserted = c->g_st.seed_patches;
+        st.patches = np;
+        st.candidates = c->g_st.candidates;
+        st.generations = c->g_st.generations;
+        st.refine_ms = c->g_st.refine_ms;
+        tot.pops += std::min<int64_t>(np, std::max<int64_t>(c->opt.max_pops, 0));
+        tot.candidates += st.candidates;
+        tot.generations += st.generations;
+        tot.stalls += c->g_st.stalls;
+        tot.refine_ms += st.refine_ms;
+        if (k == 0)
+            tot.seed_patches = st.reinserted;
+        DP_HIP(c, c->f_keep.reserve((size_t)std::max<int64_t>(np, 1)));
+        DP_HIP(c, c->bsum.reserve(dpk::kBfsBlocks));
+        DP_HIP(c, hipMemcpyAsync(c->itw.p + 2 * k, c->d_evals, sizeof(unsigned long long), hipMemcpyDeviceToDevice, s));
+        DP_HIP(c, hipEventRecord(c->fev[2 * k], s));
+        rc = dp_filter_patches_device(c, c->store.p, np, &o, c->f_keep.p, s);
+        if (rc != DP_OK)
+            return rc;
+        if (np > 0)
+            DP_HIP(c, dpk::launch_keep_count(c->f_keep.p, np, c->bsum.p, c->itw.p + 2 * k + 1, s));
+        else
+            DP_HIP(c, hipMemsetAsync(c->itw.p + 2 * k + 1, 0, sizeof(unsigned long long), s));
+        DP_HIP(c, hipEventRecord(c->fev[2 * k + 1], s));
+        st.total_ms = ms_since(tk); // host time: the filter's device time joins the next wait
+    }
+    // the last store's survivors, unchanged and in store order
+    DP_HIP(c, c->cand.reserve((size_t)std::max<int64_t>(np, 1)));
+    DP_HIP(c, dpk::launch_keep_gather(c->store.p, c->f_keep.p, np, c->bsum.p, c->cand.p, (int64_t)c->cand.cap, s));
+    unsigned long long w[2 * 16];
+    DP_HIP(c, hipMemcpyAsync(w, c->itw.p, sizeof(unsigned long long) * 2 * (size_t)iterations, hipMemcpyDeviceToHost, s));
+    DP_HIP(c, hipStreamSynchronize(s));
+    const int64_t kept = (int64_t)w[2 * (iterations - 1) + 1];
+    DP_HIP(c, c->result.resize((size_t)kept));
+    if (kept)
+        DP_HIP(c, hipMemcpyAsync(c->result.data(), c->cand.p, sizeof(dp_patch) * (size_t)kept, hipMemcpyDeviceToHost, s));
+    DP_HIP(c, hipStreamSynchronize(s));
+    for (int k = 0; k < iterations; ++k) {
+        dp_iterate_stats &st = it[(size_t)k];
+        st.evals = (int64_t)w[2 * k];
+        st.filtered_out = st.patches - (int64_t)w[2 * k + 1];
+        if (k > 0)
+            st.offered = (int64_t)w[2 * (k - 1) + 1];
+        float f = 0.f;
+        DP_HIP(c, hipEventElapsedTime(&f, c->fev[2 * k], c->fev[2 * k + 1]));
+        st.filter_ms = f;
+        tot.evals += st.evals;
+    }
+    it[(size_t)iterations - 1].total_ms = ms_since(tk); // with the result's copy
+    tot.patches = kept;
+    tot.total_ms = ms_since(t0);
+    if (stats)
+        *stats = tot;
+    if (per_iter)
+        std::copy(it.begin(), it.end(), per_iter);
+    *out = c->result.empty() ? nullptr : c->result.data();
+    *n_out = kept;
+    return DP_OK;
 }
 
 // ---------------------------------------------------------------------------

@@ -135,6 +135,10 @@ struct dp_ctx {
     DevBuf<double> f_rho;
     DevBuf<dp_patch> f_pat;
     HostBuf<dp_patch> result; // dp_densify / dp_densify_result output (pinned)
+    // dp_densify_iterate: per iteration {evaluations, filter survivors} on the
+    // device (read once, at the end) and the filters' timing events
+    DevBuf<unsigned long long> itw;
+    std::vector<hipEvent_t> fev;
     // generation-at-a-time densify (dp_densify_begin/refine/commit/result)
     DevBuf<dp_patch> seedp;  // seed patches of generation 0
     DevBuf<double> seedx;    // seed points (3 f64 each) on the device

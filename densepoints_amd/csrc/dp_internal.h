@@ -200,6 +200,14 @@ constexpr int kBfsBlocks = 1024; // chunks of the generation's scan (one block e
 hipError_t launch_bfs_organize(const BfsArgs &a, hipStream_t s);
 // *dst = v on stream s (a state written by the host without a staging copy)
 hipError_t launch_bfs_set_state(GenDev *dst, const GenDev &v, hipStream_t s);
+// survivors of a filtered store (dp_densify_iterate): launch_keep_count leaves
+// the exclusive offsets of the kBfsBlocks chunks of keep[0..n) in bsum and the
+// number of nonzero flags in *total_out; launch_keep_gather then copies the
+// kept records, unchanged and in index order, to dst (at most dst_cap)
+hipError_t launch_keep_count(const uint8_t *keep, int64_t n, uint32_t *bsum, unsigned long long *total_out,
+                             hipStream_t s);
+hipError_t launch_keep_gather(const dp_patch *src, const uint8_t *keep, int64_t n, const uint32_t *bsum, dp_patch *dst,
+                              int64_t dst_cap, hipStream_t s);
 // per-rank accepted records of one refined share, compacted (any order) into
 // a rank slot: slot[0].seq..: count header (int64 in the first 8 B of record
 // 0), records from slot + 1, each with seq = its generation position

@@ -27,6 +27,7 @@ import numpy as np
 import torch
 
 from ._native import PATCH_DTYPE
+from .pmvs import check_iterations
 
 
 def env() -> tuple[int, int, int]:
@@ -131,7 +132,21 @@ def _part_record(eng, counts) -> tuple:
     return (st["items"], int(np.max(counts)) if len(counts) else 0, st["split_items"], st["tiles"])
 
 
-def densify_partitioned(eng, seeds_xyz, dist, device: torch.device | None = None, tile_px: int = 64):
+def _sum_rounds(rounds: list) -> dict:
+    """stats of an iterated densify: the last round's, with the work counters
+    summed over the rounds and the rounds' counts under "iterations" """
+    stats = dict(rounds[-1][0])
+    for key in ("pops", "candidates", "evals", "generations", "stalls", "refine_ms", "total_ms"):
+        if key in stats:
+            stats[key] = sum(r[0].get(key, 0) for r in rounds)
+    if "seed_patches" in rounds[0][0]:
+        stats["seed_patches"] = rounds[0][0]["seed_patches"]
+    stats["iterations"] = [r[1] for r in rounds]
+    return stats
+
+
+def densify_partitioned(eng, seeds_xyz, dist, device: torch.device | None = None, tile_px: int = 64,
+                        iterations: int = 1, filter_passes: int = 0):
     """dp_densify with every generation partitioned by reference-view super-tile
     (dp_densify_owners: items sorted by their (ref, floor(v/tile),
     floor(u/tile)) key, the order cut into `world` contiguous equal shares).  Each rank
@@ -140,11 +155,42 @@ def densify_partitioned(eng, seeds_xyz, dist, device: torch.device | None = None
     by every rank (dp_densify_commit): the replicated store equals dp_densify's
     bit for bit.  Host arrays: `eng` is an Engine or the oracle's
     GenerationEngine (gloo tests on the CPU).  stats gains "partition": per
-    generation (items, largest share, items in split tiles, tiles)."""
+    generation (items, largest share, items in split tiles, tiles).
+    filter_passes != 0 filters the result (Engine.filter_patches); iterations
+    > 1 alternates expansion and filter that many times: every rank holds the
+    replicated store, so every rank filters it and restarts its BFS from the
+    survivors (eng.densify_resume) locally -- no exchange is added.  stats then
+    sums the rounds' work and lists their counts under "iterations"."""
     rank = dist.get_rank() if dist is not None else 0
     world = dist.get_world_size() if dist is not None else 1
-    gen = eng.densify_begin(seeds_xyz)
+    iterations = check_iterations(iterations, filter_passes)
     parts = []
+    rounds = []
+    patches = keep = None
+    for k in range(iterations):
+        offered = len(np.asarray(seeds_xyz).reshape(-1, 3)) if k == 0 else int(np.count_nonzero(keep))
+        gen = eng.densify_begin(seeds_xyz) if k == 0 else eng.densify_resume(patches, keep)
+        gen = _partitioned_generations(eng, gen, dist, device, tile_px, rank, world, parts)
+        patches, stats = eng.densify_result()
+        stats = _reduce_stats(stats, dist, device)
+        rec = {"offered": offered, "reinserted": int(np.count_nonzero(patches["parent"] == 0xFFFFFFFF)),
+               "patches": len(patches),
+               "filtered_out": 0}
+        if filter_passes:
+            keep = eng.filter_patches(patches, filter_passes)
+            rec["filtered_out"] = int(len(keep) - np.count_nonzero(keep))
+        rounds.append((stats, rec))
+    if filter_passes:
+        patches = patches[keep != 0]
+        stats = _sum_rounds(rounds)
+        stats["filtered_out"] = sum(r[1]["filtered_out"] for r in rounds)
+        stats["patches"] = len(patches)
+    stats["partition"] = parts
+    return patches, stats
+
+
+def _partitioned_generations(eng, gen, dist, device, tile_px, rank, world, parts):
+    """every generation from `gen` on, partitioned (host arrays)"""
     while gen.items > 0:
         owners, _ = eng.densify_owners(gen, world, tile_px)
         order, counts, offsets = partition(owners, world)
@@ -160,10 +206,7 @@ def densify_partitioned(eng, seeds_xyz, dist, device: torch.device | None = None
         item_cand[pos] = all_cand
         item_acc[pos] = all_acc
         gen = eng.densify_commit(gen, item_cand, item_acc)
-    patches, stats = eng.densify_result()
-    stats = _reduce_stats(stats, dist, device)
-    stats["partition"] = parts
-    return patches, stats
+    return gen
 
 
 class _DeviceBuffers:
@@ -192,7 +235,7 @@ def replicate_below_default(world: int) -> int:
 
 def densify_partitioned_device(eng, seeds_xyz, dist, device: torch.device, tile_px: int = 64,
                                probe_worlds: tuple = (), one_rank_exchange: bool = False, copy_result: bool = True,
-                               replicate_below: int | None = None):
+                               replicate_below: int | None = None, iterations: int = 1, filter_passes: int = 0):
     """dp_densify with every generation partitioned by reference-view super-tile,
     the records in HBM, only the ACCEPTED candidates exchanged and ONE host
     wait per generation.  Per generation, all queued on the torch current
@@ -229,12 +272,26 @@ def densify_partitioned_device(eng, seeds_xyz, dist, device: torch.device, tile_
     queued partition, refine and exchange calls; commit = up to the status
     read, i.e. mostly the generation's GPU time; run = the device-resident
     generations) and, with probe_worlds, "partition_probe" {world: the same
-    records} of the partitions those world sizes would use (statistics only)."""
+    records} of the partitions those world sizes would use (statistics only).
+    filter_passes != 0 filters the result; iterations > 1 alternates expansion
+    and filter that many times.  Every rank holds the replicated store, so
+    between rounds every rank filters it on the device
+    (dp_filter_patches_device on the store itself) and restarts its BFS from
+    the survivors (dp_densify_resume_device on the same pointer): no exchange
+    is added, and the transition itself moves no patch to the host (every
+    round's store is still read back once, by densify_result, for its
+    statistics).  stats then sums the rounds' work and lists their counts under
+    "iterations"."""
     rank = dist.get_rank() if dist is not None else 0
     world = dist.get_world_size() if dist is not None else 1
+    iterations = check_iterations(iterations, filter_passes)
     if world == 1 and not one_rank_exchange and not probe_worlds:
         t = time.perf_counter()
-        patches, stats = eng.densify(seeds_xyz, copy=copy_result)
+        if filter_passes:
+            patches, stats = eng.densify_iterate(seeds_xyz, iterations, filter_passes, copy=copy_result)
+            stats["filtered_out"] = sum(r["filtered_out"] for r in stats["iterations"])
+        else:
+            patches, stats = eng.densify(seeds_xyz, copy=copy_result)
         stats["phase_ms"] = {"densify": round((time.perf_counter() - t) * 1e3, 2)}
         stats["partition"] = []
         stats["gathered_bytes"] = [0]
@@ -249,62 +306,84 @@ def densify_partitioned_device(eng, seeds_xyz, dist, device: torch.device, tile_
     sp = stream.cuda_stream
     pool = _DeviceBuffers(device)
     ph = {"begin": 0.0, "launch": 0.0, "commit": 0.0, "run": 0.0, "replicated": 0.0}
-    t = time.perf_counter()
-    gen = eng.densify_begin(seeds_xyz)
-    ph["begin"] += time.perf_counter() - t
     parts, gathered, accepted = [], [], []
     replicated_calls = 0
     probe = {int(w): [] for w in probe_worlds}
-    while gen.items > 0:
-        per = gen.per_item
-        for w in probe:
-            own, _ = eng.densify_owners(gen, w, tile_px)
-            probe[w].append(_part_record(eng, np.bincount(own, minlength=w)))
-        if world == 1 and gen.index >= 1 and not one_rank_exchange:
-            t = time.perf_counter()
-            torch.cuda.current_stream(device).synchronize()
-            gen = eng.densify_run(gen)
-            ph["run"] += time.perf_counter() - t
-            continue
-        if gen.index >= 1 and gen.items < replicate_below and not probe:
-            # the small generations, on every rank, until one reaches the bound
-            t = time.perf_counter()
-            torch.cuda.current_stream(device).synchronize()
-            gen, ev = eng.densify_run_until(gen, replicate_below)
-            repl_evals += ev
-            replicated_calls += 1
-            ph["replicated"] += time.perf_counter() - t
-            continue
+    rounds = []
+    for k in range(iterations):
         t = time.perf_counter()
-        d_order, counts = eng.densify_partition_async(gen, world, tile_px, sp)
-        offs = np.concatenate([[0], np.cumsum(counts)[:-1]]).astype(np.int64)
-        mine = int(counts[rank])
-        stride = max(int(counts.max()) * per, 1)  # fixed-capacity rank slot (records)
-        slot = pool.get("slot", (stride + 1) * rec)[: (stride + 1) * rec]
-        d_items = d_order + 8 * int(offs[rank]) if mine else 0
-        eng.densify_refine_share_async(gen, d_items, mine, slot.data_ptr(), stride, sp)
-        if dist is None:
-            recv = slot
-        elif rccl:
-            recv = pool.get("recv", world * (stride + 1) * rec)[: world * (stride + 1) * rec]
-            dist.all_gather_into_tensor(recv, slot)
+        if k == 0:
+            offered = len(np.asarray(seeds_xyz).reshape(-1, 3))
+            gen = eng.densify_begin(seeds_xyz)
         else:
-            # gloo (one-device rehearsals): staged through the host
-            hr = torch.empty(world * (stride + 1) * rec, dtype=torch.uint8)
-            dist.all_gather_into_tensor(hr, slot.cpu())
-            recv = hr.to(device)
-        t1 = time.perf_counter()
-        ph["launch"] += t1 - t
-        n_ex = eng.densify_commit_gathered_device(gen, recv.data_ptr(), stride, world, sp)
-        ph["commit"] += time.perf_counter() - t1
-        parts.append(_part_record(eng, counts))
-        gathered.append(world * (stride + 1) * rec if dist is not None else 0)
-        accepted.append(n_ex)
-    patches, stats = eng.densify_result(copy=copy_result)
-    if rank != 0:
-        # every rank ran the replicated generations: rank 0 counts them
-        stats["evals"] -= repl_evals
-    stats = _reduce_stats(stats, dist, device)
+            # the replicated store and its keep flags stay on the device
+            d_store, n_store = eng.densify_store_device()
+            keep_t = pool.get("keep", n_store)
+            eng.filter_patches_device(d_store, n_store, keep_t.data_ptr(), filter_passes, stream=sp)
+            gen = eng.densify_resume_device(d_store, n_store, keep_t.data_ptr(), sp)
+            offered = int(torch.count_nonzero(keep_t[:n_store]).item())
+            rounds[-1][1]["filtered_out"] = n_store - offered
+        ph["begin"] += time.perf_counter() - t
+        repl_evals = 0
+        while gen.items > 0:
+            per = gen.per_item
+            for w in probe:
+                own, _ = eng.densify_owners(gen, w, tile_px)
+                probe[w].append(_part_record(eng, np.bincount(own, minlength=w)))
+            if world == 1 and gen.index >= 1 and not one_rank_exchange:
+                t = time.perf_counter()
+                torch.cuda.current_stream(device).synchronize()
+                gen = eng.densify_run(gen)
+                ph["run"] += time.perf_counter() - t
+                continue
+            if gen.index >= 1 and gen.items < replicate_below and not probe:
+                # the small generations, on every rank, until one reaches the bound
+                t = time.perf_counter()
+                torch.cuda.current_stream(device).synchronize()
+                gen, ev = eng.densify_run_until(gen, replicate_below)
+                repl_evals += ev
+                replicated_calls += 1
+                ph["replicated"] += time.perf_counter() - t
+                continue
+            t = time.perf_counter()
+            d_order, counts = eng.densify_partition_async(gen, world, tile_px, sp)
+            offs = np.concatenate([[0], np.cumsum(counts)[:-1]]).astype(np.int64)
+            mine = int(counts[rank])
+            stride = max(int(counts.max()) * per, 1)  # fixed-capacity rank slot (records)
+            slot = pool.get("slot", (stride + 1) * rec)[: (stride + 1) * rec]
+            d_items = d_order + 8 * int(offs[rank]) if mine else 0
+            eng.densify_refine_share_async(gen, d_items, mine, slot.data_ptr(), stride, sp)
+            if dist is None:
+                recv = slot
+            elif rccl:
+                recv = pool.get("recv", world * (stride + 1) * rec)[: world * (stride + 1) * rec]
+                dist.all_gather_into_tensor(recv, slot)
+            else:
+                # gloo (one-device rehearsals): staged through the host
+                hr = torch.empty(world * (stride + 1) * rec, dtype=torch.uint8)
+                dist.all_gather_into_tensor(hr, slot.cpu())
+                recv = hr.to(device)
+            t1 = time.perf_counter()
+            ph["launch"] += t1 - t
+            n_ex = eng.densify_commit_gathered_device(gen, recv.data_ptr(), stride, world, sp)
+            ph["commit"] += time.perf_counter() - t1
+            parts.append(_part_record(eng, counts))
+            gathered.append(world * (stride + 1) * rec if dist is not None else 0)
+            accepted.append(n_ex)
+        patches, stats = eng.densify_result(copy=copy_result)
+        if rank != 0:
+            # every rank ran the replicated generations: rank 0 counts them
+            stats["evals"] -= repl_evals
+        stats = _reduce_stats(stats, dist, device)
+        rounds.append((stats, {"offered": offered, "reinserted": int(stats["seed_patches"]), "patches": len(patches),
+                               "filtered_out": 0}))
+    if filter_passes:
+        keep = eng.filter_patches(patches, filter_passes)
+        rounds[-1][1]["filtered_out"] = int(len(keep) - np.count_nonzero(keep))
+        patches = patches[keep != 0]
+        stats = _sum_rounds(rounds)
+        stats["filtered_out"] = sum(r[1]["filtered_out"] for r in rounds)
+        stats["patches"] = len(patches)
     stats["replicated_calls"] = replicated_calls
     stats["replicate_below"] = int(replicate_below)
     stats["phase_ms"] = {k: round(v * 1e3, 2) for k, v in ph.items()}

@@ -394,7 +394,6 @@ class Engine:
         stats = {name: getattr(st, name) for name, _ in N.DpDensifyStats._fields_}
         return result_array(out.value, n.value, copy), stats
 
-
     # ---- one generation at a time (multi-GPU partitioning; dist.py) ----
     def densify_begin(self, seeds_xyz: np.ndarray) -> N.DpGeneration:
         seeds = np.ascontiguousarray(seeds_xyz, dtype=np.float64).reshape(-1, 3)
@@ -492,6 +491,76 @@ class Engine:
         return result_array(out.value, n.value, copy), stats
 
 
+    # ---- resume / iterated expand-filter (include/densepoints.h dp_densify_resume) ----
+    def densify_resume(self, patches: np.ndarray, keep: np.ndarray | None = None) -> N.DpGeneration:
+        """dp_densify_resume: the organizer and the store rebuilt from
+        patches[keep != 0] (TryInsert in index order, no refine); returns the
+        first expansion generation, for densify_run and the generation API."""
+        patches = np.ascontiguousarray(patches)
+        assert patches.dtype == PATCH_DTYPE
+        if keep is not None:
+            keep = np.ascontiguousarray(keep, dtype=np.uint8)
+            if len(keep) != len(patches):
+                raise ValueError("densify_resume: one keep flag per patch")
+        g = N.DpGeneration()
+        self._check(lib.dp_densify_resume(self._ctx, ptr(patches), len(patches), ptr(keep), ctypes.byref(g)))
+        return g
+
+    def densify_resume_device(self, d_patches: int, n: int, d_keep: int | None,
+                              stream: int | None = None) -> N.DpGeneration:
+        """dp_densify_resume_device: the same from device memory (d_patches may
+        be the context's own store, densify_store_device()); one host wait."""
+        g = N.DpGeneration()
+        self._check(lib.dp_densify_resume_device(self._ctx, ctypes.c_void_p(d_patches) if d_patches else None, int(n),
+                                                 ctypes.c_void_p(d_keep) if d_keep else None, ctypes.byref(g),
+                                                 ctypes.c_void_p(stream) if stream else None))
+        return g
+
+    def densify_store_device(self) -> tuple[int, int]:
+        """(device address, records) of the context's patch store."""
+        d = ctypes.c_void_p()
+        n = ctypes.c_int64()
+        self._check(lib.dp_densify_store_device(self._ctx, ctypes.byref(d), ctypes.byref(n)))
+        return int(d.value or 0), int(n.value)
+
+    def filter_patches_device(self, d_patches: int, n: int, d_keep: int, passes: int = 3,
+                              min_neighbor_frac: float = 0.25, stream: int | None = None) -> None:
+        """dp_filter_patches_device: keep flags of n device-resident patches, queued on `stream`."""
+        fo = N.DpFilterOptions(passes, 0, min_neighbor_frac)
+        self._check(lib.dp_filter_patches_device(self._ctx, ctypes.c_void_p(d_patches) if d_patches else None, int(n),
+                                                 ctypes.byref(fo), ctypes.c_void_p(d_keep) if d_keep else None,
+                                                 ctypes.c_void_p(stream) if stream else None))
+
+    def densify_iterate(self, seeds_xyz: np.ndarray, iterations: int, passes: int = 3,
+                        min_neighbor_frac: float = 0.25, copy: bool = True):
+        """dp_densify_iterate: `iterations` rounds of expansion then filter, the
+        store resident on the device between them; (surviving patches, stats)
+        with the per-round records in stats["iterations"]."""
+        seeds = np.ascontiguousarray(seeds_xyz, dtype=np.float64).reshape(-1, 3)
+        fo = N.DpFilterOptions(passes, 0, min_neighbor_frac)
+        out = ctypes.c_void_p()
+        n = ctypes.c_int64()
+        st = N.DpDensifyStats()
+        per = (N.DpIterateStats * max(int(iterations), 1))()
+        self._check(lib.dp_densify_iterate(self._ctx, ptr(seeds), len(seeds), int(iterations), ctypes.byref(fo),
+                                           ctypes.byref(out), ctypes.byref(n), ctypes.byref(st), per))
+        stats = {name: getattr(st, name) for name, _ in N.DpDensifyStats._fields_}
+        stats["iterations"] = [{name: getattr(per[k], name) for name, _ in N.DpIterateStats._fields_
+                                if name != "reserved"} for k in range(int(iterations))]
+        return result_array(out.value, n.value, copy), stats
+
+
+def check_iterations(iterations: int, filter_passes: int) -> int:
+    """the rounds of an iterated densify (PMVS.run, dist.densify_partitioned*):
+    1..16, and more than one only with a filter, which is what tells them apart"""
+    iterations = int(iterations)
+    if not 1 <= iterations <= 16:
+        raise ValueError("iterations must be in 1..16")
+    if iterations > 1 and not filter_passes:
+        raise ValueError("iterations > 1 needs filter_passes != 0 (the filter separates the rounds)")
+    return iterations
+
+
 class PMVS:
     """PMVS::PMVS (methods/pmvs/pmvs.h:14-35): AddCamera, Run, GetPointCloud.
 
@@ -515,12 +584,17 @@ class PMVS:
             return
         self.views.append(view)
 
-    def run(self, seeds_xyz=None, filter_passes: int = 0, matcher_options=None) -> bool:
+    def run(self, seeds_xyz=None, filter_passes: int = 0, matcher_options=None, iterations: int = 1) -> bool:
         """PMVS::Run (pmvs.cpp:22-43).  With seeds_xyz None the seeds come from
         Matcher::GenerateSeeds on the device (PMVS::InsertSeeds, pmvs.cpp:29-34);
         filter_passes != 0 then applies FilterPatches (pmvs.h:27; spec in
-        dp_filter_patches)."""
+        dp_filter_patches).  iterations > 1 alternates expansion and filter that
+        many times (dp_densify_iterate: each round re-expands from the previous
+        round's survivors); the filter is what tells the rounds apart, so it
+        needs filter_passes != 0."""
         from .matcher import Matcher
+
+        iterations = check_iterations(iterations, filter_passes)
 
         with Engine(self.options, self.device) as eng:
             eng.set_views(self.views)
@@ -531,6 +605,13 @@ class PMVS:
                 m = Matcher(eng, matcher_options)
                 seeds_xyz = m.generate_seeds()
                 seed_stats = m.stats
+            if iterations > 1:
+                self.patches, self.stats = eng.densify_iterate(np.asarray(seeds_xyz, dtype=np.float64), iterations,
+                                                               filter_passes)
+                self.stats["filtered_out"] = int(sum(r["filtered_out"] for r in self.stats["iterations"]))
+                if seed_stats is not None:
+                    self.stats["seed_generation"] = seed_stats
+                return True
             self.patches, self.stats = eng.densify(np.asarray(seeds_xyz, dtype=np.float64))
             if seed_stats is not None:
                 self.stats["seed_generation"] = seed_stats

@@ -334,6 +334,70 @@ int dp_filter_patches(dp_ctx *ctx, const dp_patch *patches, int64_t n, const dp_
 int dp_filter_patches_device(dp_ctx *ctx, const dp_patch *d_patches, int64_t n, const dp_filter_options *fo,
                              uint8_t *d_keep, void *stream);
 
+/* ---- iterated expand-filter (PMVS alternates expansion and filtering, three
+ * times by default: Furukawa & Ponce, PAMI 2010, 3.3-3.4) ---------------------
+ * dp_densify_resume restarts the BFS from an existing patch set
+ * (PatchOrganizer::SetSeeds, patch_organizer.cpp:70-75, applied to patches
+ * instead of refined seeds):
+ *  - offered: patches[i] with keep[i] != 0 (keep NULL = all), in ascending i;
+ *  - reset: the organizer grids, the store (emptied), the statistics and
+ *    evaluation counters and the pop count;
+ *  - insertion: each offered patch goes through TryInsert in that order,
+ *    exactly as an accepted candidate of a generation with per_item = 1.  It is
+ *    NOT refined again.  A patch that claims at most one cell is dropped and
+ *    its claims stay.  A stored record is the input record with seq = its new
+ *    store index, parent = 0xFFFFFFFF, flags |= DP_PATCH_ACCEPTED and rgb
+ *    recomputed (Patch::ComputeColor); score and evals are kept.  The claims of
+ *    patches that are not offered are not carried over: their cells are free;
+ *  - *gen = the first expansion generation: index 1, head 0, items = the
+ *    stored count (0 if nothing was stored or max_pops <= 0), per_item 4, cell
+ *    = expand_cell_size, seq0 = n; stats.seeds_in = n, stats.seed_patches = the
+ *    stored count;
+ *  - afterwards every generation call works on this state as after a seed
+ *    generation (dp_densify_run[_until], dp_densify_owners / _refine_items /
+ *    _commit, the _async device protocol, dp_densify_result); performance mode
+ *    (dp_fast_options.densify = 1) expands with the fast refine.
+ * The device form copies nothing to the host and waits once (the status read;
+ * a patch store that has to grow costs one more).  stream NULL = the context's
+ * stream.  d_patches may be any device memory INCLUDING the context's own
+ * store (the pointer dp_filter_patches_device was given): the patches are
+ * staged before the store is reset.  The order and the stored indices do not
+ * depend on the launch geometry (the sequence number is the input index). */
+int dp_densify_resume(dp_ctx *ctx, const dp_patch *patches, int64_t n, const uint8_t *keep /* NULL = all */,
+                      dp_generation *gen);
+int dp_densify_resume_device(dp_ctx *ctx, const dp_patch *d_patches, int64_t n, const uint8_t *d_keep,
+                             dp_generation *gen, void *stream);
+
+/* The context's patch store on the device: *n records at *d_store (NULL when
+ * empty), as the last dp_densify / generation call / dp_densify_resume left
+ * it; valid until the next call that changes the store.  For
+ * dp_filter_patches_device and dp_densify_resume_device without a host copy. */
+int dp_densify_store_device(dp_ctx *ctx, const dp_patch **d_store, int64_t *n);
+
+/* `iterations` (1..16, else DP_E_ARG) rounds of expansion then filter: round 1
+ * is dp_densify then dp_filter_patches on its store; round k > 1 is
+ * dp_densify_resume_device on the previous store with the previous keep flags,
+ * every generation, then the filter (fo NULL = the defaults).  The result is
+ * the last store's survivors in store order, records unchanged (patches[keep ==
+ * 1]); with iterations == 1 that is dp_densify followed by dp_filter_patches.
+ * The store never visits the host between rounds: a round costs the BFS's own
+ * waits plus the resume's status read.  *stats sums pops, candidates, evals,
+ * generations, stalls and refine_ms over the rounds; stats->patches = *n_out,
+ * stats->seed_patches = round 1's.  per_iter[k] (may be NULL): offered = the
+ * seed points (k = 0) or the previous round's survivors, reinserted = the
+ * patches the organizer stored of them, patches = the store after the BFS,
+ * filtered_out = those the filter then removed; total_ms is host time (the
+ * filter's device time shows in the next round's, the last includes the copy
+ * of the result). */
+typedef struct dp_iterate_stats {
+    int64_t offered, reinserted, patches, filtered_out, candidates, evals;
+    int32_t generations, reserved;
+    double refine_ms, filter_ms, total_ms;
+} dp_iterate_stats;
+int dp_densify_iterate(dp_ctx *ctx, const double *seeds_xyz, int n, int iterations, const dp_filter_options *fo,
+                       const dp_patch **out, int64_t *n_out, dp_densify_stats *stats,
+                       dp_iterate_stats *per_iter /* iterations entries, may be NULL */);
+
 /* ---- seed generation: Features::Matcher::GenerateSeeds ---
  * modules/features/matcher.cpp:18-43 with the default MatcherOptions
  * (matcher.h:21-32: ORB detector, kNN matcher, no direct epipolar matching,

@@ -52,6 +52,11 @@ int dp_probe_orb_level(dp_ctx *c, int view, int level, int n_levels, double scal
  * refine kernel since the last call (0 maps, 1 texture 0, 2 other views,
  * 3 NCC finish, 6 patches, 7 whole patch); DP_E_STATE otherwise */
 int dp_debug_stamps(uint64_t *out8);
+/* The survivor compaction of dp_densify_iterate on host arrays: out receives
+ * patches[i] with keep[i] != 0, unchanged and in index order (room for n
+ * records); *n_out = their count. */
+int dp_probe_keep_gather(dp_ctx *ctx, const dp_patch *patches, int64_t n, const uint8_t *keep, dp_patch *out,
+                         int64_t *n_out);
 
 #ifdef __cplusplus
 }

@@ -8,7 +8,7 @@
 // (include/densepoints.h): dp_set_views, dp_generate_seeds, dp_densify.
 //
 //   densify -i scene.json [--seeds seeds.xyz] [-s settings.json] [-o points.ply]
-//           [--device N] [--max-pops N] [--level L] [--filter] [--check-only]
+//           [--device N] [--max-pops N] [--level L] [--filter] [--iterations N] [--check-only]
 //           [--features N] [--fast-threshold T] [--epipolar-matching] [--matcher knn|flann]
 //           [--detector orb|akaze] [--akaze-threshold T]
 //   densify --synthetic V,W,H,KIND --write-scene DIR   (deterministic test scene
@@ -39,6 +39,9 @@ void usage()
     std::fprintf(stderr,
                  "usage: densify -i scene.json [--seeds seeds.xyz] [-s settings.json] [-o points.ply]\n"
                  "               [--device N] [--max-pops N] [--level L] [--filter] [--check-only]\n"
+                 "               [--iterations N]  (1..16 rounds of expansion then filter, each round\n"
+                 "                             re-expanding from the previous round's survivors with the\n"
+                 "                             store resident on the device; N > 1 implies --filter)\n"
                  "               [--features N] [--fast-threshold T] [--epipolar-matching]\n"
                  "               [--matcher knn|flann]  (MatcherType, matcher.h:12)\n"
                  "               [--detector orb|akaze] [--akaze-threshold T]  (DetectorType, matcher.h:11)\n"
@@ -296,30 +299,37 @@ struct Exchange {
 // replicate_below items run on every context device-resident instead
 // (dp_densify_run_until: no partition, no exchange, eight per host wait).
 // Returns the stats of context 0 (evals / refine_ms summed / maxed).
-int densify_multi(std::vector<dp_ctx *> &ctxs, const std::vector<int> &devices, const char *exchange_mode,
-                  const std::vector<double> &seeds, std::vector<dp_patch> &out, dp_densify_stats &st,
-                  std::string &err, int64_t &exchanged, int64_t replicate_below)
-{
-    const int G = (int)ctxs.size();
-    const int n = (int)(seeds.size() / 3);
-    Exchange ex;
-    if (!ex.init(devices, exchange_mode)) {
-        err = ex.err;
-        return DP_E_HIP;
-    }
-    std::vector<dp_generation> gen((size_t)G);
-    std::vector<int> rcs((size_t)G, DP_OK);
-    auto fail_of = [&](int g, int rc) {
+// iterations > 1 (--iterations): after each round but the last, every context
+// filters its replicated store on the device (dp_filter_patches_device) and
+// restarts the BFS from the survivors (dp_densify_resume_device on its own
+// store): no exchange is added.  The caller filters the last round's store.
+// The stats then sum over the rounds; iters[k] holds round k's counts (the
+// last round's filtered_out is the caller's).  Every round's store is read
+// back once for its statistics (dp_densify_result).
+struct MultiRun {
+    std::vector<dp_ctx *> &ctxs;
+    const std::vector<int> &devices;
+    Exchange &ex;
+    int64_t replicate_below;
+    std::string &err;
+    std::vector<dp_generation> gen;
+    std::vector<int64_t> repl_evals;
+    int64_t exchanged = 0;
+
+    int fail_of(int g, int rc)
+    {
         err = dp_last_error(ctxs[(size_t)g]);
         return rc;
-    };
-    for (int g = 0; g < G; ++g) {
-        const int rc = dp_densify_begin(ctxs[(size_t)g], seeds.data(), n, &gen[(size_t)g]);
-        if (rc != DP_OK)
-            return fail_of(g, rc);
     }
-    exchanged = 0;
-    std::vector<int64_t> counts((size_t)G), ex_g((size_t)G, 0), repl_evals((size_t)G, 0);
+    // every generation of the round that gen[] starts
+    int generations();
+};
+
+int MultiRun::generations()
+{
+    const int G = (int)ctxs.size();
+    std::vector<int> rcs((size_t)G, DP_OK);
+    std::vector<int64_t> counts((size_t)G), ex_g((size_t)G, 0);
     while (gen[0].items > 0) {
         const int per = gen[0].per_item;
         if (gen[0].index >= 1 && gen[0].items < replicate_below) {
@@ -380,20 +390,128 @@ int densify_multi(std::vector<dp_ctx *> &ctxs, const std::vector<int> &devices, 
                 return fail_of(g, rcs[(size_t)g]);
         exchanged += ex_g[0];
     }
-    std::vector<dp_densify_stats> sts((size_t)G);
-    const dp_patch *res = nullptr;
-    int64_t np = 0;
-    for (int g = G - 1; g >= 0; --g) {
-        const int rc = dp_densify_result(ctxs[(size_t)g], &res, &np, &sts[(size_t)g]);
-        if (rc != DP_OK)
-            return fail_of(g, rc);
+    return DP_OK;
+}
+
+int densify_multi(std::vector<dp_ctx *> &ctxs, const std::vector<int> &devices, const char *exchange_mode,
+                  const std::vector<double> &seeds, std::vector<dp_patch> &out, dp_densify_stats &st,
+                  std::string &err, int64_t &exchanged, int64_t replicate_below, int iterations,
+                  const dp_filter_options &fopt, std::vector<dp_iterate_stats> &iters)
+{
+    const int G = (int)ctxs.size();
+    const int n = (int)(seeds.size() / 3);
+    Exchange ex;
+    if (!ex.init(devices, exchange_mode)) {
+        err = ex.err;
+        return DP_E_HIP;
     }
-    out.assign(res, res + np);
-    st = sts[0];
-    for (int g = 1; g < G; ++g) {
-        st.evals += sts[(size_t)g].evals - repl_evals[(size_t)g];
-        st.refine_ms = std::max(st.refine_ms, sts[(size_t)g].refine_ms);
+    MultiRun run{ctxs, devices, ex, replicate_below, err, std::vector<dp_generation>((size_t)G),
+                 std::vector<int64_t>((size_t)G, 0)};
+    // per-context keep flags of the rounds' filters (device), grown as needed
+    struct KeepBufs {
+        std::vector<uint8_t *> p;
+        std::vector<size_t> cap;
+        std::vector<int> dev;
+        ~KeepBufs()
+        {
+            for (size_t g = 0; g < p.size(); ++g)
+                if (p[g]) {
+                    (void)hipSetDevice(dev[g]);
+                    (void)hipFree(p[g]);
+                }
+        }
+    } keepb{std::vector<uint8_t *>((size_t)G, nullptr), std::vector<size_t>((size_t)G, 0), devices};
+    iters.assign((size_t)iterations, dp_iterate_stats{});
+    dp_densify_stats sum;
+    std::memset(&sum, 0, sizeof sum);
+    sum.seeds_in = n;
+    for (int round = 0; round < iterations; ++round) {
+        dp_iterate_stats &is = iters[(size_t)round];
+        std::fill(run.repl_evals.begin(), run.repl_evals.end(), 0);
+        if (round == 0) {
+            for (int g = 0; g < G; ++g) {
+                const int rc = dp_densify_begin(ctxs[(size_t)g], seeds.data(), n, &run.gen[(size_t)g]);
+                if (rc != DP_OK)
+                    return run.fail_of(g, rc);
+            }
+            is.offered = n;
+        }
+        for (int g = 0; round > 0 && g < G; ++g) {
+            // every context filters its replicated store and resumes from the survivors
+            const dp_patch *d_store = nullptr;
+            int64_t ns = 0;
+            int rc = dp_densify_store_device(ctxs[(size_t)g], &d_store, &ns);
+            if (rc != DP_OK)
+                return run.fail_of(g, rc);
+            if (!ex.hip(hipSetDevice(devices[(size_t)g]), "hipSetDevice"))
+                return err = ex.err, DP_E_HIP;
+            const size_t need = (size_t)std::max<int64_t>(ns, 1);
+            if (keepb.cap[(size_t)g] < need) {
+                if (keepb.p[(size_t)g])
+                    (void)hipFree(keepb.p[(size_t)g]);
+                keepb.p[(size_t)g] = nullptr;
+                keepb.cap[(size_t)g] = 0;
+                if (!ex.hip(hipMalloc(&keepb.p[(size_t)g], need + need / 4), "hipMalloc"))
+                    return err = ex.err, DP_E_HIP;
+                keepb.cap[(size_t)g] = need + need / 4;
+            }
+            uint8_t *d_keep = keepb.p[(size_t)g];
+            rc = dp_filter_patches_device(ctxs[(size_t)g], d_store, ns, &fopt, d_keep, ex.stream[(size_t)g]);
+            if (rc == DP_OK)
+                rc = dp_densify_resume_device(ctxs[(size_t)g], d_store, ns, d_keep, &run.gen[(size_t)g],
+                                              ex.stream[(size_t)g]);
+            if (rc != DP_OK)
+                return run.fail_of(g, rc);
+            if (g == 0) {
+                // the flags (not the store) for the round's counts
+                std::vector<uint8_t> hk((size_t)ns);
+                if (ns > 0 && !ex.hip(hipMemcpy(hk.data(), d_keep, (size_t)ns, hipMemcpyDeviceToHost), "hipMemcpy"))
+                    return err = ex.err, DP_E_HIP;
+                int64_t kept = 0;
+                for (uint8_t f : hk)
+                    kept += f != 0;
+                is.offered = kept;
+                iters[(size_t)round - 1].filtered_out = ns - kept;
+            }
+        }
+        const int grc = run.generations();
+        if (grc != DP_OK)
+            return grc;
+        std::vector<dp_densify_stats> sts((size_t)G);
+        const dp_patch *res = nullptr;
+        int64_t np = 0;
+        for (int g = G - 1; g >= 0; --g) {
+            const int rc = dp_densify_result(ctxs[(size_t)g], &res, &np, &sts[(size_t)g]);
+            if (rc != DP_OK)
+                return run.fail_of(g, rc);
+        }
+        if (round == iterations - 1)
+            out.assign(res, res + np);
+        dp_densify_stats r = sts[0];
+        for (int g = 1; g < G; ++g) {
+            r.evals += sts[(size_t)g].evals - run.repl_evals[(size_t)g];
+            r.refine_ms = std::max(r.refine_ms, sts[(size_t)g].refine_ms);
+        }
+        is.reinserted = r.seed_patches;
+        is.patches = r.patches;
+        is.candidates = r.candidates;
+        is.evals = r.evals;
+        is.generations = r.generations;
+        is.refine_ms = r.refine_ms;
+        is.total_ms = r.total_ms;
+        sum.pops += r.pops;
+        sum.candidates += r.candidates;
+        sum.evals += r.evals;
+        sum.generations += r.generations;
+        sum.stalls += r.stalls;
+        sum.refine_ms += r.refine_ms;
+        sum.total_ms += r.total_ms;
+        if (round == 0)
+            sum.seed_patches = r.seed_patches;
+        sum.patches = r.patches;
     }
+    exchanged = run.exchanged;
+    st = sum;
     return DP_OK;
 }
 
@@ -409,6 +527,7 @@ int main(int argc, char **argv)
     long long max_pops = -1;
     int level = 0;
     bool check_only = false, do_filter = false, fast = false;
+    int iterations = 1;
     int fast_iters = -1, fast_gradient = -1;
     dp_matcher_options mopt; // MatcherOptions defaults (matcher.h:21-32), ORB::create(40000)
     dp_default_matcher_options(&mopt);
@@ -439,6 +558,13 @@ int main(int argc, char **argv)
         else if (a == "--max-pops") max_pops = std::atoll(next().c_str());
         else if (a == "--level") level = std::atoi(next().c_str());
         else if (a == "--filter") do_filter = true;
+        else if (a == "--iterations") {
+            iterations = std::atoi(next().c_str());
+            if (iterations < 1 || iterations > 16) {
+                std::fprintf(stderr, "densify: --iterations expects 1..16\n");
+                return 2;
+            }
+        }
         else if (a == "--check-only") check_only = true;
         else if (a == "--features") mopt.n_features = std::atoi(next().c_str());
         else if (a == "--fast-threshold") mopt.fast_threshold = std::atoi(next().c_str());
@@ -484,6 +610,8 @@ int main(int argc, char **argv)
             return 2;
         }
     }
+    if (iterations > 1)
+        do_filter = true; // the filter is what tells the rounds apart
     try {
         if (!synth.empty()) {
             if (scene_dir.empty())
@@ -572,6 +700,10 @@ int main(int argc, char **argv)
         std::memset(&st, 0, sizeof st);
         std::vector<dp_patch> multi_out;
         int64_t exchanged = -1;
+        std::vector<dp_iterate_stats> iters;
+        dp_filter_options filt;
+        dp_default_filter_options(&filt);
+        bool filtered = false; // `out` holds survivors only
         if (gpus > 1 || force_multi) {
             // contexts 1..N-1 on the next devices (wrapping: several ranks may share a GPU)
             const int ndev = dp_device_count();
@@ -606,7 +738,8 @@ int main(int argc, char **argv)
             std::string err;
             const int64_t rb = replicate_below >= 0 ? (int64_t)replicate_below : 1024 * (int64_t)gpus;
             const int mrc =
-                densify_multi(ctxs, devices, exchange_mode.c_str(), use, multi_out, st, err, exchanged, rb);
+                densify_multi(ctxs, devices, exchange_mode.c_str(), use, multi_out, st, err, exchanged, rb, iterations, filt,
+                              iters);
             for (int g = 1; g < gpus; ++g)
                 dp_ctx_destroy(ctxs[(size_t)g]);
             if (mrc != DP_OK) {
@@ -616,16 +749,20 @@ int main(int argc, char **argv)
             }
             out = multi_out.data();
             n_out = (int64_t)multi_out.size();
+        } else if (iterations > 1) {
+            // expansion and filter alternated on the device (dp_densify_iterate)
+            iters.assign((size_t)iterations, dp_iterate_stats{});
+            check(dp_densify_iterate(ctx, use.data(), (int)(use.size() / 3), iterations, &filt, &out, &n_out, &st,
+                                     iters.data()),
+                  "dp_densify_iterate");
+            filtered = true;
         } else {
             check(dp_densify(ctx, use.data(), (int)(use.size() / 3), &out, &n_out, &st), "dp_densify");
         }
         // PMVS::FilterPatches (pmvs.h:27, undefined in the reference): dp_filter_patches spec
         std::vector<uint8_t> keep((size_t)n_out, 1);
-        if (do_filter && n_out > 0) {
-            dp_filter_options fo;
-            dp_default_filter_options(&fo);
-            check(dp_filter_patches(ctx, out, n_out, &fo, keep.data()), "dp_filter_patches");
-        }
+        if (do_filter && !filtered && n_out > 0)
+            check(dp_filter_patches(ctx, out, n_out, &filt, keep.data()), "dp_filter_patches");
         std::vector<dpio::CloudPoint> cloud;
         cloud.reserve((size_t)n_out);
         for (int64_t i = 0; i < n_out; ++i) {
@@ -641,17 +778,46 @@ int main(int argc, char **argv)
         }
         dp_ctx_destroy(ctx);
         dpio::write_ply(output, cloud);
+        // the per-round counts (one round: the densify and the optional filter)
+        if (iters.empty()) {
+            dp_iterate_stats one{};
+            one.offered = st.seeds_in;
+            one.reinserted = st.seed_patches;
+            one.patches = st.patches;
+            one.candidates = st.candidates;
+            one.evals = st.evals;
+            one.generations = st.generations;
+            iters.push_back(one);
+        }
+        if (!filtered) {
+            iters.back().filtered_out = n_out - (int64_t)cloud.size();
+            if (iterations > 1)
+                st.patches = (int64_t)cloud.size(); // as dp_densify_iterate reports: the survivors
+        }
+        std::string iters_json = "[";
+        for (size_t k = 0; k < iters.size(); ++k) {
+            char buf[320];
+            std::snprintf(buf, sizeof buf,
+                          "%s{\"offered\": %lld, \"reinserted\": %lld, \"patches\": %lld, \"filtered_out\": %lld, "
+                          "\"candidates\": %lld, \"evals\": %lld, \"generations\": %d}",
+                          k ? ", " : "", (long long)iters[k].offered, (long long)iters[k].reinserted,
+                          (long long)iters[k].patches, (long long)iters[k].filtered_out, (long long)iters[k].candidates,
+                          (long long)iters[k].evals, iters[k].generations);
+            iters_json += buf;
+        }
+        iters_json += "]";
         const double wall =
             std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
         std::printf("{\"output\": \"%s\", \"patches\": %lld, \"written\": %zu, \"seeds\": %zu, \"generated_seeds\": %s, "
                     "\"keypoints\": %lld, \"matches\": %lld, \"seed_ms\": %.3f, \"seed_patches\": %lld, "
                     "\"pops\": %lld, \"candidates\": %lld, \"evals\": %lld, \"generations\": %d, \"refine_ms\": %.3f, "
-                    "\"densify_ms\": %.3f, \"wall_ms\": %.3f, \"gpus\": %d, \"mode\": \"%s\", \"exchanged\": %lld}\n",
+                    "\"densify_ms\": %.3f, \"wall_ms\": %.3f, \"gpus\": %d, \"mode\": \"%s\", \"exchanged\": %lld, "
+                    "\"iterations\": %s}\n",
                     output.c_str(), (long long)st.patches, cloud.size(), use.size() / 3,
                     seeds_path.empty() ? "true" : "false", (long long)sst.keypoints, (long long)sst.matches,
                     sst.total_ms, (long long)st.seed_patches, (long long)st.pops, (long long)st.candidates,
                     (long long)st.evals, st.generations, st.refine_ms, st.total_ms, wall, gpus,
-                    fast ? "fast" : "parity", (long long)exchanged);
+                    fast ? "fast" : "parity", (long long)exchanged, iters_json.c_str());
         return 0;
     } catch (const std::exception &e) {
         std::fprintf(stderr, "densify: %s\n", e.what());
