@@ -28,8 +28,10 @@ from .pmvs import (  # noqa: F401
     empty_patches,
     mask_from_list,
     ncc_score,
+    read_pfm,
     read_scene_json,
     visible_list,
+    write_pfm,
     write_ply,
 )
 from . import synth  # noqa: F401

@@ -132,6 +132,27 @@ class DpFilterOptions(ctypes.Structure):
 FILTER_VISIBILITY, FILTER_NEIGHBORS = 1, 2
 
 
+class DpRenderOptions(ctypes.Structure):
+    _fields_ = [
+        ("splat_scale", ctypes.c_float),
+        ("max_radius_px", ctypes.c_int32),
+        ("flags", ctypes.c_int32),
+    ]
+
+
+class DpRenderStats(ctypes.Structure):
+    _fields_ = [
+        ("patches", ctypes.c_int64),
+        ("pairs", ctypes.c_int64),
+        ("pixel_tests", ctypes.c_int64),
+        ("covered_pixels", ctypes.c_int64),
+        ("render_ms", ctypes.c_double),
+    ]
+
+
+RENDER_ALL_FACING = 1
+
+
 class DpSynthConfig(ctypes.Structure):
     _fields_ = [
         ("n_views", ctypes.c_int32),
@@ -252,6 +273,9 @@ SIGNATURES = [
     ("dp_default_filter_options", None, [_P]),
     ("dp_filter_patches", _I, [_P, _P, ctypes.c_int64, _P, _P]),
     ("dp_filter_patches_device", _I, [_P, _P, ctypes.c_int64, _P, _P, _P]),
+    ("dp_default_render_options", None, [_P]),
+    ("dp_render_maps", _I, [_P, _P, ctypes.c_int64, _P, _P, _I, _P, _P, _P, _P, _P, _P]),
+    ("dp_render_maps_device", _I, [_P, _P, ctypes.c_int64, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P]),
     ("dp_last_kernel_ms", _I, [_P, _P]),
     ("dp_default_matcher_options", None, [_P]),
     ("dp_orb_pattern", _I, [_P]),

@@ -270,6 +270,16 @@ extern "C" int dp_ctx_destroy(dp_ctx *c)
     c->f_keep.release();
     c->f_rho.release();
     c->f_pat.release();
+    c->r_z.release();
+    c->r_count.release();
+    c->r_pairs.release();
+    c->r_slots.release();
+    c->r_slot_of.release();
+    c->r_out.release();
+    if (c->r_e0)
+        hipEventDestroy(c->r_e0);
+    if (c->r_e1)
+        hipEventDestroy(c->r_e1);
     c->pat.release();
     c->store.release();
     c->cand.release();

@@ -134,6 +134,15 @@ struct dp_ctx {
     DevBuf<uint8_t> f_alive, f_keep;
     DevBuf<double> f_rho;
     DevBuf<dp_patch> f_pat;
+    // dp_render_maps: z-buffer (8 B per pixel of the requested views), pair list,
+    // counters (dpk::kRenderCounters, then one per chunk), slot tables, the host
+    // form's output planes, timing events
+    DevBuf<unsigned long long> r_z, r_count;
+    DevBuf<dpk::RenderPair> r_pairs;
+    DevBuf<dpk::RenderSlot> r_slots;
+    DevBuf<int32_t> r_slot_of;
+    DevBuf<unsigned char> r_out;
+    hipEvent_t r_e0 = nullptr, r_e1 = nullptr;
     HostBuf<dp_patch> result; // dp_densify / dp_densify_result output (pinned)
     // dp_densify_iterate: per iteration {evaluations, filter survivors} on the
     // device (read once, at the end) and the filters' timing events

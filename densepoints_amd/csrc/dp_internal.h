@@ -250,6 +250,47 @@ hipError_t launch_filter_front(const FilterArgs &a, hipStream_t s);
 hipError_t launch_filter_visibility(const FilterArgs &a, uint8_t *keep, hipStream_t s);
 hipError_t launch_filter_neighbors(const FilterArgs &a, uint8_t *keep, hipStream_t s);
 
+// depth / index / normal / score maps (dp_render.hip; spec in
+// include/densepoints.h, dp_render_maps)
+struct RenderSlot { // one requested view
+    int32_t view, W, H, pad;
+    int64_t zoff; // first z-buffer word of the view
+    float *depth; // output planes, any may be null
+    int32_t *index;
+    float *normal;
+    float *score;
+};
+struct RenderPair { // one (patch, view) pair, its uniform fp64 done once
+    double A[9], D, s, RR; // adj(H), det(H), |e1|^2, R^2
+    int32_t x0, x1, y0, y1; // clipped candidate box, inclusive
+    int32_t slot, index;
+};
+constexpr int kRenderCounters = 4; // patches, pairs, pixel tests, covered pixels
+struct RenderArgs {
+    const dpg::ViewDev *views;
+    int32_t V;
+    int32_t n_slots;
+    const dp_patch *patches;
+    const uint8_t *keep; // optional
+    const double *rho;
+    int64_t n;
+    const RenderSlot *slots;
+    const int32_t *slot_of; // DP_MAX_VIEWS entries: slot of a view, -1 = not requested
+    uint64_t req[2];        // requested views as a mask
+    double splat_scale, max_radius;
+    int32_t all_facing, pad;
+    RenderPair *pairs;
+    int64_t pair_cap;
+    unsigned long long *zbuf;  // per pixel: f32 depth bits << 32 | index, ~0 = empty
+    unsigned long long *count; // kRenderCounters, then one pair count per chunk
+};
+// pairs of patches [i0, i1) into a.pairs, counted in a.count[kRenderCounters + chunk];
+// (i1 - i0) * n_slots <= pair_cap
+hipError_t launch_render_pairs(const RenderArgs &a, int64_t i0, int64_t i1, int chunk, hipStream_t s);
+// the chunk's pairs into the z-buffer (sized from the device-held count)
+hipError_t launch_render_raster(const RenderArgs &a, int chunk, hipStream_t s);
+hipError_t launch_render_resolve(const RenderArgs &a, int max_pixels, hipStream_t s);
+
 hipError_t launch_refine(const RefineArgs &a, hipStream_t s);
 hipError_t launch_pyr_down(const PyrPlane *d_src, const PyrPlane *d_dst, int V, int max_dw, int max_dh,
                            hipStream_t s);

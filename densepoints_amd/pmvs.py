@@ -34,6 +34,8 @@ __all__ = [
     "ncc_score",
     "read_scene_json",
     "write_ply",
+    "write_pfm",
+    "read_pfm",
     "empty_patches",
     "visible_list",
     "mask_from_list",
@@ -184,6 +186,8 @@ class Engine:
         check(rc)
         self.views: list[View] = []
         self._keep = []
+        self._V = 0      # views set (either form)
+        self._level = 0  # current pyramid level
 
     @property
     def handle(self):
@@ -226,6 +230,7 @@ class Engine:
             imgs[i].bgr = im.ctypes.data
         self._check(lib.dp_set_views(self._ctx, V, ptr(P), imgs))
         self.views = list(views)
+        self._V, self._level = V, 0
 
     def set_views_device(self, P: np.ndarray, widths, heights, pitches, dev_ptrs):
         V = len(dev_ptrs)
@@ -236,15 +241,18 @@ class Engine:
         arr = (ctypes.c_void_p * V)(*[int(p) for p in dev_ptrs])
         self._check(lib.dp_set_views_device(self._ctx, V, ptr(P), ptr(w), ptr(h), ptr(pt), arr))
         self._keep = [P, w, h, pt, arr]
+        self._V, self._level = V, 0
 
     # ---- image pyramid (include/densepoints.h dp_build_pyramid / dp_set_level) ----
     def build_pyramid(self, levels: int):
         """Levels 1..levels-1 by cv::pyrDown on the device (level 0 = the views)."""
         self._check(lib.dp_build_pyramid(self._ctx, int(levels)))
+        self._level = 0
 
     def set_level(self, level: int):
         """Run the patch loop on pyramid level `level` (P rows 0-1 scaled by 2^-level)."""
         self._check(lib.dp_set_level(self._ctx, int(level)))
+        self._level = int(level)
 
     def level_info(self, level: int, view: int):
         w, h, d = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_void_p()
@@ -549,6 +557,131 @@ class Engine:
                                 if name != "reserved"} for k in range(int(iterations))]
         return result_array(out.value, n.value, copy), stats
 
+    # ---- per-view maps (include/densepoints.h dp_render_maps) ----
+    def view_sizes(self, views=None) -> list[tuple[int, int]]:
+        """(width, height) of views at the current pyramid level."""
+        V = self.num_views()
+        return [self.level_info(self._level, v)[:2] for v in (range(V) if views is None else views)]
+
+    def num_views(self) -> int:
+        return self._V
+
+    def render_maps(self, patches: np.ndarray, views=None, keep: np.ndarray | None = None, splat_scale: float = 1.0,
+                    max_radius_px: int = 32, all_facing: bool = False, normals: bool = False,
+                    scores: bool = False) -> dict:
+        """dp_render_maps: every patch splatted as an oriented disc of radius
+        splat_scale * rho(p) into `views` (None = all) at the current level,
+        nearest disc per pixel.  Returns {"views", "depth" (f32, 0 = empty),
+        "index" (int32, -1 = empty), "normal" / "score" when asked for, "stats"},
+        each map a list of H x W (x 3) arrays in the order of "views"."""
+        patches = np.ascontiguousarray(patches)
+        assert patches.dtype == PATCH_DTYPE
+        ro, vid, keep = check_render_args(len(patches), self.num_views(), views, keep, splat_scale, max_radius_px,
+                                          all_facing)
+        sizes = self.view_sizes(vid)
+        out = {"views": [int(v) for v in vid],
+               "depth": [np.zeros((h, w), np.float32) for w, h in sizes],
+               "index": [np.zeros((h, w), np.int32) for w, h in sizes]}
+        if normals:
+            out["normal"] = [np.zeros((h, w, 3), np.float32) for w, h in sizes]
+        if scores:
+            out["score"] = [np.zeros((h, w), np.float32) for w, h in sizes]
+
+        def table(key):
+            return (ctypes.c_void_p * len(vid))(*[a.ctypes.data for a in out[key]]) if key in out else None
+
+        st = N.DpRenderStats()
+        self._check(lib.dp_render_maps(self._ctx, ptr(patches), len(patches), ptr(keep), ptr(vid), len(vid),
+                                       ctypes.byref(ro), table("depth"), table("index"), table("normal"),
+                                       table("score"), ctypes.byref(st)))
+        out["stats"] = {name: getattr(st, name) for name, _ in N.DpRenderStats._fields_}
+        return out
+
+    def render_maps_device(self, d_patches: int, n: int, d_keep: int | None, views, d_depth=None, d_index=None,
+                           d_normal=None, d_score=None, splat_scale: float = 1.0, max_radius_px: int = 32,
+                           all_facing: bool = False, stream: int | None = None, stats: bool = True) -> dict | None:
+        """dp_render_maps_device: n device-resident patches (the context's own
+        store included) and optional device keep flags into device planes --
+        d_depth / d_index / d_normal / d_score are lists of device addresses, one
+        per entry of `views` (None or 0 = not wanted).  Queued on `stream`;
+        waits only for the statistics (stats=False: no wait, returns None)."""
+        ro, vid, _ = check_render_args(int(n), self.num_views(), views, None, splat_scale, max_radius_px, all_facing)
+
+        def table(addrs):
+            if addrs is None:
+                return None
+            if len(addrs) != len(vid):
+                raise ValueError("render_maps_device: one plane address per view")
+            return (ctypes.c_void_p * len(vid))(*[int(a) if a else None for a in addrs])
+
+        st = N.DpRenderStats()
+        self._check(lib.dp_render_maps_device(self._ctx, ctypes.c_void_p(d_patches) if d_patches else None, int(n),
+                                              ctypes.c_void_p(d_keep) if d_keep else None, ptr(vid), len(vid),
+                                              ctypes.byref(ro), table(d_depth), table(d_index), table(d_normal),
+                                              table(d_score), ctypes.byref(st) if stats else None,
+                                              ctypes.c_void_p(stream) if stream else None))
+        return {name: getattr(st, name) for name, _ in N.DpRenderStats._fields_} if stats else None
+
+
+def check_render_args(n: int, V: int, views, keep, splat_scale: float, max_radius_px: int, all_facing: bool):
+    """Argument validation of Engine.render_maps[_device] (the limits of
+    dp_render_maps, raised as ValueError before any device call); returns
+    (dp_render_options, view ids as int32, keep as uint8 or None)."""
+    if not 0 <= n <= 2**31 - 1:
+        raise ValueError("render_maps: at most 2^31 - 1 patches")
+    if not (isinstance(splat_scale, (int, float)) and splat_scale > 0 and np.isfinite(splat_scale)):
+        raise ValueError("render_maps: splat_scale must be > 0")
+    if int(max_radius_px) != max_radius_px or not 1 <= int(max_radius_px) <= 255:
+        raise ValueError("render_maps: max_radius_px must be in 1..255")
+    vid = np.arange(V, dtype=np.int32) if views is None else np.asarray(list(views), dtype=np.int64)
+    if vid.ndim != 1 or len(vid) == 0:
+        raise ValueError("render_maps: no views")
+    if (vid < 0).any() or (vid >= V).any() or len(set(vid.tolist())) != len(vid):
+        raise ValueError("render_maps: view ids must be unique and < %d" % V)
+    if keep is not None:
+        keep = np.ascontiguousarray(keep, dtype=np.uint8)
+        if keep.shape != (n,):
+            raise ValueError("render_maps: one keep flag per patch")
+    ro = N.DpRenderOptions(float(splat_scale), int(max_radius_px), N.RENDER_ALL_FACING if all_facing else 0)
+    return ro, np.ascontiguousarray(vid, dtype=np.int32), keep
+
+
+def write_pfm(path: str, array: np.ndarray) -> None:
+    """Little-endian PFM ("Pf" 1 channel, "PF" 3 channels; scale -1.0), rows
+    stored bottom-up as the format requires."""
+    a = np.asarray(array, dtype=np.float32)
+    if a.ndim == 3 and a.shape[2] == 1:
+        a = a[:, :, 0]
+    if not (a.ndim == 2 or (a.ndim == 3 and a.shape[2] == 3)):
+        raise ValueError("write_pfm: H x W or H x W x 3 expected")
+    with open(path, "wb") as f:
+        f.write(b"%s\n%d %d\n-1.0\n" % (b"PF" if a.ndim == 3 else b"Pf", a.shape[1], a.shape[0]))
+        f.write(np.ascontiguousarray(a[::-1]).astype("<f4").tobytes())
+
+
+def read_pfm(path: str) -> np.ndarray:
+    """A PFM written by write_pfm or any conforming writer (either byte order),
+    as an H x W (x 3) float32 array with row 0 at the top."""
+    with open(path, "rb") as f:
+        data = f.read()
+    parts, pos = [], 0
+    while len(parts) < 4:  # magic, width, height, scale: whitespace-separated
+        while data[pos:pos + 1].isspace():
+            pos += 1
+        end = pos
+        while end < len(data) and not data[end:end + 1].isspace():
+            end += 1
+        parts.append(data[pos:end])
+        pos = end
+    pos += 1  # the single whitespace byte after the scale
+    if parts[0] not in (b"PF", b"Pf"):
+        raise ValueError("read_pfm: not a PFM file")
+    ch = 3 if parts[0] == b"PF" else 1
+    w, h, scale = int(parts[1]), int(parts[2]), float(parts[3])
+    a = np.frombuffer(data, dtype="<f4" if scale < 0 else ">f4", count=w * h * ch, offset=pos)
+    a = a.reshape((h, w, 3) if ch == 3 else (h, w))[::-1]
+    return np.ascontiguousarray(a, dtype=np.float32)
+
 
 def check_iterations(iterations: int, filter_passes: int) -> int:
     """the rounds of an iterated densify (PMVS.run, dist.densify_partitioned*):
@@ -577,6 +710,7 @@ class PMVS:
         self.views: list[View] = []
         self.patches = empty_patches(0)
         self.stats: dict = {}
+        self._ran = False
 
     def add_camera(self, view: View) -> None:
         # PMVS::AddCamera (pmvs.cpp:11-20): views whose image failed to load are dropped
@@ -611,6 +745,7 @@ class PMVS:
                 self.stats["filtered_out"] = int(sum(r["filtered_out"] for r in self.stats["iterations"]))
                 if seed_stats is not None:
                     self.stats["seed_generation"] = seed_stats
+                self._ran = True
                 return True
             self.patches, self.stats = eng.densify(np.asarray(seeds_xyz, dtype=np.float64))
             if seed_stats is not None:
@@ -619,10 +754,21 @@ class PMVS:
                 keep = eng.filter_patches(self.patches, filter_passes)
                 self.stats["filtered_out"] = int(len(keep) - keep.sum())
                 self.patches = self.patches[keep == 1]
+        self._ran = True
         return True
 
     def get_point_cloud(self) -> np.ndarray:
         return self.patches
+
+    def depth_maps(self, **kw) -> dict:
+        """Per-view depth / index (and normal, score) maps of the last run()'s
+        result -- the survivors after run(iterations=N) or filter_passes != 0 --
+        by Engine.render_maps, whose keyword arguments pass through."""
+        if not self._ran:
+            raise ValueError("depth_maps: call run() first")
+        with Engine(self.options, self.device) as eng:
+            eng.set_views(self.views)
+            return eng.render_maps(self.patches, **kw)
 
 
 def ncc_score(a: np.ndarray, b: np.ndarray, denom_min: float = 0.1) -> float:

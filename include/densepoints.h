@@ -398,6 +398,92 @@ int dp_densify_iterate(dp_ctx *ctx, const double *seeds_xyz, int n, int iteratio
                        const dp_patch **out, int64_t *n_out, dp_densify_stats *stats,
                        dp_iterate_stats *per_iter /* iterations entries, may be NULL */);
 
+/* ---- per-view depth / index / normal / score maps of a patch set ------------
+ * No reference counterpart (the reference's only product is the point list).
+ * Every patch is splatted as an oriented disc in its own plane into the
+ * requested views of the CURRENT level (dp_set_level: level-L P, W, H); each
+ * pixel keeps the nearest disc.  Every decision is a function of one (patch,
+ * view, pixel) alone and the per-pixel resolve is a minimum, so the result
+ * does not depend on the patch order or the launch geometry.  All arithmetic is
+ * fp64, one IEEE rounding per operation, in exactly the order written (the
+ * build has -ffp-contract=off); dot(a, b) = (a0*b0 + a1*b1) + a2*b2 and
+ * row_r(P, X) = ((P[4r]*X0 + P[4r+1]*X1) + P[4r+2]*X2) + P[4r+3] throughout;
+ * project(P, X) = (row_0 / row_2, row_1 / row_2).
+ *
+ * Patch p (index i, keep NULL or keep[i] != 0) takes part iff the six floats of
+ * pos and normal are finite, ref < V and rho(p) > 0, where rho(p) is the
+ * filter's: with rv = view ref, (cu, cv) = project(P_rv, X0), (qu, qv) =
+ * project(P_rv, X0 + xr_rv) (componentwise sum), du = qu - cu, dv = qv - cv,
+ * dx = sqrt(du*du + dv*dv), rho = dx > 0 ? grid_scale / dx : 0.
+ * X0, n = the stored f32 pos, normal widened to fp64 (n is NOT renormalised);
+ * R = (double)splat_scale * rho(p).
+ *
+ * (p, v) is a pair iff, tested in this order,
+ *   1. v is requested, and v is in vis(p) -- or, with DP_RENDER_ALL_FACING,
+ *      dot(n, d) > 0 for d_k = X0[k] - C_v[k] instead of the vis test (a stored
+ *      normal points AWAY from the cameras that see the patch: InitRelatedImages
+ *      takes the angle between n and X - C, patch.cpp:36-47);
+ *   2. d0 = row_2(P_v, X0) > 0;
+ *   3. frame: t = dot(xr_v, n) (xr_v = the view's own camera x-axis,
+ *      GetXAxis().normalized()), e1_k = xr_v[k] - t*n[k], s = dot(e1, e1);
+ *      skipped unless s >= 1e-12;  e2 = n x e1 (e2_0 = n1*e1_2 - n2*e1_1,
+ *      e2_1 = n2*e1_0 - n0*e1_2, e2_2 = n0*e1_1 - n1*e1_0);
+ *   4. box: (cu, cv) = project(P_v, X0); skipped unless |cu| < 2e9 and
+ *      |cv| < 2e9 (NaN skips); (qu, qv) = project(P_v, X0 + xr_v), dxv =
+ *      sqrt(du*du + dv*dv) as above; Bq = (2.0*R)*dxv + 2.0, B = Bq <
+ *      (double)max_radius_px ? Bq : (double)max_radius_px; columns x0 =
+ *      max(0, floor(cu - B)) .. x1 = min(W - 1, ceil(cu + B)), rows y0, y1 the
+ *      same from cv and H; skipped if x0 > x1 or y0 > y1.
+ * The box is normative: no pixel outside it is ever covered by the pair.
+ *
+ * Plane-to-pixel homography H (3x3, rows r = 0..2) and its adjugate:
+ *   h[3r] = (P[4r]*e1_0 + P[4r+1]*e1_1) + P[4r+2]*e1_2,  h[3r+1] = the same
+ *   with e2,  h[3r+2] = row_r(P_v, X0);
+ *   A0 = h4*h8 - h5*h7, A1 = h2*h7 - h1*h8, A2 = h1*h5 - h2*h4,
+ *   A3 = h5*h6 - h3*h8, A4 = h0*h8 - h2*h6, A5 = h2*h3 - h0*h5,
+ *   A6 = h3*h7 - h4*h6, A7 = h1*h6 - h0*h7, A8 = h0*h4 - h1*h3,
+ *   D = (h0*A0 + h1*A3) + h2*A6.
+ * Integer pixel (x, y) of the box: a = (A0*x + A1*y) + A2, b = (A3*x + A4*y) +
+ * A5, w = (A6*x + A7*y) + A8.  It is covered by the pair iff (w > 0 and D > 0,
+ * or w < 0 and D < 0) and (a*a + b*b)*s <= (R*R)*(w*w); its depth is z =
+ * (float)(D / w) (the exact ray-plane depth: row 3 of H times A is D e3),
+ * accepted iff z > 0.  Per pixel the minimum of key = (f32 bits of z) << 32 | i
+ * wins: nearest depth, ties to the lowest patch index (the rule of front()).
+ *
+ * Outputs, one pointer per requested view in the order of `views`, each
+ * row-major W x H of that view at the current level; an array or an entry may
+ * be NULL: depth f32 (0 where empty), index int32 (-1), normal 3 x f32 (the
+ * winner's stored normal, 0), score f32 (the winner's score, 0).
+ * Errors (DP_E_ARG): n < 0 or n > 2^31 - 1, n_views outside 1..V, a view id
+ * repeated or >= V, splat_scale not > 0, max_radius_px outside 1..255; no views
+ * set: DP_E_STATE.  ro NULL = the defaults.
+ * stats (may be NULL), counted on the device: patches taking part, pairs,
+ * pixel_tests = the sum of the pairs' box areas, covered_pixels = non-empty
+ * pixels after the resolve; render_ms = device time of the call's kernels.
+ * The device form takes device patches (the context's own store,
+ * dp_densify_store_device, included), device keep flags (the filter's) and
+ * device output planes, queues everything on `stream` (NULL = the context's)
+ * and waits only when stats != NULL, for the statistics read. */
+#define DP_RENDER_ALL_FACING 1
+typedef struct dp_render_options {
+    float splat_scale;      /* 1.0  disc radius in units of rho(p)                  */
+    int32_t max_radius_px;  /* 32   bound of the candidate box half-size (1..255)   */
+    int32_t flags;          /* DP_RENDER_* bits (default 0)                         */
+} dp_render_options;
+typedef struct dp_render_stats {
+    int64_t patches, pairs, pixel_tests, covered_pixels;
+    double render_ms;
+} dp_render_stats;
+
+void dp_default_render_options(dp_render_options *ro);
+int dp_render_maps(dp_ctx *ctx, const dp_patch *patches, int64_t n, const uint8_t *keep /* NULL = all */,
+                   const int32_t *views, int n_views, const dp_render_options *ro, float *const *depth,
+                   int32_t *const *index, float *const *normal, float *const *score, dp_render_stats *stats);
+int dp_render_maps_device(dp_ctx *ctx, const dp_patch *d_patches, int64_t n, const uint8_t *d_keep,
+                          const int32_t *views, int n_views, const dp_render_options *ro, float *const *d_depth,
+                          int32_t *const *d_index, float *const *d_normal, float *const *d_score,
+                          dp_render_stats *stats, void *stream);
+
 /* ---- seed generation: Features::Matcher::GenerateSeeds ---
  * modules/features/matcher.cpp:18-43 with the default MatcherOptions
  * (matcher.h:21-32: ORB detector, kNN matcher, no direct epipolar matching,

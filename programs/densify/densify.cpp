@@ -11,6 +11,7 @@
 //           [--device N] [--max-pops N] [--level L] [--filter] [--iterations N] [--check-only]
 //           [--features N] [--fast-threshold T] [--epipolar-matching] [--matcher knn|flann]
 //           [--detector orb|akaze] [--akaze-threshold T]
+//           [--depth-maps DIR [--splat-scale S] [--depth-normals]]
 //   densify --synthetic V,W,H,KIND --write-scene DIR   (deterministic test scene
 //           written as scene.json + PPM images + seeds.xyz; no GPU needed)
 #include "scene_io.h"
@@ -22,6 +23,7 @@
 
 #include <chrono>
 #include <climits>
+#include <cerrno>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -56,6 +58,10 @@ void usage()
                  "                            (fast: the performance-mode refine -- LDS-staged gray\n"
                  "                             tiles, fused CG -- for the seed stage and every expansion;\n"
                  "                             gradient 1: analytic, 0: forward differences)\n"
+                 "               [--depth-maps DIR [--splat-scale S] [--depth-normals]]  (after the PLY:\n"
+                 "                             DIR/depth_%%04d.pfm, and normal_%%04d.pfm, of every view --\n"
+                 "                             the written patches as discs of radius S x rho, nearest\n"
+                 "                             per pixel: dp_render_maps)\n"
                  "       densify --synthetic V,W,H,KIND --write-scene DIR\n");
 }
 
@@ -515,11 +521,28 @@ int densify_multi(std::vector<dp_ctx *> &ctxs, const std::vector<int> &devices, 
     return DP_OK;
 }
 
+// little-endian PFM ("Pf" 1 channel, "PF" 3), rows bottom-up as the format requires
+void write_pfm(const std::string &path, const float *px, int w, int h, int channels)
+{
+    std::FILE *f = std::fopen(path.c_str(), "wb");
+    if (!f)
+        throw std::runtime_error("cannot write " + path);
+    std::fprintf(f, "%s\n%d %d\n-1.0\n", channels == 3 ? "PF" : "Pf", w, h);
+    const size_t row = (size_t)w * (size_t)channels;
+    bool ok = true;
+    for (int y = h - 1; y >= 0 && ok; --y)
+        ok = std::fwrite(px + (size_t)y * row, sizeof(float), row, f) == row;
+    if (std::fclose(f) != 0 || !ok)
+        throw std::runtime_error("short write to " + path);
+}
+
 } // namespace
 
 int main(int argc, char **argv)
 {
-    std::string input, settings, output = "points.ply", seeds_path, synth, scene_dir;
+    std::string input, settings, output = "points.ply", seeds_path, synth, scene_dir, depth_dir;
+    double splat_scale = 1.0;
+    bool depth_normals = false;
     int device = 0, gpus = 1;
     bool force_multi = false;
     std::string exchange_mode = "auto";
@@ -602,6 +625,15 @@ int main(int argc, char **argv)
         else if (a == "--fast-gradient") fast_gradient = std::atoi(next().c_str());
         else if (a == "--synthetic") synth = next();
         else if (a == "--write-scene") scene_dir = next();
+        else if (a == "--depth-maps") depth_dir = next();
+        else if (a == "--splat-scale") {
+            splat_scale = std::atof(next().c_str());
+            if (!(splat_scale > 0.0)) {
+                std::fprintf(stderr, "densify: --splat-scale expects a positive number\n");
+                return 2;
+            }
+        }
+        else if (a == "--depth-normals") depth_normals = true;
         else if (a == "-h" || a == "--help") {
             usage();
             return 0;
@@ -776,8 +808,51 @@ int main(int argc, char **argv)
             }
             cloud.push_back(cp);
         }
-        dp_ctx_destroy(ctx);
         dpio::write_ply(output, cloud);
+        // --depth-maps: the written patches as per-view depth (and normal) maps of
+        // the level the densify ran on (dp_render_maps), one view at a time; with
+        // --gpus N this context (rank 0) renders, the store being replicated
+        char depth_json[160] = "";
+        if (!depth_dir.empty()) {
+            if (mkdir(depth_dir.c_str(), 0777) != 0 && errno != EEXIST)
+                throw std::runtime_error("cannot create " + depth_dir);
+            std::vector<dp_patch> kept;
+            kept.reserve(cloud.size());
+            for (int64_t i = 0; i < n_out; ++i)
+                if (keep[i])
+                    kept.push_back(out[i]);
+            dp_render_options ro;
+            dp_default_render_options(&ro);
+            ro.splat_scale = (float)splat_scale;
+            int64_t covered = 0;
+            double render_ms = 0.0;
+            std::vector<float> depth, normal;
+            for (int32_t v = 0; v < (int32_t)imgs.size(); ++v) {
+                int32_t w = 0, h = 0;
+                check(dp_level_info(ctx, level, v, &w, &h, nullptr), "dp_level_info");
+                depth.assign((size_t)w * h, 0.0f);
+                if (depth_normals)
+                    normal.assign((size_t)w * h * 3, 0.0f);
+                float *pd = depth.data(), *pn = depth_normals ? normal.data() : nullptr;
+                dp_render_stats rs;
+                check(dp_render_maps(ctx, kept.data(), (int64_t)kept.size(), nullptr, &v, 1, &ro, &pd, nullptr,
+                                     depth_normals ? &pn : nullptr, nullptr, &rs),
+                      "dp_render_maps");
+                covered += rs.covered_pixels;
+                render_ms += rs.render_ms;
+                char name[64];
+                std::snprintf(name, sizeof name, "/depth_%04d.pfm", (int)v);
+                write_pfm(depth_dir + name, pd, w, h, 1);
+                if (depth_normals) {
+                    std::snprintf(name, sizeof name, "/normal_%04d.pfm", (int)v);
+                    write_pfm(depth_dir + name, pn, w, h, 3);
+                }
+            }
+            std::snprintf(depth_json, sizeof depth_json,
+                          ", \"depth_maps\": {\"views\": %zu, \"covered_pixels\": %lld, \"render_ms\": %.3f}",
+                          imgs.size(), (long long)covered, render_ms);
+        }
+        dp_ctx_destroy(ctx);
         // the per-round counts (one round: the densify and the optional filter)
         if (iters.empty()) {
             dp_iterate_stats one{};
@@ -812,12 +887,12 @@ int main(int argc, char **argv)
                     "\"keypoints\": %lld, \"matches\": %lld, \"seed_ms\": %.3f, \"seed_patches\": %lld, "
                     "\"pops\": %lld, \"candidates\": %lld, \"evals\": %lld, \"generations\": %d, \"refine_ms\": %.3f, "
                     "\"densify_ms\": %.3f, \"wall_ms\": %.3f, \"gpus\": %d, \"mode\": \"%s\", \"exchanged\": %lld, "
-                    "\"iterations\": %s}\n",
+                    "\"iterations\": %s%s}\n",
                     output.c_str(), (long long)st.patches, cloud.size(), use.size() / 3,
                     seeds_path.empty() ? "true" : "false", (long long)sst.keypoints, (long long)sst.matches,
                     sst.total_ms, (long long)st.seed_patches, (long long)st.pops, (long long)st.candidates,
                     (long long)st.evals, st.generations, st.refine_ms, st.total_ms, wall, gpus,
-                    fast ? "fast" : "parity", (long long)exchanged, iters_json.c_str());
+                    fast ? "fast" : "parity", (long long)exchanged, iters_json.c_str(), depth_json);
         return 0;
     } catch (const std::exception &e) {
         std::fprintf(stderr, "densify: %s\n", e.what());
