@@ -1,6 +1,8 @@
-// dp_ctx.h -- the context object behind the C ABI, shared by the C-ABI
-// translation units (dp_capi.hip: views, refine, densify; dp_seeds.hip:
-// seed generation).
+// dp_ctx.h -- the context object behind the C ABI and the description of a
+// refine launch, shared by the C-ABI translation units (dp_capi.hip: contexts,
+// views, pyramid, filter, batch refine/expand; dp_densify.hip: the densify
+// engine; dp_fast.hip: performance mode; dp_synth.hip: synthetic scenes and
+// probes; dp_seeds_capi.hip: seed generation; dp_render.hip: maps).
 #pragma once
 
 #include "dp_internal.h"
@@ -193,15 +195,56 @@ struct dp_ctx {
     int gray_level = -1, gray_V = 0;
 };
 
-// performance-mode launch (dp_fast.hip): refine/eval of n patches in device
-// memory, or the 4 (n / 4) expansion children of parents
-// d_parents[parent0 + (items ? items[k] : k)], k < n / 4, of which only those
-// with a parent index below max_pops expand (dp_densify's pop cap)
-// gen: a device-resident BFS generation (n and parent0 read on the device)
-// epi: the densify epilogue (dpk::kEpi* bits; claims at seq0 + index into c->grid)
-int dp_fast_launch(dp_ctx *c, dp_patch *d, int n, int cell, int mode, uint8_t *acc, const dp_patch *d_parents,
-                   hipStream_t s, int64_t parent0 = 0, const int64_t *items = nullptr,
-                   int64_t max_pops = INT64_MAX, const dpk::GenDev *gen = nullptr, int epi = 0, uint32_t seq0 = 0);
+namespace dpk {
+
+// One refine launch as its caller describes it, for either engine (the parity
+// kernel, dp_kernels.hip, or the performance kernel, dp_fast.hip); everything
+// an engine derives from the context stays in refine_args / dp_fast_launch.
+// Refine/eval of n patches in device memory, or with parents the 4 (n / 4)
+// expansion children of parents[parent0 + (items ? items[k] : k)], k < n / 4.
+// Callers brace-initialise the first five members, in this order, and name the rest.
+struct RefineJob {
+    dp_patch *patches = nullptr; // in/out; with parents, the children (out)
+    uint8_t *accept = nullptr;   // optional
+    int n = 0;                   // with gen: the candidate buffers' capacity
+    int cell = 0;
+    int mode = 0;                // DP_MODE_*; >= DP_MODE_FAST_EVAL: the performance kernel
+    const dp_patch *parents = nullptr;
+    int64_t parent0 = 0;
+    const int64_t *items = nullptr;
+    // only parents with an index below max_pops expand (dp_densify's pop cap);
+    // both kernels read it under `parents` only, so a launch without parents
+    // leaves the default
+    int64_t max_pops = INT64_MAX;
+    const GenDev *gen = nullptr; // a device-resident BFS generation (its size and parent0 read on the device)
+    int epi = 0;                 // the densify epilogue (kEpi* bits; claims at seq0 + index into c->grid)
+    uint32_t seq0 = 0;
+    // The (e0, e1) event pair behind dp_last_kernel_ms.  The performance engine
+    // records it on every launch; the parity engine records it (and sets
+    // c->timed) unless this is set, which refine_gen does: its batch times
+    // each generation with the gev events, and dp_last_kernel_ms keeps naming
+    // the last launch outside the batch.
+    bool parity_untimed = false;
+};
+
+} // namespace dpk
+
+// performance-mode launch of a job (dp_fast.hip)
+int dp_fast_launch(dp_ctx *c, const dpk::RefineJob &job, hipStream_t s);
+
+// shared by the batch API (dp_capi.hip, where they live) and the densify
+// engine (dp_densify.hip)
+dpk::RefineArgs refine_args(dp_ctx *c, const dpk::RefineJob &job);
+// the job on the engine job.mode names
+int launch_job(dp_ctx *c, const dpk::RefineJob &job, hipStream_t s);
+int check_refine(dp_ctx *c, int n, int cell, int mode);
+// n host seed points -> seed patches in device memory d_out (async on s)
+int seeds_device(dp_ctx *c, const double *xyz, int64_t n, dp_patch *d_out, hipStream_t s);
+// the epilogue a densify generation's refine runs: the colours always, the
+// claims when the organizer's capacity is 1 (k > 1 claims in rounds)
+int densify_epi(const dp_ctx *c);
+// View::SetProjectionMatrix: the ViewDev of a W x H view with projection P
+int view_from_P(const double *P, int W, int H, int gs, dpg::ViewDev &v);
 
 static inline int fail(dp_ctx *c, int code, const std::string &msg)
 {

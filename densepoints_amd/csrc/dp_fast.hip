@@ -1945,34 +1945,36 @@ template <int B> static hipError_t fast_dispatch(int N, const dpk::FastArgs &a, 
 #endif
 }
 
-int dp_fast_launch(dp_ctx *c, dp_patch *d, int n, int cell, int mode, uint8_t *acc, const dp_patch *d_parents,
-                   hipStream_t s, int64_t parent0, const int64_t *items, int64_t max_pops, const dpk::GenDev *gen,
-                   int epi, uint32_t seq0)
+int dp_fast_launch(dp_ctx *c, const dpk::RefineJob &job, hipStream_t s)
 {
     int rc = ensure_gray(c);
     if (rc != DP_OK)
         return rc;
+    const int cell = job.cell;
+    const dpk::GenDev *gen = job.gen;
     dpk::FastArgs a{};
     a.views = c->d_views;
     a.gray = (const dpk::GrayPlane *)c->d_gray;
     a.cams = (const dpk::FastCam *)((const char *)c->d_gray + fast_cam_offset(c->V));
     a.V = c->V;
     a.cell = cell;
-    a.mode = mode;
-    a.n = n;
+    a.mode = job.mode;
+    // a device-resident generation is sized on the device: its launch is laid
+    // out as for n = 0 (one candidate per dequeue), whatever the buffers hold
+    a.n = gen ? 0 : job.n;
     a.opt = c->opt;
     a.fo = c->fopt;
-    a.patches = d;
-    a.accept = acc;
+    a.patches = job.patches;
+    a.accept = job.accept;
     a.work = c->d_work;
     a.evals = c->d_evals;
-    a.parents = d_parents;
-    a.parent0 = parent0;
-    a.items = items;
-    a.max_pops = max_pops;
+    a.parents = job.parents;
+    a.parent0 = job.parent0;
+    a.items = job.items;
+    a.max_pops = job.max_pops;
     a.gen = gen;
-    a.epi = epi;
-    a.seq0 = seq0;
+    a.epi = job.epi;
+    a.seq0 = job.seq0;
     a.claim_grid = c->grid.p;
     a.grid_scale = (double)c->opt.grid_scale;
     // the InitRelatedImages thresholds as cosines, by the host libm (the
@@ -2071,51 +2073,6 @@ extern "C" int dp_read_gray(dp_ctx *c, int view, uint16_t *out)
         off += (size_t)gray_pitch(c->hv[v].W) * (size_t)c->hv[v].H;
     DP_HIP(c, hipMemcpy2D(out, (size_t)W * 2, (const __half *)c->gray_pool + off, (size_t)pitch * 2, (size_t)W * 2,
                           (size_t)H, hipMemcpyDeviceToHost));
-    return DP_OK;
-}
-
-extern "C" int dp_fast_expand_batch_device(dp_ctx *c, const dp_patch *d_parents, int n, dp_patch *d_children,
-                                           uint8_t *d_accept, void *stream)
-{
-    if (!c)
-        return DP_E_ARG;
-    if (!c->V)
-        return fail(c, DP_E_STATE, "no views set");
-    const int cell = c->opt.expand_cell_size;
-    if (n < 0 || cell < 2 || cell > DP_MAX_CELL)
-        return fail(c, DP_E_ARG, "fast expand: bad n/cell");
-    if (n == 0)
-        return DP_OK;
-    if ((int64_t)n * 4 > INT32_MAX || !d_parents || !d_children)
-        return fail(c, DP_E_ARG, "fast expand: bad arguments");
-    hipSetDevice(c->device);
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    return dp_fast_launch(c, d_children, 4 * n, cell, DP_MODE_FAST_REFINE, d_accept, d_parents, s);
-}
-
-extern "C" int dp_fast_expand_batch(dp_ctx *c, const dp_patch *parents, int n, dp_patch *children,
-                                    uint8_t *accept_out)
-{
-    if (!c)
-        return DP_E_ARG;
-    if (n < 0)
-        return fail(c, DP_E_ARG, "fast expand: bad n");
-    if (n == 0)
-        return DP_OK;
-    if (!parents || !children)
-        return fail(c, DP_E_ARG, "fast expand: null arrays");
-    hipSetDevice(c->device);
-    DP_HIP(c, c->cand.reserve((size_t)n));
-    DP_HIP(c, c->pat.reserve((size_t)4 * n));
-    DP_HIP(c, c->ok.reserve((size_t)4 * n));
-    DP_HIP(c, hipMemcpyAsync(c->cand.p, parents, sizeof(dp_patch) * n, hipMemcpyHostToDevice, c->stream));
-    int rc = dp_fast_expand_batch_device(c, c->cand.p, n, c->pat.p, c->ok.p, c->stream);
-    if (rc != DP_OK)
-        return rc;
-    DP_HIP(c, hipMemcpyAsync(children, c->pat.p, sizeof(dp_patch) * 4 * n, hipMemcpyDeviceToHost, c->stream));
-    if (accept_out)
-        DP_HIP(c, hipMemcpyAsync(accept_out, c->ok.p, (size_t)4 * n, hipMemcpyDeviceToHost, c->stream));
-    DP_HIP(c, hipStreamSynchronize(c->stream));
     return DP_OK;
 }
 
