@@ -17,6 +17,7 @@ from ._native import (  # noqa: F401
     PATCH_DEGENERATE,
     PATCH_DTYPE,
     DensePointsError,
+    FUSED_DTYPE,
     LIB_PATH,
 )
 from .pmvs import (  # noqa: F401
@@ -25,6 +26,7 @@ from .pmvs import (  # noqa: F401
     FastOptions,
     Options,
     View,
+    check_fuse_args,
     empty_patches,
     mask_from_list,
     ncc_score,

@@ -153,6 +153,45 @@ class DpRenderStats(ctypes.Structure):
 RENDER_ALL_FACING = 1
 
 
+class DpFuseOptions(ctypes.Structure):
+    _fields_ = [
+        ("depth_tol", ctypes.c_float),
+        ("min_views", ctypes.c_int32),
+        ("min_normal_cos", ctypes.c_float),
+        ("flags", ctypes.c_int32),
+    ]
+
+
+class DpFuseStats(ctypes.Structure):
+    _fields_ = [
+        ("depth_pixels", ctypes.c_int64),
+        ("matched_pairs", ctypes.c_int64),
+        ("consistent_pairs", ctypes.c_int64),
+        ("fusable", ctypes.c_int64),
+        ("emitted", ctypes.c_int64),
+        ("fuse_ms", ctypes.c_double),
+    ]
+
+
+FUSE_NO_SUPPRESS = 1
+
+# dp_fused_point (include/densepoints.h) -- 40 bytes; pos, rgb and normal are
+# named as in PATCH_DTYPE, so write_ply takes either
+FUSED_DTYPE = np.dtype(
+    [
+        ("pos", "<f4", 3),
+        ("normal", "<f4", 3),
+        ("rgb", "u1", 3),
+        ("n_views", "u1"),
+        ("view", "<i4"),
+        ("x", "<i4"),
+        ("y", "<i4"),
+    ],
+    align=True,
+)
+assert FUSED_DTYPE.itemsize == 40
+
+
 class DpSynthConfig(ctypes.Structure):
     _fields_ = [
         ("n_views", ctypes.c_int32),
@@ -276,6 +315,9 @@ SIGNATURES = [
     ("dp_default_render_options", None, [_P]),
     ("dp_render_maps", _I, [_P, _P, ctypes.c_int64, _P, _P, _I, _P, _P, _P, _P, _P, _P]),
     ("dp_render_maps_device", _I, [_P, _P, ctypes.c_int64, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P]),
+    ("dp_default_fuse_options", None, [_P]),
+    ("dp_fuse_maps", _I, [_P, _P, _I, _P, _P, _P, _P, _P, _P]),
+    ("dp_fuse_maps_device", _I, [_P, _P, _I, _P, _P, _P, _P, ctypes.c_int64, _P, _P, _P]),
     ("dp_last_kernel_ms", _I, [_P, _P]),
     ("dp_default_matcher_options", None, [_P]),
     ("dp_orb_pattern", _I, [_P]),

@@ -266,6 +266,19 @@ extern "C" int dp_ctx_destroy(dp_ctx *c)
         hipEventDestroy(c->r_e0);
     if (c->r_e1)
         hipEventDestroy(c->r_e1);
+    c->u_flag.release();
+    c->u_bcount.release();
+    c->u_boff.release();
+    c->u_count.release();
+    c->u_tab.release();
+    c->u_in.release();
+    c->u_pts.release();
+    c->u_res.release();
+    c->u_hcount.release();
+    if (c->u_e0)
+        hipEventDestroy(c->u_e0);
+    if (c->u_e1)
+        hipEventDestroy(c->u_e1);
     c->pat.release();
     c->store.release();
     c->cand.release();

@@ -2,7 +2,8 @@
 // refine launch, shared by the C-ABI translation units (dp_capi.hip: contexts,
 // views, pyramid, filter, batch refine/expand; dp_densify.hip: the densify
 // engine; dp_fast.hip: performance mode; dp_synth.hip: synthetic scenes and
-// probes; dp_seeds_capi.hip: seed generation; dp_render.hip: maps).
+// probes; dp_seeds_capi.hip: seed generation; dp_render.hip: maps; dp_fuse.hip:
+// their fusion).
 #pragma once
 
 #include "dp_internal.h"
@@ -145,6 +146,18 @@ struct dp_ctx {
     DevBuf<int32_t> r_slot_of;
     DevBuf<unsigned char> r_out;
     hipEvent_t r_e0 = nullptr, r_e1 = nullptr;
+    // dp_fuse_maps: the per-pixel masks live in r_z (8 B per pixel of the
+    // requested views, as the z-buffer; the calls never overlap); emitted flags,
+    // per-block counts and their scan, striped counters, the view table, the
+    // host form's staged planes and points, the statistics read, timing events
+    DevBuf<uint8_t> u_flag;
+    DevBuf<unsigned long long> u_bcount, u_boff, u_count;
+    DevBuf<dpk::FuseView> u_tab;
+    DevBuf<unsigned char> u_in;
+    DevBuf<dp_fused_point> u_pts;
+    HostBuf<dp_fused_point> u_res;
+    HostBuf<unsigned long long> u_hcount;
+    hipEvent_t u_e0 = nullptr, u_e1 = nullptr;
     HostBuf<dp_patch> result; // dp_densify / dp_densify_result output (pinned)
     // dp_densify_iterate: per iteration {evaluations, filter survivors} on the
     // device (read once, at the end) and the filters' timing events

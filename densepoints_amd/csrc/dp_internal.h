@@ -291,6 +291,36 @@ hipError_t launch_render_pairs(const RenderArgs &a, int64_t i0, int64_t i1, int 
 hipError_t launch_render_raster(const RenderArgs &a, int chunk, hipStream_t s);
 hipError_t launch_render_resolve(const RenderArgs &a, int max_pixels, hipStream_t s);
 
+// depth-map fusion (dp_fuse.hip; spec in include/densepoints.h, dp_fuse_maps)
+struct FuseView { // one requested view; indexed wave-uniformly (scalar loads)
+    double P[12];
+    double A[9], det;     // adjugate and determinant of the left 3x3 of P
+    const float *depth;   // W x H
+    const float *normal;  // W x H x 3, or null
+    const uint32_t *img;  // BGRA8 plane of the current level
+    int64_t poff;         // first pixel of the view in the mask and flag buffers
+    int32_t W, H, pitch, view;
+};
+constexpr int kFuseBlock = 256;    // pixels per block, consecutive in one plane
+constexpr int kFuseCounters = 4;   // depth pixels, matched pairs, consistent pairs, fusable
+constexpr int kFuseStripes = 64;   // each counter kept kFuseStripes times (summed by the host)
+struct FuseArgs {
+    const FuseView *tab;
+    int32_t K, min_views, no_suppress, has_normals;
+    double tol, cos2;               // (double)depth_tol, cs*cs
+    unsigned long long *mask;       // per pixel of the requested views
+    uint8_t *flag;                  // per pixel: emitted
+    unsigned long long *bcount;     // per block: emitted pixels; [blocks] = 0
+    const unsigned long long *boff; // their exclusive scan; [blocks] = the total
+    unsigned long long *count;      // kFuseStripes x kFuseCounters
+    dp_fused_point *out;
+    int64_t cap;
+};
+// gx blocks per view (the largest plane's), K views: block (x, k) is scan entry k * gx + x
+hipError_t launch_fuse_mask(const FuseArgs &a, unsigned gx, hipStream_t s);
+hipError_t launch_fuse_count(const FuseArgs &a, unsigned gx, hipStream_t s);
+hipError_t launch_fuse_emit(const FuseArgs &a, unsigned gx, hipStream_t s);
+
 hipError_t launch_refine(const RefineArgs &a, hipStream_t s);
 hipError_t launch_pyr_down(const PyrPlane *d_src, const PyrPlane *d_dst, int V, int max_dw, int max_dh,
                            hipStream_t s);

@@ -23,7 +23,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import _native as N
-from ._native import PATCH_DTYPE, check, lib, ptr
+from ._native import FUSED_DTYPE, PATCH_DTYPE, check, lib, ptr
 
 __all__ = [
     "Options",
@@ -35,6 +35,7 @@ __all__ = [
     "read_scene_json",
     "write_ply",
     "write_pfm",
+    "check_fuse_args",
     "read_pfm",
     "empty_patches",
     "visible_list",
@@ -622,6 +623,83 @@ class Engine:
                                               ctypes.c_void_p(stream) if stream else None))
         return {name: getattr(st, name) for name, _ in N.DpRenderStats._fields_} if stats else None
 
+    # ---- depth-map fusion (include/densepoints.h dp_fuse_maps) ----
+    def fuse_maps(self, depth, normal=None, views=None, depth_tol: float = 0.01, min_views: int = 2,
+                  min_normal_cos: float = 0.5, suppress: bool = True):
+        """dp_fuse_maps: the depth (and normal) planes of `views` (None = all),
+        as render_maps returns them, fused into one cross-view-consistent cloud.
+        Returns (points as a FUSED_DTYPE array in (view rank, y, x) order, stats)."""
+        fo, vid = check_fuse_args(self.num_views(), views, depth_tol, min_views, min_normal_cos, suppress)
+        sizes = self.view_sizes(vid)
+
+        def planes(arrs, name, tail):
+            if len(arrs) != len(vid):
+                raise ValueError("fuse_maps: one %s plane per view" % name)
+            out = [np.ascontiguousarray(a, dtype=np.float32) for a in arrs]
+            for a, (w, h) in zip(out, sizes):
+                if a.shape != (h, w) + tail:
+                    raise ValueError("fuse_maps: a %s plane of shape %s, expected %s" % (name, a.shape, (h, w) + tail))
+            return out, (ctypes.c_void_p * len(vid))(*[a.ctypes.data for a in out])
+
+        depth, dtab = planes(depth, "depth", ())
+        normal, ntab = planes(normal, "normal", (3,)) if normal is not None else (None, None)
+        out, n, st = ctypes.c_void_p(), ctypes.c_int64(), N.DpFuseStats()
+        self._check(lib.dp_fuse_maps(self._ctx, ptr(vid), len(vid), ctypes.byref(fo), dtab, ntab, ctypes.byref(out),
+                                     ctypes.byref(n), ctypes.byref(st)))
+        pts = np.zeros(n.value, dtype=FUSED_DTYPE)
+        if n.value:
+            ctypes.memmove(pts.ctypes.data, out.value, pts.nbytes)
+        return pts, {name: getattr(st, name) for name, _ in N.DpFuseStats._fields_}
+
+    def fuse_maps_device(self, views, d_depth, d_normal, d_points: int | None, cap: int, depth_tol: float = 0.01,
+                         min_views: int = 2, min_normal_cos: float = 0.5, suppress: bool = True,
+                         stream: int | None = None):
+        """dp_fuse_maps_device: device planes (lists of device addresses, one per
+        entry of `views`; d_normal None = no normals) into at most `cap`
+        dp_fused_point records at d_points.  Queued on `stream`; one wait.
+        Returns (the full emitted count -- above cap: an overflow --, stats)."""
+        fo, vid = check_fuse_args(self.num_views(), views, depth_tol, min_views, min_normal_cos, suppress)
+        if int(cap) != cap or cap < 0 or (cap > 0 and not d_points):
+            raise ValueError("fuse_maps_device: cap must be >= 0, with d_points given when > 0")
+
+        def table(addrs):
+            if addrs is None:
+                return None
+            if len(addrs) != len(vid) or not all(addrs):
+                raise ValueError("fuse_maps_device: one plane address per view")
+            return (ctypes.c_void_p * len(vid))(*[int(a) for a in addrs])
+
+        if d_depth is None:
+            raise ValueError("fuse_maps_device: depth planes must be given")
+        n, st = ctypes.c_int64(), N.DpFuseStats()
+        self._check(lib.dp_fuse_maps_device(self._ctx, ptr(vid), len(vid), ctypes.byref(fo), table(d_depth),
+                                            table(d_normal), ctypes.c_void_p(d_points) if d_points else None,
+                                            int(cap), ctypes.byref(n), ctypes.byref(st),
+                                            ctypes.c_void_p(stream) if stream else None))
+        return int(n.value), {name: getattr(st, name) for name, _ in N.DpFuseStats._fields_}
+
+
+def check_fuse_args(V: int, views, depth_tol: float, min_views: int, min_normal_cos: float, suppress: bool):
+    """Argument validation of Engine.fuse_maps[_device] (the limits of
+    dp_fuse_maps, raised as ValueError before any device call); returns
+    (dp_fuse_options, view ids as int32)."""
+    def number(x):
+        return isinstance(x, (int, float, np.integer, np.floating)) and not isinstance(x, bool)
+
+    if not (number(depth_tol) and np.isfinite(depth_tol) and depth_tol >= 0):
+        raise ValueError("fuse_maps: depth_tol must be finite and >= 0")
+    if not (number(min_views) and int(min_views) == min_views and 0 <= int(min_views) <= 63):
+        raise ValueError("fuse_maps: min_views must be in 0..63")
+    if not (number(min_normal_cos) and 0 <= min_normal_cos <= 1):
+        raise ValueError("fuse_maps: min_normal_cos must be in 0..1")
+    vid = np.arange(V, dtype=np.int64) if views is None else np.asarray(list(views), dtype=np.int64)
+    if vid.ndim != 1 or not 1 <= len(vid) <= 64:
+        raise ValueError("fuse_maps: 1..64 views")
+    if (vid < 0).any() or (vid >= V).any() or len(set(vid.tolist())) != len(vid):
+        raise ValueError("fuse_maps: view ids must be unique and < %d" % V)
+    fo = N.DpFuseOptions(float(depth_tol), int(min_views), float(min_normal_cos), 0 if suppress else N.FUSE_NO_SUPPRESS)
+    return fo, np.ascontiguousarray(vid, dtype=np.int32)
+
 
 def check_render_args(n: int, V: int, views, keep, splat_scale: float, max_radius_px: int, all_facing: bool):
     """Argument validation of Engine.render_maps[_device] (the limits of
@@ -769,6 +847,42 @@ class PMVS:
         with Engine(self.options, self.device) as eng:
             eng.set_views(self.views)
             return eng.render_maps(self.patches, **kw)
+
+    def fused_cloud(self, views=None, splat_scale: float = 1.0, max_radius_px: int = 32, all_facing: bool = False,
+                    normals: bool = True, **fuse_kw) -> np.ndarray:
+        """The last run()'s result as a dense fused cloud (a FUSED_DTYPE array):
+        its depth and normal maps rendered on the device (Engine.render_maps_device)
+        and fused there (Engine.fuse_maps_device, whose keyword arguments pass
+        through) -- the planes never visit the host.  The statistics of both
+        calls are left in self.stats["render"] and self.stats["fused"]."""
+        if not self._ran:
+            raise ValueError("fused_cloud: call run() first")
+        import torch
+
+        with Engine(self.options, self.device) as eng:
+            eng.set_views(self.views)
+            _, vid = check_fuse_args(eng.num_views(), views, fuse_kw.get("depth_tol", 0.01),
+                                     fuse_kw.get("min_views", 2), fuse_kw.get("min_normal_cos", 0.5),
+                                     fuse_kw.get("suppress", True))
+            dev = torch.device("cuda", self.device)
+            pat = torch.from_numpy(np.ascontiguousarray(self.patches).view(np.uint8).reshape(-1).copy()).to(dev)
+            depth = [torch.empty((h, w), dtype=torch.float32, device=dev) for w, h in eng.view_sizes(vid)]
+            normal = [torch.empty((h, w, 3), dtype=torch.float32, device=dev) for w, h in eng.view_sizes(vid)]
+            torch.cuda.synchronize(dev)
+            rst = eng.render_maps_device(pat.data_ptr() if len(self.patches) else 0, len(self.patches), None, vid,
+                                         [t.data_ptr() for t in depth], None,
+                                         [t.data_ptr() for t in normal] if normals else None,
+                                         splat_scale=splat_scale, max_radius_px=max_radius_px, all_facing=all_facing)
+            # an empty pixel is never emitted: the covered pixels bound the cloud
+            cap = int(rst["covered_pixels"])
+            pts = torch.empty((max(cap, 1), FUSED_DTYPE.itemsize), dtype=torch.uint8, device=dev)
+            torch.cuda.synchronize(dev)
+            n, fst = eng.fuse_maps_device(vid, [t.data_ptr() for t in depth],
+                                          [t.data_ptr() for t in normal] if normals else None, pts.data_ptr(), cap,
+                                          **fuse_kw)
+            out = pts[:n].cpu().numpy().reshape(-1).view(FUSED_DTYPE).copy()
+        self.stats["render"], self.stats["fused"] = rst, fst
+        return out
 
 
 def ncc_score(a: np.ndarray, b: np.ndarray, denom_min: float = 0.1) -> float:

@@ -484,6 +484,100 @@ int dp_render_maps_device(dp_ctx *ctx, const dp_patch *d_patches, int64_t n, con
                           int32_t *const *d_index, float *const *d_normal, float *const *d_score,
                           dp_render_stats *stats, void *stream);
 
+/* ---- depth-map fusion: per-view depth maps into one cross-view-consistent,
+ * oriented, coloured point cloud ------------------------------------------------
+ * No reference counterpart (the reference's only product is the point list).
+ * Every depth pixel of the requested views is back-projected, observed in every
+ * other requested view's depth map, kept when enough of them agree, and written
+ * once as the mean of the agreeing back-projections.  All arithmetic is fp64,
+ * one IEEE rounding per operation, in exactly the order written (the build has
+ * -ffp-contract=off); dot, row_r and project are dp_render_maps's.
+ *
+ * Inputs: the requested views views[0..K-1] (unique ids < V, 1 <= K <= 64) at
+ * the CURRENT level (dp_set_level: level-L P, W, H and BGRA8 planes); per
+ * requested view, in the order of `views`, an f32 depth plane W x H, row-major
+ * (0 = empty; the value is the projective depth row_2(P_v, X), which is what
+ * dp_render_maps writes) and, optionally, a 3 x f32 normal plane (all of them or
+ * none: the array pointer NULL = none); the options below.  A plane value z is a
+ * depth iff z > 0 and z is finite (0, negatives, NaN and +inf are not).
+ *
+ * Per requested view v, once on the host in fp64 (the view table): m = the left
+ * 3x3 of P_v, m[0..8] = P[0,1,2,4,5,6,8,9,10]; its adjugate A0..A8 by the
+ * cofactor formulas dp_render_maps gives for h (with h = m) and det = (m0*A0 +
+ * m1*A3) + m2*A6.  A requested view whose det is 0 or not finite: DP_E_ARG.
+ *
+ * backproject(v, x, y, z): zd = (double)z, b0 = zd*x - P[3], b1 = zd*y - P[7],
+ *   b2 = zd - P[11], X_j = ((A[3j]*b0 + A[3j+1]*b1) + A[3j+2]*b2) / det.
+ *
+ * observe(s, X), of a pixel of view r with normal nr:
+ *   1. d = row_2(P_s, X); require d > 0;
+ *   2. u = row_0 / d, v = row_1 / d; require |u| < 2e9 and |v| < 2e9 (NaN fails);
+ *   3. xi = rint(u), yi = rint(v), round-half-even; require 0 <= xi < W_s and
+ *      0 <= yi < H_s;
+ *   4. zs = depth_s[yi][xi]; require zs > 0;              -- a MATCHED pair
+ *   5. require fabs((double)zs - d) <= (double)depth_tol * d;
+ *   6. with normal planes only: ns = normal_s[yi][xi], nr, ns widened to fp64,
+ *      c = dot(nr, ns); require c >= 0 and c*c >= (cs*cs) * (dot(nr, nr) *
+ *      dot(ns, ns)), cs = (double)min_normal_cos.        -- a CONSISTENT pair
+ *
+ * Pixel (k, x, y), r = views[k], z = depth_r[y][x], takes part iff z is a depth.
+ * X = backproject(r, x, y, z); bit k' of its 64-bit mask is set iff k' != k and
+ * observe(views[k'], X) passes; it is FUSABLE iff popcount(mask) >= min_views.
+ * A fusable pixel is EMITTED iff DP_FUSE_NO_SUPPRESS is set, or no set bit
+ * k' < k of its mask has a matched pixel (k', xi, yi) that is itself fusable
+ * (one surface point comes out once, from the first requested view that holds
+ * it, instead of once per view).  This is a function of the masks alone, so it
+ * does not depend on the launch geometry.
+ *
+ * Emitted point (dp_fused_point): acc = X; for each set bit k' in ascending
+ * order acc_j += backproject(views[k'], xi, yi, zs)_j; m = 1 + popcount(mask);
+ * pos_j = (float)(acc_j / (double)m).  With normal planes: sum = nr, then sum_j
+ * += ns_j in the same order; q = dot(sum, sum); normal_j = q > 0 ? (float)(sum_j
+ * / sqrt(q)) : 0; without them the normal is zeros.  rgb = the R, G, B of view
+ * r's BGRA8 texel at (x, y) of the current level; n_views = m; view = r.
+ * Order of the output: ascending (k, y, x).
+ *
+ * Statistics, all counted on the device: depth_pixels (pixels taking part),
+ * matched_pairs (observations that pass steps 1-4), consistent_pairs (the sum of
+ * popcount(mask)), fusable, emitted; fuse_ms = device time of the call's kernels.
+ *
+ * Host form: host planes; *out is context-owned, valid until the next
+ * dp_fuse_maps or destroy.  Device form: device planes; writes the first
+ * min(cap, emitted) points to d_points (may be NULL with cap 0) and nothing
+ * beyond them; *n_out = the full emitted count, so a caller sees an overflow;
+ * everything is queued on `stream` (NULL = the context's) and the call waits
+ * once, for n_out and the statistics.  fo NULL = the defaults; stats may be NULL.
+ * Errors (DP_E_ARG): n_views outside 1..min(V, 64), a view id repeated or >= V,
+ * depth_tol negative or not finite, min_views outside 0..63, min_normal_cos
+ * outside 0..1, depth NULL or a NULL depth entry, a NULL normal entry, cap < 0,
+ * cap > 0 without d_points, out or n_out NULL; no views set: DP_E_STATE. */
+#define DP_FUSE_NO_SUPPRESS 1
+typedef struct dp_fuse_options {
+    float depth_tol;       /* 0.01 relative depth agreement                        */
+    int32_t min_views;     /* 2    consistent views other than the pixel's own     */
+    float min_normal_cos;  /* 0.5  least cosine between agreeing normals           */
+    int32_t flags;         /* DP_FUSE_* bits (default 0)                           */
+} dp_fuse_options;
+typedef struct dp_fused_point {
+    float pos[3];
+    float normal[3];
+    uint8_t rgb[3];
+    uint8_t n_views;       /* 1 + the consistent views                             */
+    int32_t view, x, y;    /* the emitting pixel                                   */
+} dp_fused_point;
+typedef struct dp_fuse_stats {
+    int64_t depth_pixels, matched_pairs, consistent_pairs, fusable, emitted;
+    double fuse_ms;
+} dp_fuse_stats;
+
+void dp_default_fuse_options(dp_fuse_options *fo);
+int dp_fuse_maps(dp_ctx *ctx, const int32_t *views, int n_views, const dp_fuse_options *fo,
+                 const float *const *depth, const float *const *normal /* NULL = none */,
+                 const dp_fused_point **out, int64_t *n_out, dp_fuse_stats *stats);
+int dp_fuse_maps_device(dp_ctx *ctx, const int32_t *views, int n_views, const dp_fuse_options *fo,
+                        const float *const *d_depth, const float *const *d_normal, dp_fused_point *d_points,
+                        int64_t cap, int64_t *n_out, dp_fuse_stats *stats, void *stream);
+
 /* ---- seed generation: Features::Matcher::GenerateSeeds ---
  * modules/features/matcher.cpp:18-43 with the default MatcherOptions
  * (matcher.h:21-32: ORB detector, kNN matcher, no direct epipolar matching,

@@ -12,6 +12,7 @@
 //           [--features N] [--fast-threshold T] [--epipolar-matching] [--matcher knn|flann]
 //           [--detector orb|akaze] [--akaze-threshold T]
 //           [--depth-maps DIR [--splat-scale S] [--depth-normals]]
+//           [--fuse FILE.ply [--fuse-min-views K] [--fuse-depth-tol T]]
 //   densify --synthetic V,W,H,KIND --write-scene DIR   (deterministic test scene
 //           written as scene.json + PPM images + seeds.xyz; no GPU needed)
 #include "scene_io.h"
@@ -62,6 +63,11 @@ void usage()
                  "                             DIR/depth_%%04d.pfm, and normal_%%04d.pfm, of every view --\n"
                  "                             the written patches as discs of radius S x rho, nearest\n"
                  "                             per pixel: dp_render_maps)\n"
+                 "               [--fuse FILE.ply [--fuse-min-views K] [--fuse-depth-tol T]]  (after those:\n"
+                 "                             the depth and normal maps of every view, rendered and fused\n"
+                 "                             on the device into one cross-view-consistent cloud --\n"
+                 "                             dp_fuse_maps; K = 0..63 agreeing other views, default 2;\n"
+                 "                             T = relative depth tolerance, default 0.01)\n"
                  "       densify --synthetic V,W,H,KIND --write-scene DIR\n");
 }
 
@@ -540,7 +546,9 @@ void write_pfm(const std::string &path, const float *px, int w, int h, int chann
 
 int main(int argc, char **argv)
 {
-    std::string input, settings, output = "points.ply", seeds_path, synth, scene_dir, depth_dir;
+    std::string input, settings, output = "points.ply", seeds_path, synth, scene_dir, depth_dir, fuse_path;
+    dp_fuse_options fuse_opt;
+    dp_default_fuse_options(&fuse_opt);
     double splat_scale = 1.0;
     bool depth_normals = false;
     int device = 0, gpus = 1;
@@ -634,6 +642,27 @@ int main(int argc, char **argv)
             }
         }
         else if (a == "--depth-normals") depth_normals = true;
+        else if (a == "--fuse") fuse_path = next();
+        else if (a == "--fuse-min-views") {
+            char *end = nullptr;
+            const std::string v = next();
+            const long k = std::strtol(v.c_str(), &end, 10);
+            if (v.empty() || *end || k < 0 || k > 63) {
+                std::fprintf(stderr, "densify: --fuse-min-views expects 0..63\n");
+                return 2;
+            }
+            fuse_opt.min_views = (int32_t)k;
+        }
+        else if (a == "--fuse-depth-tol") {
+            char *end = nullptr;
+            const std::string v = next();
+            const double t = std::strtod(v.c_str(), &end);
+            if (v.empty() || *end || !(t >= 0.0) || !(t <= 3.0e38)) {
+                std::fprintf(stderr, "densify: --fuse-depth-tol expects a finite number >= 0\n");
+                return 2;
+            }
+            fuse_opt.depth_tol = (float)t;
+        }
         else if (a == "-h" || a == "--help") {
             usage();
             return 0;
@@ -852,6 +881,88 @@ int main(int argc, char **argv)
                           ", \"depth_maps\": {\"views\": %zu, \"covered_pixels\": %lld, \"render_ms\": %.3f}",
                           imgs.size(), (long long)covered, render_ms);
         }
+        // --fuse: depth and normal maps of every view rendered into device planes
+        // (dp_render_maps_device, honouring --splat-scale) and fused there
+        // (dp_fuse_maps_device); only the points come back.  An empty pixel is
+        // never emitted, so the render's covered pixels size the point buffer;
+        // should the fusion report more, it is reallocated once and re-run.
+        std::string fused_json;
+        if (!fuse_path.empty()) {
+            std::vector<dp_patch> kept;
+            kept.reserve(cloud.size());
+            for (int64_t i = 0; i < n_out; ++i)
+                if (keep[i])
+                    kept.push_back(out[i]);
+            const int V = (int)imgs.size();
+            struct DevMem {
+                std::vector<void *> p;
+                void *get(size_t bytes)
+                {
+                    void *q = nullptr;
+                    if (hipMalloc(&q, bytes ? bytes : 1) != hipSuccess)
+                        throw std::runtime_error("--fuse: out of device memory");
+                    p.push_back(q);
+                    return q;
+                }
+                ~DevMem()
+                {
+                    for (void *q : p)
+                        (void)hipFree(q);
+                }
+            } mem;
+            check(hipSetDevice(device) == hipSuccess ? DP_OK : DP_E_HIP, "hipSetDevice");
+            std::vector<int32_t> vid((size_t)V);
+            std::vector<float *> dd((size_t)V), dn((size_t)V);
+            for (int32_t v = 0; v < V; ++v) {
+                int32_t w = 0, h = 0;
+                check(dp_level_info(ctx, level, v, &w, &h, nullptr), "dp_level_info");
+                vid[(size_t)v] = v;
+                dd[(size_t)v] = (float *)mem.get((size_t)w * h * 4);
+                dn[(size_t)v] = (float *)mem.get((size_t)w * h * 12);
+            }
+            dp_patch *d_pat = (dp_patch *)mem.get(kept.size() * sizeof(dp_patch));
+            if (!kept.empty() &&
+                hipMemcpy(d_pat, kept.data(), kept.size() * sizeof(dp_patch), hipMemcpyHostToDevice) != hipSuccess)
+                throw std::runtime_error("--fuse: copy of the patches failed");
+            dp_render_options ro;
+            dp_default_render_options(&ro);
+            ro.splat_scale = (float)splat_scale;
+            dp_render_stats rs;
+            check(dp_render_maps_device(ctx, kept.empty() ? nullptr : d_pat, (int64_t)kept.size(), nullptr, vid.data(), V,
+                                        &ro, dd.data(), nullptr, dn.data(), nullptr, &rs, nullptr),
+                  "dp_render_maps_device");
+            int64_t cap = rs.covered_pixels, n_fused = 0;
+            dp_fuse_stats fs;
+            dp_fused_point *d_pts = nullptr;
+            for (int attempt = 0; attempt < 2; ++attempt) {
+                d_pts = (dp_fused_point *)mem.get((size_t)cap * sizeof(dp_fused_point));
+                check(dp_fuse_maps_device(ctx, vid.data(), V, &fuse_opt, dd.data(), dn.data(), d_pts, cap, &n_fused, &fs,
+                                          nullptr),
+                      "dp_fuse_maps_device");
+                if (n_fused <= cap)
+                    break;
+                cap = n_fused;
+            }
+            if (n_fused > cap)
+                throw std::runtime_error("--fuse: the point count changed between two runs");
+            std::vector<dp_fused_point> pts((size_t)n_fused);
+            if (n_fused > 0 &&
+                hipMemcpy(pts.data(), d_pts, pts.size() * sizeof(dp_fused_point), hipMemcpyDeviceToHost) != hipSuccess)
+                throw std::runtime_error("--fuse: copy of the points failed");
+            std::vector<dpio::CloudPoint> fused(pts.size());
+            for (size_t i = 0; i < pts.size(); ++i)
+                for (int k = 0; k < 3; ++k) {
+                    fused[i].pos[k] = pts[i].pos[k];
+                    fused[i].normal[k] = pts[i].normal[k];
+                    fused[i].rgb[k] = pts[i].rgb[k];
+                }
+            dpio::write_ply(fuse_path, fused);
+            char buf[240];
+            std::snprintf(buf, sizeof buf,
+                          ", \"fused\": {\"points\": %lld, \"fusable\": %lld, \"depth_pixels\": %lld, \"fuse_ms\": %.3f}",
+                          (long long)n_fused, (long long)fs.fusable, (long long)fs.depth_pixels, fs.fuse_ms);
+            fused_json = buf;
+        }
         dp_ctx_destroy(ctx);
         // the per-round counts (one round: the densify and the optional filter)
         if (iters.empty()) {
@@ -887,12 +998,12 @@ int main(int argc, char **argv)
                     "\"keypoints\": %lld, \"matches\": %lld, \"seed_ms\": %.3f, \"seed_patches\": %lld, "
                     "\"pops\": %lld, \"candidates\": %lld, \"evals\": %lld, \"generations\": %d, \"refine_ms\": %.3f, "
                     "\"densify_ms\": %.3f, \"wall_ms\": %.3f, \"gpus\": %d, \"mode\": \"%s\", \"exchanged\": %lld, "
-                    "\"iterations\": %s%s}\n",
+                    "\"iterations\": %s%s%s}\n",
                     output.c_str(), (long long)st.patches, cloud.size(), use.size() / 3,
                     seeds_path.empty() ? "true" : "false", (long long)sst.keypoints, (long long)sst.matches,
                     sst.total_ms, (long long)st.seed_patches, (long long)st.pops, (long long)st.candidates,
                     (long long)st.evals, st.generations, st.refine_ms, st.total_ms, wall, gpus,
-                    fast ? "fast" : "parity", (long long)exchanged, iters_json.c_str(), depth_json);
+                    fast ? "fast" : "parity", (long long)exchanged, iters_json.c_str(), depth_json, fused_json.c_str());
         return 0;
     } catch (const std::exception &e) {
         std::fprintf(stderr, "densify: %s\n", e.what());
