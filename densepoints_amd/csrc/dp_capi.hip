@@ -175,10 +175,9 @@ extern "C" int dp_ctx_create(const dp_options *opt, int device, dp_ctx **out)
         return rc;
     }
     if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess ||
-        hipMalloc(&c->d_work, dpk::kWorkCounters * sizeof(uint32_t)) != hipSuccess ||
-        hipMalloc(&c->d_evals, sizeof(unsigned long long)) != hipSuccess ||
-        hipEventCreate(&c->e0) != hipSuccess || hipEventCreate(&c->e1) != hipSuccess ||
-        hipEventCreateWithFlags(&c->ej, hipEventDisableTiming) != hipSuccess || c->mbox.reserve(8) != hipSuccess ||
+        c->d_work.reserve(dpk::kWorkCounters) != hipSuccess || c->d_evals.reserve(1) != hipSuccess ||
+        c->e0.create() != hipSuccess || c->e1.create() != hipSuccess ||
+        c->ej.create(hipEventDisableTiming) != hipSuccess || c->mbox.reserve(8) != hipSuccess ||
         hipMemset(c->mbox.p, 0, 8 * sizeof(unsigned long long)) != hipSuccess) {
         dp_ctx_destroy(c);
         return DP_E_HIP;
@@ -220,90 +219,11 @@ extern "C" int dp_ctx_destroy(dp_ctx *c)
     if (c->stream)
         hipStreamSynchronize(c->stream);
     free_views(c);
-    dp_seedgen_free(c->seeds);
-    c->seeds = nullptr;
-    c->grid.release();
-    c->cellmin.release();
-    c->pend.release();
-    c->granted.release();
-    c->tkeys.release();
-    c->okeys.release();
-    c->oiota.release();
-    c->porder.release();
-    c->olo.release();
-    c->gstate.release();
-    c->bsum.release();
-    c->wcand.release();
-    c->wok.release();
-    for (hipEvent_t e : c->gev)
-        if (e)
-            hipEventDestroy(e);
-    c->gev.clear();
-    c->mbox.release();
-    c->itw.release();
-    for (hipEvent_t e : c->fev)
-        if (e)
-            hipEventDestroy(e);
-    c->fev.clear();
-    c->result.release();
-    c->items.release();
-    c->seedp.release();
-    c->seedx.release();
-    c->sconv.release();
-    c->lpt.release();
-    c->front.release();
-    c->f_alive.release();
-    c->f_keep.release();
-    c->f_rho.release();
-    c->f_pat.release();
-    c->r_z.release();
-    c->r_count.release();
-    c->r_pairs.release();
-    c->r_slots.release();
-    c->r_slot_of.release();
-    c->r_out.release();
-    if (c->r_e0)
-        hipEventDestroy(c->r_e0);
-    if (c->r_e1)
-        hipEventDestroy(c->r_e1);
-    c->u_flag.release();
-    c->u_bcount.release();
-    c->u_boff.release();
-    c->u_count.release();
-    c->u_tab.release();
-    c->u_in.release();
-    c->u_pts.release();
-    c->u_res.release();
-    c->u_hcount.release();
-    if (c->u_e0)
-        hipEventDestroy(c->u_e0);
-    if (c->u_e1)
-        hipEventDestroy(c->u_e1);
-    c->pat.release();
-    c->store.release();
-    c->cand.release();
-    c->ok.release();
-    c->acc.release();
-    c->scan_tmp.release();
-    if (c->gray_pool)
-        hipFree(c->gray_pool);
-    if (c->d_fstats)
-        hipFree(c->d_fstats);
-    if (c->d_gray)
-        hipFree(c->d_gray);
-    if (c->d_work)
-        hipFree(c->d_work);
-    if (c->d_evals)
-        hipFree(c->d_evals);
-    if (c->e0)
-        hipEventDestroy(c->e0);
-    if (c->e1)
-        hipEventDestroy(c->e1);
-    if (c->ej)
-        hipEventDestroy(c->ej);
-    if (c->stream)
-        hipStreamDestroy(c->stream);
+    // the members free themselves (dp_buf.h); the stream outlives them all
+    const hipStream_t stream = c->stream;
     delete c;
+    if (stream)
+        hipStreamDestroy(stream);
     return DP_OK;
 }
 
@@ -715,8 +635,8 @@ dpk::RefineArgs refine_args(dp_ctx *c, const dpk::RefineJob &job)
     a.opt = c->opt;
     a.patches = job.patches;
     a.accept = job.accept;
-    a.work = c->d_work;
-    a.evals = c->d_evals;
+    a.work = c->d_work.p;
+    a.evals = c->d_evals.p;
     a.parents = job.parents;
     a.parent0 = job.parent0;
     a.max_pops = job.max_pops;

@@ -2,24 +2,30 @@
 // refine launch, shared by the C-ABI translation units (dp_capi.hip: contexts,
 // views, pyramid, filter, batch refine/expand; dp_densify.hip: the densify
 // engine; dp_fast.hip: performance mode; dp_synth.hip: synthetic scenes and
-// probes; dp_seeds_capi.hip: seed generation; dp_render.hip: maps; dp_fuse.hip:
-// their fusion).
+// probes; dp_seeds_capi.hip, dp_seeds_orb.hip, dp_seeds_akaze.hip: seed
+// generation (their own state is dp_seedgen.h); dp_render.hip: maps;
+// dp_fuse.hip: their fusion).  Every member that owns a device or pinned
+// allocation or an event has an owning type (dp_buf.h), so deleting the
+// context frees them; only the views and the pyramid (free_views) and the
+// stream, which must outlive them all, are released by hand.
 #pragma once
 
+#include "dp_buf.h"
 #include "dp_internal.h"
 
 #include <chrono>
+#include <memory>
 #include <string>
 #include <thread>
 #include <vector>
 
-struct dp_seedgen; // seed-generation state (dp_seeds.hip)
-void dp_seedgen_free(dp_seedgen *s);
+struct dp_seedgen; // seed-generation state (dp_seedgen.h)
+void dp_seedgen_free(dp_seedgen *s); // delete s (dp_seeds_capi.hip)
 
-namespace {
+namespace dpk {
 
 // host-side parallel loop (the product library carries no OpenMP runtime)
-template <typename F> void parallel_for(int64_t n, F f)
+template <typename F> inline void parallel_for(int64_t n, F f)
 {
     unsigned hw = std::thread::hardware_concurrency();
     int64_t nt = hw ? (int64_t)(hw > 32 ? 32 : hw) : 4;
@@ -40,66 +46,17 @@ template <typename F> void parallel_for(int64_t n, F f)
         x.join();
 }
 
-template <typename T> struct DevBuf {
-    T *p = nullptr;
-    size_t cap = 0;
-    hipError_t reserve(size_t n)
-    {
-        if (n <= cap)
-            return hipSuccess;
-        if (p)
-            hipFree(p);
-        p = nullptr;
-        cap = 0;
-        size_t want = n < 1024 ? 1024 : n + n / 4;
-        hipError_t e = hipMalloc(&p, want * sizeof(T));
-        if (e == hipSuccess)
-            cap = want;
-        return e;
-    }
-    void release()
-    {
-        if (p)
-            hipFree(p);
-        p = nullptr;
-        cap = 0;
-    }
-};
+} // namespace dpk
 
-// pinned host memory (grown, never shrunk): device->host copies of a result run
-// at DMA speed instead of through a staging buffer
-template <typename T> struct HostBuf {
-    T *p = nullptr;
-    size_t cap = 0, n = 0;
-    hipError_t resize(size_t k)
-    {
-        if (k > cap) {
-            if (p)
-                hipHostFree(p);
-            p = nullptr;
-            cap = 0;
-            const size_t want = k + k / 4;
-            hipError_t e = hipHostMalloc((void **)&p, want * sizeof(T), hipHostMallocDefault);
-            if (e != hipSuccess)
-                return e;
-            cap = want;
-        }
-        n = k;
-        return hipSuccess;
-    }
-    void clear() { n = 0; }
-    bool empty() const { return n == 0; }
-    T *data() { return p; }
-    void release()
-    {
-        if (p)
-            hipHostFree(p);
-        p = nullptr;
-        cap = n = 0;
-    }
-};
+using dpk::DevBuf;
+using dpk::DevMem;
+using dpk::Event;
+using dpk::HostBuf;
+using dpk::parallel_for;
 
-} // namespace
+struct SeedgenFree {
+    void operator()(dp_seedgen *s) const { dp_seedgen_free(s); }
+};
 
 struct dp_ctx {
     int device = 0;
@@ -117,9 +74,9 @@ struct dp_ctx {
     std::vector<uint32_t *> pyr_pool;
     int level = 0;
     bool narrow = false;            // all planes within 4 GiB of img_base (32-bit tap offsets)
-    uint32_t *d_work = nullptr;
-    unsigned long long *d_evals = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
+    DevBuf<uint32_t> d_work;
+    DevBuf<unsigned long long> d_evals;
+    Event e0, e1;
     bool timed = false;
     int64_t grid_cells = 0;
     DevBuf<uint32_t> grid;
@@ -145,7 +102,7 @@ struct dp_ctx {
     DevBuf<dpk::RenderSlot> r_slots;
     DevBuf<int32_t> r_slot_of;
     DevBuf<unsigned char> r_out;
-    hipEvent_t r_e0 = nullptr, r_e1 = nullptr;
+    Event r_e0, r_e1;
     // dp_fuse_maps: the per-pixel masks live in r_z (8 B per pixel of the
     // requested views, as the z-buffer; the calls never overlap); emitted flags,
     // per-block counts and their scan, striped counters, the view table, the
@@ -157,12 +114,12 @@ struct dp_ctx {
     DevBuf<dp_fused_point> u_pts;
     HostBuf<dp_fused_point> u_res;
     HostBuf<unsigned long long> u_hcount;
-    hipEvent_t u_e0 = nullptr, u_e1 = nullptr;
+    Event u_e0, u_e1;
     HostBuf<dp_patch> result; // dp_densify / dp_densify_result output (pinned)
     // dp_densify_iterate: per iteration {evaluations, filter survivors} on the
     // device (read once, at the end) and the filters' timing events
     DevBuf<unsigned long long> itw;
-    std::vector<hipEvent_t> fev;
+    std::vector<Event> fev;
     // generation-at-a-time densify (dp_densify_begin/refine/commit/result)
     DevBuf<dp_patch> seedp;  // seed patches of generation 0
     DevBuf<double> seedx;    // seed points (3 f64 each) on the device
@@ -186,10 +143,10 @@ struct dp_ctx {
     DevBuf<uint32_t> bsum;
     int g_slot = 0;
     uint32_t *g_lpt_scratch = nullptr;
-    std::vector<hipEvent_t> gev;
+    std::vector<Event> gev;
     DevBuf<dp_patch> wcand; // a rank's refined share (partitioned generations)
     DevBuf<uint8_t> wok;
-    hipEvent_t ej = nullptr;   // stream joins (no host wait)
+    Event ej;                  // stream joins (no host wait)
     bool g_time_pending = false; // a densify refine's events (e0, e1) not yet read
     int64_t g_np = 0;        // patches in the replicated store
     int64_t g_nseeds = 0;
@@ -197,14 +154,14 @@ struct dp_ctx {
     dp_densify_stats g_st{};
     std::chrono::steady_clock::time_point g_t0;
     // seed generation (Features::Matcher, dp_seeds.hip)
-    dp_seedgen *seeds = nullptr;
+    std::unique_ptr<dp_seedgen, SeedgenFree> seeds;
     // performance mode (dp_fast.hip): options and the fp16 gray planes of one level
     dp_fast_options fopt{4, 2, 6656, 8, 0.5f, 1.0f, 0, 0, 32}; // = dp_default_fast_options (tests/test_gpu_fast.py)
-    void *gray_pool = nullptr; // __half planes, pitch = width rounded up to 64
+    DevMem gray_pool;          // __half planes, pitch = width rounded up to 64
     size_t gray_cap = 0;       // elements
-    void *d_gray = nullptr;    // device GrayPlane table
+    DevMem d_gray;             // device GrayPlane table
     bool gray_ready = false;
-    unsigned long long *d_fstats = nullptr; // dp_fast_stats counters of the last launch
+    DevBuf<unsigned long long> d_fstats;    // dp_fast_stats counters of the last launch
     int gray_level = -1, gray_V = 0;
 };
 

@@ -79,9 +79,9 @@ static int ensure_gen_events(dp_ctx *c)
 {
     if (!c->gev.empty())
         return DP_OK;
-    c->gev.assign(2 * kGenBatch + 2, nullptr);
+    c->gev.resize(2 * kGenBatch + 2);
     for (auto &e : c->gev)
-        DP_HIP(c, hipEventCreate(&e));
+        DP_HIP(c, e.create());
     return DP_OK;
 }
 
@@ -117,7 +117,7 @@ static int organize_gen(dp_ctx *c, const dp_patch *cand, const uint8_t *okf, int
     b.cand_cap = cand_cap;
     b.max_pops = c->opt.max_pops;
     b.mbox = c->mbox.p;
-    b.work = c->d_work;
+    b.work = c->d_work.p;
     b.lpt_scratch = c->g_lpt_scratch;
     b.fused = fused;
     b.yield_items = yield_items;
@@ -249,12 +249,11 @@ static int run_generations(dp_ctx *c, int64_t max_gens, int64_t cap0, hipStream_
             c->g_lpt_scratch = c->lpt.p + cap;
         }
         // the first generation's counters (later ones are zeroed by the previous organizer)
-        DP_HIP(c, hipMemsetAsync(c->d_work, 0, dpk::kWorkCounters * sizeof(uint32_t), s));
+        DP_HIP(c, hipMemsetAsync(c->d_work.p, 0, dpk::kWorkCounters * sizeof(uint32_t), s));
         if (c->fopt.densify) {
             // dp_fast_last_stats: the batch's generations count as one launch
-            if (!c->d_fstats)
-                DP_HIP(c, hipMalloc(&c->d_fstats, 8 * sizeof(unsigned long long)));
-            DP_HIP(c, hipMemsetAsync(c->d_fstats, 0, 8 * sizeof(unsigned long long), s));
+            DP_HIP(c, c->d_fstats.reserve(8));
+            DP_HIP(c, hipMemsetAsync(c->d_fstats.p, 0, 8 * sizeof(unsigned long long), s));
         }
         if (c->g_lpt_scratch)
             DP_HIP(c, hipMemsetAsync(c->g_lpt_scratch, 0, 2 * dpk::kLptBuckets * sizeof(uint32_t), s));
@@ -338,7 +337,7 @@ static int begin_impl(dp_ctx *c, int n, hipStream_t s)
     if (rc != DP_OK || (rc = reserve_organizer(c, std::max<int64_t>(n, 1))) != DP_OK)
         return rc;
     DP_HIP(c, c->store.reserve((size_t)store_capacity(c, n)));
-    DP_HIP(c, hipMemsetAsync(c->d_evals, 0, sizeof(unsigned long long), s));
+    DP_HIP(c, hipMemsetAsync(c->d_evals.p, 0, sizeof(unsigned long long), s));
     DP_HIP(c, hipMemsetAsync(c->mbox.p, 0, 8 * sizeof(unsigned long long), s));
     return set_state(c, 0, seed_state(n), s);
 }
@@ -350,7 +349,7 @@ static int result_impl(dp_ctx *c, hipStream_t s, const dp_patch **out, int64_t *
     if (np)
         DP_HIP(c, hipMemcpyAsync(c->result.data(), c->store.p, sizeof(dp_patch) * np, hipMemcpyDeviceToHost, s));
     unsigned long long ev = 0;
-    DP_HIP(c, hipMemcpyAsync(&ev, c->d_evals, sizeof(ev), hipMemcpyDeviceToHost, s));
+    DP_HIP(c, hipMemcpyAsync(&ev, c->d_evals.p, sizeof(ev), hipMemcpyDeviceToHost, s));
     DP_HIP(c, hipStreamSynchronize(s));
     dp_densify_stats st = c->g_st;
     st.patches = np;
@@ -574,7 +573,7 @@ extern "C" int dp_densify_run_until(dp_ctx *c, dp_generation *gen, int32_t max_g
     // the evaluation counter before this call's refines (read after its waits)
     unsigned long long ev[2] = {0, 0};
     if (evals_out)
-        DP_HIP(c, hipMemcpyAsync(&ev[0], c->d_evals, sizeof(ev[0]), hipMemcpyDeviceToHost, s));
+        DP_HIP(c, hipMemcpyAsync(&ev[0], c->d_evals.p, sizeof(ev[0]), hipMemcpyDeviceToHost, s));
     dpk::GenDev g{};
     rc = run_generations(c, max_generations, std::max<int64_t>(4 * gen->items + 4096, (int64_t)c->cand.cap), s, &g,
                          yield_items);
@@ -582,7 +581,7 @@ extern "C" int dp_densify_run_until(dp_ctx *c, dp_generation *gen, int32_t max_g
         return rc;
     take_state(c, g, gen);
     if (evals_out) {
-        DP_HIP(c, hipMemcpyAsync(&ev[1], c->d_evals, sizeof(ev[1]), hipMemcpyDeviceToHost, s));
+        DP_HIP(c, hipMemcpyAsync(&ev[1], c->d_evals.p, sizeof(ev[1]), hipMemcpyDeviceToHost, s));
         DP_HIP(c, hipStreamSynchronize(s));
         *evals_out = (int64_t)(ev[1] - ev[0]);
     }
@@ -997,9 +996,9 @@ extern "C" int dp_densify_iterate(dp_ctx *c, const double *seeds, int n, int ite
     // evaluations, [2k + 1] the filter's survivors
     DP_HIP(c, c->itw.reserve(2 * 16));
     if (c->fev.empty()) {
-        c->fev.assign(2 * 16, nullptr);
+        c->fev.resize(2 * 16);
         for (auto &e : c->fev)
-            DP_HIP(c, hipEventCreate(&e));
+            DP_HIP(c, e.create());
     }
     std::vector<dp_iterate_stats> it((size_t)iterations, dp_iterate_stats{});
     dp_densify_stats tot{};
@@ -1043,7 +1042,7 @@ extern "C" int dp_densify_iterate(dp_ctx *c, const double *seeds, int n, int ite
             tot.seed_patches = st.reinserted;
         DP_HIP(c, c->f_keep.reserve((size_t)std::max<int64_t>(np, 1)));
         DP_HIP(c, c->bsum.reserve(dpk::kBfsBlocks));
-        DP_HIP(c, hipMemcpyAsync(c->itw.p + 2 * k, c->d_evals, sizeof(unsigned long long), hipMemcpyDeviceToDevice, s));
+        DP_HIP(c, hipMemcpyAsync(c->itw.p + 2 * k, c->d_evals.p, sizeof(unsigned long long), hipMemcpyDeviceToDevice, s));
         DP_HIP(c, hipEventRecord(c->fev[2 * k], s));
         rc = dp_filter_patches_device(c, c->store.p, np, &o, c->f_keep.p, s);
         if (rc != DP_OK)

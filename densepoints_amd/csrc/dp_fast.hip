@@ -1861,15 +1861,12 @@ int ensure_gray(dp_ctx *c)
         gp[v].pad = 0;
     }
     if (total > c->gray_cap) {
-        if (c->gray_pool)
-            hipFree(c->gray_pool);
-        c->gray_pool = nullptr;
         c->gray_cap = 0;
-        DP_HIP(c, hipMalloc(&c->gray_pool, total * sizeof(__half)));
+        DP_HIP(c, c->gray_pool.alloc(total * sizeof(__half)));
         c->gray_cap = total;
     }
     for (int v = 0; v < c->V; ++v)
-        gp[v].p = (const __half *)c->gray_pool + off[v];
+        gp[v].p = (const __half *)c->gray_pool.p + off[v];
     std::vector<dpk::PyrPlane> src(c->V);
     int mw = 0, mh = 0;
     for (int v = 0; v < c->V; ++v) {
@@ -1891,19 +1888,16 @@ int ensure_gray(dp_ctx *c)
         fc[v].W = h.W;
         fc[v].H = h.H;
     }
-    if (c->d_gray)
-        hipFree(c->d_gray);
-    c->d_gray = nullptr;
     dpk::PyrPlane *d_src = nullptr;
     // one table: GrayPlane[V], then FastCam[V] at fast_cam_offset(V)
-    DP_HIP(c, hipMalloc(&c->d_gray, fast_cam_offset(c->V) + sizeof(dpk::FastCam) * c->V));
+    DP_HIP(c, c->d_gray.alloc(fast_cam_offset(c->V) + sizeof(dpk::FastCam) * c->V));
     DP_HIP(c, hipMalloc(&d_src, sizeof(dpk::PyrPlane) * c->V));
-    DP_HIP(c, hipMemcpy(c->d_gray, gp.data(), sizeof(dpk::GrayPlane) * c->V, hipMemcpyHostToDevice));
-    DP_HIP(c, hipMemcpy((char *)c->d_gray + fast_cam_offset(c->V), fc.data(), sizeof(dpk::FastCam) * c->V,
+    DP_HIP(c, hipMemcpy(c->d_gray.p, gp.data(), sizeof(dpk::GrayPlane) * c->V, hipMemcpyHostToDevice));
+    DP_HIP(c, hipMemcpy((char *)c->d_gray.p + fast_cam_offset(c->V), fc.data(), sizeof(dpk::FastCam) * c->V,
                         hipMemcpyHostToDevice));
     DP_HIP(c, hipMemcpy(d_src, src.data(), sizeof(dpk::PyrPlane) * c->V, hipMemcpyHostToDevice));
     hipLaunchKernelGGL(dpk::gray_kernel, dim3((gray_pitch(mw) + 1023) / 1024, mh, c->V), dim3(256), 0, c->stream, d_src,
-                       (const dpk::GrayPlane *)c->d_gray);
+                       (const dpk::GrayPlane *)c->d_gray.p);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess)
         e = hipStreamSynchronize(c->stream);
@@ -1954,8 +1948,8 @@ int dp_fast_launch(dp_ctx *c, const dpk::RefineJob &job, hipStream_t s)
     const dpk::GenDev *gen = job.gen;
     dpk::FastArgs a{};
     a.views = c->d_views;
-    a.gray = (const dpk::GrayPlane *)c->d_gray;
-    a.cams = (const dpk::FastCam *)((const char *)c->d_gray + fast_cam_offset(c->V));
+    a.gray = (const dpk::GrayPlane *)c->d_gray.p;
+    a.cams = (const dpk::FastCam *)((const char *)c->d_gray.p + fast_cam_offset(c->V));
     a.V = c->V;
     a.cell = cell;
     a.mode = job.mode;
@@ -1966,8 +1960,8 @@ int dp_fast_launch(dp_ctx *c, const dpk::RefineJob &job, hipStream_t s)
     a.fo = c->fopt;
     a.patches = job.patches;
     a.accept = job.accept;
-    a.work = c->d_work;
-    a.evals = c->d_evals;
+    a.work = c->d_work.p;
+    a.evals = c->d_evals.p;
     a.parents = job.parents;
     a.parent0 = job.parent0;
     a.items = job.items;
@@ -1989,14 +1983,13 @@ int dp_fast_launch(dp_ctx *c, const dpk::RefineJob &job, hipStream_t s)
         a.dminf = (float)a.dmin;
         a.gs = (1.0f / c->fopt.fd_step) * 0x1p-24f;
     }
-    if (!c->d_fstats)
-        DP_HIP(c, hipMalloc(&c->d_fstats, 8 * sizeof(unsigned long long)));
-    a.stats = c->d_fstats;
+    DP_HIP(c, c->d_fstats.reserve(8));
+    a.stats = c->d_fstats.p;
     if (!gen) {
         // a device-resident generation's counters are zeroed by the previous
         // organizer (dp_bfs.hip) and its statistics by its batch (run_generations)
-        DP_HIP(c, hipMemsetAsync(c->d_fstats, 0, 8 * sizeof(unsigned long long), s));
-        DP_HIP(c, hipMemsetAsync(c->d_work, 0, sizeof(uint32_t), s));
+        DP_HIP(c, hipMemsetAsync(c->d_fstats.p, 0, 8 * sizeof(unsigned long long), s));
+        DP_HIP(c, hipMemsetAsync(c->d_work.p, 0, sizeof(uint32_t), s));
     }
     DP_HIP(c, hipEventRecord(c->e0, s));
     const int N = cell * cell;
@@ -2071,7 +2064,7 @@ extern "C" int dp_read_gray(dp_ctx *c, int view, uint16_t *out)
     size_t off = 0;
     for (int v = 0; v < view; ++v)
         off += (size_t)gray_pitch(c->hv[v].W) * (size_t)c->hv[v].H;
-    DP_HIP(c, hipMemcpy2D(out, (size_t)W * 2, (const __half *)c->gray_pool + off, (size_t)pitch * 2, (size_t)W * 2,
+    DP_HIP(c, hipMemcpy2D(out, (size_t)W * 2, (const __half *)c->gray_pool.p + off, (size_t)pitch * 2, (size_t)W * 2,
                           (size_t)H, hipMemcpyDeviceToHost));
     return DP_OK;
 }
@@ -2128,11 +2121,11 @@ extern "C" int dp_fast_last_stats(dp_ctx *c, dp_fast_stats *out)
     if (!c || !out)
         return DP_E_ARG;
     *out = dp_fast_stats{};
-    if (!c->d_fstats)
+    if (!c->d_fstats.p)
         return DP_OK;
     unsigned long long v[5];
     DP_HIP(c, hipDeviceSynchronize());
-    DP_HIP(c, hipMemcpy(v, c->d_fstats, sizeof(v), hipMemcpyDeviceToHost));
+    DP_HIP(c, hipMemcpy(v, c->d_fstats.p, sizeof(v), hipMemcpyDeviceToHost));
     out->clipped_stagings = (int64_t)v[4];
     out->patches = (int64_t)v[0];
     out->evals = (int64_t)v[1];

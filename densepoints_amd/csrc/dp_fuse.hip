@@ -377,10 +377,8 @@ extern "C" int dp_fuse_maps_device(dp_ctx *c, const int32_t *views, int n_views,
     }
     hipSetDevice(c->device);
     hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    if (!c->u_e0) {
-        DP_HIP(c, hipEventCreate(&c->u_e0));
-        DP_HIP(c, hipEventCreate(&c->u_e1));
-    }
+    DP_HIP(c, c->u_e0.create());
+    DP_HIP(c, c->u_e1.create());
     const unsigned gx = (unsigned)std::max<int64_t>((max_px + dpk::kFuseBlock - 1) / dpk::kFuseBlock, 1);
     const int64_t blocks = (int64_t)gx * n_views;
     if (blocks > 0x7FFFFFFFll - 1)

@@ -328,10 +328,8 @@ extern "C" int dp_render_maps_device(dp_ctx *c, const dp_patch *d_patches, int64
         return rc;
     hipSetDevice(c->device);
     hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    if (!c->r_e0) {
-        DP_HIP(c, hipEventCreate(&c->r_e0));
-        DP_HIP(c, hipEventCreate(&c->r_e1));
-    }
+    DP_HIP(c, c->r_e0.create());
+    DP_HIP(c, c->r_e1.create());
 
     // slot tables and the z-buffer layout
     std::vector<dpk::RenderSlot> slots((size_t)n_views);

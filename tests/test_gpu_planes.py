@@ -66,6 +66,14 @@ def test_akaze_planes_fed_steps_per_launch(orc, monkeypatch, steps):
     _compare_akaze_planes(orc, [c["noise"], c["border"]])
 
 
+def test_akaze_planes_of_views_in_later_chunks(orc, monkeypatch):
+    """A chunk budget of one byte puts each of 3 views of 160 x 120 in a chunk
+    of its own: the probe runs the chunks before its view's and stops after it."""
+    monkeypatch.setenv("DP_AKAZE_CHUNK_BYTES", "1")
+    c = ic.content_cases(160, 120)
+    assert _compare_akaze_planes(orc, [c["noise"], c["border"], c["noise01"]]) == 8
+
+
 @pytest.mark.parametrize("size", PLANE_SIZES, ids=lambda s: f"{s[0]}x{s[1]}")
 def test_orb_gray_levels_equal_oracle(orc, size):
     W, H = size
