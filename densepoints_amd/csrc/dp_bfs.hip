@@ -61,8 +61,7 @@ __global__ __launch_bounds__(256) void bfs_claims_kernel(BfsArgs a)
 }
 
 // -- capacity k > 1 (PatchGrid::TryInsert's size() < max_patches_per_cell):
-// k rounds, each granting every cell with room its smallest pending seq (the
-// same rounds as dp_kernels.hip's host-sized claimk_* kernels)
+// k rounds, each granting every cell with room its smallest pending seq
 __global__ __launch_bounds__(256) void bfs_claimk_init_kernel(BfsArgs a)
 {
     const int64_t n = a.cur->ncand;
@@ -215,8 +214,8 @@ __global__ __launch_bounds__(kBfsBlocks) void bfs_scan_kernel(BfsArgs a)
     const uint32_t before = (t >> 6) ? ws[(t >> 6) - 1] : 0u;
     a.bsum[t] = before + x - v; // exclusive offset of chunk t
     const uint32_t total = ws[kBfsBlocks / 64 - 1];
-    for (int k = t; k < kWorkCounters; k += blockDim.x)
-        a.work[k] = 0u;
+    if (t == 0)
+        a.work[0] = 0u;
     if (a.lpt_scratch)
         for (int k = t; k < 2 * kLptBuckets; k += blockDim.x)
             a.lpt_scratch[k] = 0u;

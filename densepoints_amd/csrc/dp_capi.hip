@@ -175,7 +175,7 @@ extern "C" int dp_ctx_create(const dp_options *opt, int device, dp_ctx **out)
         return rc;
     }
     if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess ||
-        c->d_work.reserve(dpk::kWorkCounters) != hipSuccess || c->d_evals.reserve(1) != hipSuccess ||
+        c->d_work.reserve(1) != hipSuccess || c->d_evals.reserve(1) != hipSuccess ||
         c->e0.create() != hipSuccess || c->e1.create() != hipSuccess ||
         c->ej.create(hipEventDisableTiming) != hipSuccess || c->mbox.reserve(8) != hipSuccess ||
         hipMemset(c->mbox.p, 0, 8 * sizeof(unsigned long long)) != hipSuccess) {

@@ -168,7 +168,7 @@ struct dp_ctx {
 namespace dpk {
 
 // One refine launch as its caller describes it, for either engine (the parity
-// kernel, dp_kernels.hip, or the performance kernel, dp_fast.hip); everything
+// kernel, dp_refine.hip, or the performance kernel, dp_fast_kernel.hip); everything
 // an engine derives from the context stays in refine_args / dp_fast_launch.
 // Refine/eval of n patches in device memory, or with parents the 4 (n / 4)
 // expansion children of parents[parent0 + (items ? items[k] : k)], k < n / 4.

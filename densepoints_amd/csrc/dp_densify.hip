@@ -249,7 +249,7 @@ static int run_generations(dp_ctx *c, int64_t max_gens, int64_t cap0, hipStream_
             c->g_lpt_scratch = c->lpt.p + cap;
         }
         // the first generation's counters (later ones are zeroed by the previous organizer)
-        DP_HIP(c, hipMemsetAsync(c->d_work.p, 0, dpk::kWorkCounters * sizeof(uint32_t), s));
+        DP_HIP(c, hipMemsetAsync(c->d_work.p, 0, sizeof(uint32_t), s));
         if (c->fopt.densify) {
             // dp_fast_last_stats: the batch's generations count as one launch
             DP_HIP(c, c->d_fstats.reserve(8));

@@ -11,9 +11,6 @@ namespace dpk {
 constexpr int kWave = 64;
 constexpr int kWavesPerBlock = 4;
 constexpr int kBlock = kWave * kWavesPerBlock;
-// refine work counters: one per XCD range, each on its own 64-B line
-constexpr int kWorkStride = 16;
-constexpr int kWorkCounters = 8 * kWorkStride;
 
 struct GenDev;
 
@@ -110,7 +107,7 @@ struct RefineArgs {
     dp_options opt;
     dp_patch *patches;       // in/out (EVAL..EXPAND on existing patches)
     uint8_t *accept;         // optional
-    uint32_t *work;          // dequeue counters, kWorkCounters (zeroed per launch)
+    uint32_t *work;          // the launch's dequeue counter (one word, zeroed per launch)
     unsigned long long *evals; // optional: total objective evaluations
     // expansion-generation fields (mode DP_MODE_EXPAND with parents != null)
     const dp_patch *parents; // queue; child c expands parents[parent0 + c/4] direction c%4

@@ -1,4 +1,4 @@
-// dp_kernels.hip -- gfx950 kernels of the PMVS patch loop.
+// dp_refine.hip -- the parity refine of the PMVS patch loop (gfx950).
 //
 //   refine_kernel   one WAVEFRONT per candidate patch: objective evaluation
 //                   (window map per view, fixed-point bilinear sampling of the
@@ -7,27 +7,21 @@
 //                   and the NCC filter fused in one launch.  Waves pull patches
 //                   from a device work counter (NM needs 8..70+ evaluations per
 //                   patch, so static assignment would leave CUs idle).
-//   claim/resolve   organizer occupancy: cell owner = min sequence number
-//                   (atomicMin), which reproduces the reference's single-thread
-//                   TryInsert order generation by generation.
-//   append          accepted candidates -> patch store, ComputeColor.
+//   lpt_*           the longest-first dequeue order of a launch (launch_refine)
+//
+// (The organizer kernels are in dp_bfs.hip, the pyramid in dp_pyramid.hip, the
+// multi-GPU partition in dp_partition.hip.)
 //
 // Reference anchors: methods/pmvs/optimization_opencv.cpp:14-78 (functor +
-// DownhillSolver), optimization.cpp:14-132, patch.cpp:19-164,
-// patch_organizer.cpp:15-65, expand.cpp:34-143.
+// DownhillSolver), optimization.cpp:14-132, patch.cpp:19-164, expand.cpp:34-143.
 #include "dp_internal.h"
+#include "dp_wave.h"
 
 namespace dpk {
 namespace {
 
 #ifndef DP_TEX_PER_LANE
 #define DP_TEX_PER_LANE 4
-#endif
-
-// texels whose fp64 coordinate chains the scheduler may interleave in a pass
-// (a scheduling barrier after every DP_TEX_ILP texels)
-#ifndef DP_TEX_ILP
-#define DP_TEX_ILP 1
 #endif
 
 #ifndef DP_MAP_CHUNK
@@ -77,52 +71,6 @@ __device__ unsigned long long g_stamps[8];
 #define STAMP_BEGIN
 #define STAMP(L, cat)
 #endif
-
-__device__ __forceinline__ void wave_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-__device__ __forceinline__ int uni(int v) { return __builtin_amdgcn_readfirstlane(v); }
-
-// wave-uniform copy of a double (lane 0's), so comparisons on it are scalar branches
-__device__ __forceinline__ double uni_f64(double v)
-{
-    const long long b = __double_as_longlong(v);
-    const int lo = __builtin_amdgcn_readfirstlane((int)(b & 0xffffffff));
-    const int hi = __builtin_amdgcn_readfirstlane((int)(b >> 32));
-    return __longlong_as_double(((long long)(unsigned)hi << 32) | (unsigned)lo);
-}
-
-__device__ __forceinline__ double readlane_f64(double v, int l)
-{
-    const long long b = __double_as_longlong(v);
-    const int lo = __builtin_amdgcn_readlane((int)(b & 0xffffffff), l);
-    const int hi = __builtin_amdgcn_readlane((int)(b >> 32), l);
-    return __longlong_as_double(((long long)(unsigned)hi << 32) | (unsigned)lo);
-}
-
-// Lane id through an opaque (volatile) mbcnt: values derived from it are
-// recomputed where they are used instead of being hoisted to kernel scope,
-// where dozens of per-lane LDS addresses would stay live in VGPRs across the
-// whole Nelder-Mead loop.
-__device__ __forceinline__ int lane_id()
-{
-    int l;
-    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
-    return l;
-}
-
-// A dp_options field read afresh from the kernel-argument segment at its use
-// (a volatile scalar load) instead of an SGPR kept live across the kernel:
-// the kernel runs out of SGPRs, and the compiler's spills of the option block
-// came back through v_readlane (VALU) in the per-evaluation loops.
-#define DP_KARG(T, field)                                                                             \
-    (*(const volatile __attribute__((address_space(4))) T *)((const __attribute__((address_space(4))) char *) \
-                                                                  __builtin_amdgcn_kernarg_segment_ptr() +   \
-                                                              offsetof(RefineArgs, field)))
 
 // visible mask -> ascending list + count (Patch::GetTrullyVisibleImages)
 __device__ __forceinline__ void decode_vis(WaveLds &L, uint64_t v0, uint64_t v1)
@@ -199,14 +147,8 @@ __device__ __forceinline__ TexelLoad texel_fetch(gpix_t roi, int pitch, int wm32
     // pixel offsets inside one image plane: pitch < 2^24, y < 2^24
     const uint32_t o0 = __umul24((uint32_t)cy >> 5, (uint32_t)pitch) + ((uint32_t)cx >> 5);
     TexelLoad t;
-#ifdef DP_DIAG_HOTIMG
-    // diagnostic build: every gather hits one 1 KiB block (timing only)
-    t.a = *(gpair_t)(roi + (o0 & 127u));
-    t.b = *(gpair_t)(roi + ((o0 + 16u) & 127u));
-#else
     t.a = *(gpair_t)(roi + o0);
     t.b = *(gpair_t)(roi + o0 + pitch);
-#endif
     t.fx = (uint32_t)cx & 31u;
     t.fy = (uint32_t)cy & 31u;
     return t;
@@ -228,11 +170,6 @@ __device__ __forceinline__ TexelLoad texel_fetch_n(gbyte_t base, gbyte_t base1, 
     uint32_t xo, o0;
     asm("v_lshl_add_u32 %0, %1, 2, %2" : "=v"(xo) : "v"((uint32_t)cx >> 5), "v"(roi));
     asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(o0) : "v"((uint32_t)cy >> 5), "v"(pitch4), "v"(xo));
-#ifdef DP_DIAG_HOTIMG
-    // diagnostic build: every gather hits the first DP_DIAG_HOTIMG bytes of the
-    // pool (a power of two; timing only)
-    o0 &= (uint32_t)(DP_DIAG_HOTIMG) - 1u;
-#endif
     TexelLoad t;
     t.a = *(gpair_t)(base + o0);
     if (kUniPitch)
@@ -393,15 +330,6 @@ __host__ __device__ constexpr int pass_width(int cell)
 
 static_assert(kTexPerLane % 2 == 0, "texels are packed in u16 pairs");
 
-typedef __attribute__((address_space(3))) const double *lds_f64_t;
-typedef __attribute__((address_space(3))) uint32_t *lds_u32_t;
-typedef __attribute__((address_space(3))) uint16_t *lds_u16_t;
-
-__device__ __forceinline__ uint32_t lds_addr(const void *p)
-{
-    return (uint32_t)(uintptr_t)(__attribute__((address_space(3))) const char *)p;
-}
-
 // Per-lane texel descriptors of a pass (fixed per launch: depend on the wave's
 // LDS block, the lane, G and the cell only), computed once per wave so the
 // texel loop does no index arithmetic: LDS byte addresses of each texel's row
@@ -485,10 +413,9 @@ __device__ __forceinline__ void group_sample_safe(const RefineArgs &a, WaveLds &
             tl[i] = texel_fetch_n<kUniPitch>((gbyte_t)a.img_base, base1, (uint32_t)roi, pitch * 4, wm32, hm32, ix, iy);
         else
             tl[i] = texel_fetch((gpix_t)roi, pitch, wm32, hm32, ix, iy);
-        // DP_TEX_ILP texels' fp64 coordinate math at a time: only the issued
-        // loads stay live across the pass
-        if ((i + 1) % DP_TEX_ILP == 0)
-            __builtin_amdgcn_sched_barrier(0);
+        // one texel's fp64 coordinate math at a time: only the issued loads
+        // stay live across the pass
+        __builtin_amdgcn_sched_barrier(0);
     }
     // one consume phase for all lanes (no divergence): grays packed in u16
     // pairs, moments as u16 dot products.  In the anchor pass the texture-0
@@ -908,18 +835,6 @@ __device__ __forceinline__ int wave_scores(const RefineArgs &a, WaveLds &L, cons
     const int nv = m - 1;
     const int cell = a.cell;
     const int N = cell * cell;
-    // view data of the first map round: the visible list is fixed during the
-    // refine, so these loads go out before the corner math and overlap it
-#ifndef DP_PRELOAD_VIEWS
-#define DP_PRELOAD_VIEWS 0
-#endif
-#if DP_PRELOAD_VIEWS
-    const MapView mv0 = load_map_view(a, L, 0, m, 0);
-#endif
-#ifdef DP_DIAG_CORNER_REPEAT
-    // diagnostic build (timing only): the idempotent corner block runs twice
-    for (int rep = 0; rep < 2; ++rep)
-#endif
     {
         double c12[12];
         const double Xs[3] = {L.X[0], L.X[1], L.X[2]};
@@ -949,21 +864,12 @@ __device__ __forceinline__ int wave_scores(const RefineArgs &a, WaveLds &L, cons
     for (int base = 0; base < m; base += kMapChunk) {
         // window maps of this chunk, 16 views per round (4 lanes per view)
         uint64_t okmask = 0;
-#ifdef DP_DIAG_MAP_REPEAT
-        // diagnostic build (timing only): the idempotent map build runs twice
-        for (int rep = 0; rep < 2; ++rep, okmask = rep < 2 ? 0 : okmask)
-#endif
         if (m - base > 16) {
             // more than 16 views in this chunk: one round, two lanes per view
             static_assert(kMapChunk <= 32, "a pair round covers the chunk");
             okmask = build_maps_pair(load_map_view<1>(a, L, base, m, 0), L, base, m, 0, cell, a.narrow != 0);
         } else {
-#if DP_PRELOAD_VIEWS
-            okmask = build_maps_quad(base == 0 ? mv0 : load_map_view(a, L, base, m, 0), L, base, m, 0, cell,
-                                     a.narrow != 0);
-#else
             okmask = build_maps_quad(load_map_view(a, L, base, m, 0), L, base, m, 0, cell, a.narrow != 0);
-#endif
         }
         wave_sync();
         STAMP(L, 0);
@@ -978,31 +884,13 @@ __device__ __forceinline__ int wave_scores(const RefineArgs &a, WaveLds &L, cons
                                        ~((1ull << (kb - base)) - 1ull));
         const bool anc = base == 0 && va;
         views_all<G>(a, L, td, base, todo, anc, Sa, Saa);
-#ifdef DP_DIAG_PASS_REPEAT
-        // diagnostic build (timing only): the idempotent view passes run twice
-        views_all<G>(a, L, td, base, todo, anc, Sa, Saa);
-#endif
         STAMP(L, 1);
         wave_sync();
         STAMP(L, 2);
         // NCC finish, one lane per view of the chunk (error_measurements.cpp:47-59)
-#ifdef DP_DIAG_NCC_REPEAT
-        // diagnostic build (timing only): the idempotent NCC finish runs twice
-        for (int rep = 0; rep < 2; ++rep) {
-            const int kr = base + lane;
-            if (kr >= kb && kr < ke) {
-                double sc = -1.0;
-                if ((valid >> lane) & 1ull)
-                    sc = dpg::ncc_finish(N, Sa, Saa, L.mom[lane][0], L.mom[lane][1], L.mom[lane][2],
-                                         a.opt.ncc_denom_min);
-                L.score[kr - 1] = sc;
-            }
-            wave_sync();
-        }
-#endif
         const int k = base + lane;
         const bool scored = k >= kb && k < ke && ((valid >> lane) & 1ull);
-        const double sc = wave_ncc_finish(N, Sa, Saa, L, scored, DP_KARG(double, opt.ncc_denom_min));
+        const double sc = wave_ncc_finish(N, Sa, Saa, L, scored, DP_KARG(RefineArgs, double, opt.ncc_denom_min));
         if (k >= kb && k < ke)
             L.score[k - 1] = scored ? sc : -1.0;
         wave_sync();
@@ -1039,17 +927,7 @@ __device__ __forceinline__ double wave_objective(const RefineArgs &a, WaveLds &L
 enum NmPhase { kInit = 0, kReflect = 1, kExpand = 2, kContract = 3, kShrink = 4 };
 
 // Nelder-Mead decisions on wave-uniform copies (scalar branches, SGPR state)
-#ifndef DP_NM_UNIFORM
-#define DP_NM_UNIFORM 1
-#endif
-__device__ __forceinline__ double nm_uni(double v)
-{
-#if DP_NM_UNIFORM
-    return uni_f64(v);
-#else
-    return v;
-#endif
-}
+__device__ __forceinline__ double nm_uni(double v) { return uni_f64(v); }
 
 // y[i] for a uniform index without a private array
 __device__ __forceinline__ double pick_y(const double *yy, int i)
@@ -1064,8 +942,8 @@ __device__ __forceinline__ double pick_y(const double *yy, int i)
 template <int G>
 __device__ __forceinline__ int wave_nelder_mead(const RefineArgs &a, WaveLds &L, const TexDesc &td, bool &degen)
 {
-    const double step[3] = {DP_KARG(double, opt.nm_step[0]), DP_KARG(double, opt.nm_step[1]),
-                            DP_KARG(double, opt.nm_step[2])};
+    const double step[3] = {DP_KARG(RefineArgs, double, opt.nm_step[0]), DP_KARG(RefineArgs, double, opt.nm_step[1]),
+                            DP_KARG(RefineArgs, double, opt.nm_step[2])};
     for (int i = 1; i <= 3; ++i) {
         for (int jj = 0; jj < 3; ++jj)
             L.sp[i][jj] = 0.0;
@@ -1196,8 +1074,8 @@ __device__ __forceinline__ int wave_nelder_mead(const RefineArgs &a, WaveLds &L,
             const double rr = fabs(mx - mn);
             range = (range < rr) ? rr : range;
         }
-        if (range <= DP_KARG(double, opt.nm_eps) || err <= DP_KARG(double, opt.nm_eps) ||
-            fcount >= DP_KARG(int32_t, opt.nm_max_evals))
+        if (range <= DP_KARG(RefineArgs, double, opt.nm_eps) || err <= DP_KARG(RefineArgs, double, opt.nm_eps) ||
+            fcount >= DP_KARG(RefineArgs, int32_t, opt.nm_max_evals))
             break;
         fcount += 2;
         L.ylo = L.y[ilo];
@@ -1241,7 +1119,7 @@ __device__ __forceinline__ bool wave_filter(const RefineArgs &a, WaveLds &L, con
     score = (float)(sum / (double)nv);
     const uint64_t v0 = L.vis[0], v1 = L.vis[1];
     const uint64_t below = (1ull << lane) - 1ull;
-    const double thr = DP_KARG(double, opt.ncc_threshold);
+    const double thr = DP_KARG(RefineArgs, double, opt.ncc_threshold);
     const int c0 = __popcll(v0);
     const bool in0 = (v0 >> lane) & 1ull;
     const int r0 = __popcll(v0 & below);
@@ -1253,7 +1131,7 @@ __device__ __forceinline__ bool wave_filter(const RefineArgs &a, WaveLds &L, con
     const uint64_t n1 = __ballot(in1 && !drop1);
     wave_sync();
     decode_vis(L, n0, n1);
-    return uni(L.m) >= DP_KARG(int32_t, opt.min_visible);
+    return uni(L.m) >= DP_KARG(RefineArgs, int32_t, opt.min_visible);
 }
 
 // Patch::InitRelatedImages (patch.cpp:19-49), one lane per view
@@ -1265,11 +1143,11 @@ __device__ void wave_init_related(const RefineArgs &a, WaveLds &L)
     const double n[3] = {L.n[0], L.n[1], L.n[2]};
     int cls0 = 0, cls1 = 0;
     if (lane < a.V && lane != ref)
-        cls0 = dpg::classify_view(a.views[lane], X, n, DP_KARG(double, opt.visible_angle),
-                                  DP_KARG(double, opt.candidate_angle));
+        cls0 = dpg::classify_view(a.views[lane], X, n, DP_KARG(RefineArgs, double, opt.visible_angle),
+                                  DP_KARG(RefineArgs, double, opt.candidate_angle));
     if (64 + lane < a.V && 64 + lane != ref)
-        cls1 = dpg::classify_view(a.views[64 + lane], X, n, DP_KARG(double, opt.visible_angle),
-                                  DP_KARG(double, opt.candidate_angle));
+        cls1 = dpg::classify_view(a.views[64 + lane], X, n, DP_KARG(RefineArgs, double, opt.visible_angle),
+                                  DP_KARG(RefineArgs, double, opt.candidate_angle));
     const uint64_t v0 = __ballot(cls0 == 1), v1 = __ballot(cls1 == 1);
     const uint64_t c0 = __ballot(cls0 == 2), c1 = __ballot(cls1 == 2);
     wave_sync();
@@ -1291,7 +1169,7 @@ __device__ void child_position(const RefineArgs &a, const dp_patch &par, int dir
     dpg::project(rv.P, X[0] + rv.xr[0], X[1] + rv.xr[1], X[2] + rv.xr[2], qu, qv);
     const double du = qu - cu, dv = qv - cv;
     const double dx = sqrt(du * du + dv * dv);
-    const double scale = (double)DP_KARG(int32_t, opt.grid_scale) / dx;
+    const double scale = (double)DP_KARG(RefineArgs, int32_t, opt.grid_scale) / dx;
     for (int i = 0; i < 3; ++i) {
         const double d = dir == 0 ? rv.xr[i] : dir == 1 ? -rv.xr[i] : dir == 2 ? yax[i] : -yax[i];
         out[i] = (float)(X[i] + scale * d);
@@ -1311,34 +1189,6 @@ __device__ void child_position(const RefineArgs &a, const dp_patch &par, int dir
 #else
 #define DP_REFINE_BOUNDS __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(DP_REFINE_WAVES_PER_EU)))
 #endif
-
-#ifndef DP_XCD_RANGES
-#define DP_XCD_RANGES 0
-#endif
-#ifndef DP_SIBLING_DEQUEUE
-#define DP_SIBLING_DEQUEUE 1
-#endif
-#if DP_XCD_RANGES
-constexpr int kXcds = 8;
-#else
-constexpr int kXcds = 1;
-#endif
-
-__device__ __forceinline__ uint32_t xcc_id()
-{
-#if DP_XCD_RANGES
-    uint32_t x;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(x));
-    return x;
-#else
-    return 0;
-#endif
-}
-
-__device__ __forceinline__ uint32_t range_lo(int n, int x)
-{
-    return (uint32_t)(((uint64_t)n * (uint64_t)x) / (uint64_t)kXcds);
-}
 
 template <int kMode, int G, bool kGen = false>
 __global__ DP_REFINE_BOUNDS void refine_kernel(RefineArgs a)
@@ -1361,47 +1211,20 @@ __global__ DP_REFINE_BOUNDS void refine_kernel(RefineArgs a)
         L.stamp[c] = 0;
 #endif
     const TexDesc td = make_texdesc<G>(L, a.cell);
-    // XCD-local work ranges: the batch is cut into kXcds contiguous ranges and
-    // the waves of XCD x dequeue from range x first (consecutive candidates are
-    // spatial neighbours, so their windows share the XCD's L2 across the
-    // evaluations of a patch), then help the other ranges in order.
-    int cur = (int)(xcc_id() & (kXcds - 1));
-    int left = kXcds;
     const uint32_t gs = a.parents ? 4u : 1u;                     // LPT group size
     const int npos = a.order ? (int)(((uint32_t)n + gs - 1) / gs * gs) : n; // dequeue positions
-    // positions per dequeue: DP_SIBLING_DEQUEUE = 4 takes a parent's 4 children
-    // at once (one wave refines them back to back: their windows overlap)
-    const uint32_t step = (a.order && gs == 4u) ? (uint32_t)DP_SIBLING_DEQUEUE : 1u;
-    uint32_t run_pos = 0, run_left = 0;
     for (;;) {
+        // one position per dequeue from the launch's work counter (lane 0's,
+        // clamped to npos and broadcast)
         uint32_t idx = (uint32_t)npos;
-        if (run_left == 0) {
-            uint32_t cnt = 0;
-            if (lane == 0) {
-                while (left > 0) {
-                    const uint32_t lo = range_lo(npos, cur), hi = range_lo(npos, cur + 1);
-                    const uint32_t t = lo + atomicAdd(a.work + kWorkStride * cur, step);
-                    if (t < hi) {
-                        idx = t;
-                        // a run never crosses into the next XCD range (whose own
-                        // waves dequeue those positions)
-                        cnt = hi - t < step ? hi - t : step;
-                        break;
-                    }
-                    cur = (cur + 1) & (kXcds - 1);
-                    --left;
-                }
-            }
-            idx = (uint32_t)uni((int)idx);
-            if (idx >= (uint32_t)npos)
-                break;
-            run_pos = idx;
-            run_left = (uint32_t)uni((int)cnt);
+        if (lane == 0) {
+            const uint32_t t = atomicAdd(a.work, 1u);
+            if (t < (uint32_t)npos)
+                idx = t;
         }
-        idx = run_pos++;
-        --run_left;
+        idx = (uint32_t)uni((int)idx);
         if (idx >= (uint32_t)npos)
-            continue;
+            break;
         if (a.order) {
             idx = (uint32_t)uni((int)(a.order[idx / gs] * gs + idx % gs));
             if (idx >= (uint32_t)n) // the last group's missing children
@@ -1564,77 +1387,7 @@ __global__ void probe_texel_kernel(const unsigned long long *ta, const unsigned 
     gray[i] = texel_gray(t);
 }
 
-// ---- image pyramid ------------------------------------------------------------
-// cv::pyrDown on BGRA8 planes: dst(x, y) = sum_ij w_i w_j src(2x+j-2, 2y+i-2)
-// with w = [1 4 6 4 1] (total 256), BORDER_REFLECT_101, (s + 128) >> 8 per
-// channel.  One block = 64 x 16 outputs of one view; its 132 x 36 source tile
-// (reflected at the image borders) is staged in LDS once, then each thread
-// forms 4 outputs with SWAR sums: B,R and G,A in the 16-bit halves of two
-// u32 accumulators (column sums <= 16*255, totals <= 256*255 < 2^16, so no
-// carry crosses a half).
-constexpr int kPyrTX = 64, kPyrTY = 16;
-constexpr int kPyrCols = 2 * kPyrTX + 4, kPyrRows = 2 * kPyrTY + 4;
-
-__device__ __forceinline__ int reflect101(int x, int n)
-{
-    x = x < 0 ? -x : x;
-    x = x >= n ? 2 * n - 2 - x : x;
-    return x < 0 ? 0 : (x >= n ? n - 1 : x); // n == 1
-}
-
-__global__ __launch_bounds__(256) void pyr_down_kernel(const PyrPlane *src, const PyrPlane *dst)
-{
-    __shared__ uint32_t tile[kPyrRows][kPyrCols + 1];
-    const PyrPlane s = src[blockIdx.z], d = dst[blockIdx.z];
-    const int ox0 = blockIdx.x * kPyrTX, oy0 = blockIdx.y * kPyrTY;
-    if (ox0 >= d.w || oy0 >= d.h)
-        return; // uniform per block
-    const int sx0 = 2 * ox0 - 2, sy0 = 2 * oy0 - 2;
-    for (int e = threadIdx.x; e < kPyrRows * kPyrCols; e += 256) {
-        const int r = e / kPyrCols, c = e - r * kPyrCols;
-        const int yy = reflect101(sy0 + r, s.h), xx = reflect101(sx0 + c, s.w);
-        tile[r][c] = s.img[(size_t)yy * (size_t)s.pitch + (size_t)xx];
-    }
-    __syncthreads();
-    const int tx = threadIdx.x & (kPyrTX - 1), ty = threadIdx.x / kPyrTX;
-    const int ox = ox0 + tx;
-    const uint32_t w[5] = {1u, 4u, 6u, 4u, 1u};
-#pragma unroll
-    for (int k = 0; k < kPyrTY / 4; ++k) {
-        const int r = ty + 4 * k;
-        const int oy = oy0 + r;
-        uint32_t br = 0u, ga = 0u;
-#pragma unroll
-        for (int j = 0; j < 5; ++j) {
-            uint32_t cbr = 0u, cga = 0u;
-#pragma unroll
-            for (int i = 0; i < 5; ++i) {
-                const uint32_t p = tile[2 * r + i][2 * tx + j];
-                cbr += w[i] * (p & 0x00FF00FFu);
-                cga += w[i] * ((p >> 8) & 0x00FF00FFu);
-            }
-            br += w[j] * cbr;
-            ga += w[j] * cga;
-        }
-        if (ox < d.w && oy < d.h) {
-            br = ((br + 0x00800080u) >> 8) & 0x00FF00FFu;
-            ga = ((ga + 0x00800080u) >> 8) & 0x00FF00FFu;
-            d.img[(size_t)oy * (size_t)d.pitch + (size_t)ox] = br | (ga << 8);
-        }
-    }
-}
-
 } // namespace
-
-hipError_t launch_pyr_down(const PyrPlane *d_src, const PyrPlane *d_dst, int V, int max_dw, int max_dh,
-                           hipStream_t s)
-{
-    if (V <= 0 || max_dw <= 0 || max_dh <= 0)
-        return hipSuccess;
-    const dim3 grid((max_dw + kPyrTX - 1) / kPyrTX, (max_dh + kPyrTY - 1) / kPyrTY, V);
-    hipLaunchKernelGGL(pyr_down_kernel, grid, dim3(256), 0, s, d_src, d_dst);
-    return hipGetLastError();
-}
 
 hipError_t launch_probe_texel(const unsigned long long *ta, const unsigned long long *tb, const uint32_t *fxy, int n,
                               int32_t *gray)
@@ -1750,7 +1503,7 @@ hipError_t launch_refine(const RefineArgs &a, hipStream_t s)
     const int64_t cap = (int64_t)cus * 8;
     const int grid = gen ? (int)cap : (int)(want < cap ? want : cap);
     hipError_t e = hipSuccess;
-    if (!gen && (e = hipMemsetAsync(a.work, 0, kWorkCounters * sizeof(uint32_t), s)) != hipSuccess)
+    if (!gen && (e = hipMemsetAsync(a.work, 0, sizeof(uint32_t), s)) != hipSuccess)
         return e;
     const int g = pass_width(a.cell);
     if (g <= 0)
@@ -1796,156 +1549,6 @@ hipError_t launch_refine(const RefineArgs &a, hipStream_t s)
     default:
         return hipErrorInvalidValue;
     }
-    return hipGetLastError();
-}
-
-// Seed::CreatePatchesFromPoints (seed.cpp:26-54), one thread per seed point:
-// ref = the nearest camera centre (first minimum), normal = the unit ray from
-// it, then InitRelatedImages (patch.cpp:19-49) on the stored f32 pose.  The
-// views are read in lock-step by the wave (broadcast loads).
-__global__ void seed_patches_kernel(const dpg::ViewDev *views, int V, const double *xyz, int64_t n,
-                                    double vis_angle, double cand_angle, dp_patch *out)
-{
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n)
-        return;
-    const double X[3] = {xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]};
-    double best = 0.0;
-    int ref = 0;
-    for (int v = 0; v < V; ++v) {
-        const double d[3] = {X[0] - views[v].C[0], X[1] - views[v].C[1], X[2] - views[v].C[2]};
-        const double dist = sqrt(dpg::dot3(d, d));
-        if (v == 0 || dist < best) {
-            best = dist;
-            ref = v;
-        }
-    }
-    const double t[3] = {X[0] - views[ref].C[0], X[1] - views[ref].C[1], X[2] - views[ref].C[2]};
-    const double tn = sqrt(dpg::dot3(t, t));
-    dp_patch p{};
-    p.ref = (uint32_t)ref;
-    p.parent = 0xFFFFFFFFu;
-    for (int k = 0; k < 3; ++k) {
-        p.pos[k] = (float)X[k];
-        p.normal[k] = (float)(t[k] / tn);
-    }
-    const double Xs[3] = {p.pos[0], p.pos[1], p.pos[2]};
-    const double ns[3] = {p.normal[0], p.normal[1], p.normal[2]};
-    for (int v = 0; v < V; ++v) {
-        if (v == ref)
-            continue;
-        const int cls = dpg::classify_view(views[v], Xs, ns, vis_angle, cand_angle);
-        if (cls == 1)
-            p.vis[v >> 6] |= 1ull << (v & 63);
-        else if (cls == 2)
-            p.cand[v >> 6] |= 1ull << (v & 63);
-    }
-    out[i] = p;
-}
-
-hipError_t launch_seed_patches(const dpg::ViewDev *views, int V, const double *xyz, int64_t n, double vis_angle,
-                               double cand_angle, dp_patch *out, hipStream_t s)
-{
-    if (n <= 0)
-        return hipSuccess;
-    hipLaunchKernelGGL(seed_patches_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, views, V, xyz, n,
-                       vis_angle, cand_angle, out);
-    return hipGetLastError();
-}
-
-// Super-tile key of each item (spec in include/densepoints.h): the
-// centre projected into its reference view, ty = floor(v / tile) and tx =
-// floor(u / tile) clamped to [-1, TY] / [-1, TX] (NaN and |q| >= 2e9 count as
-// 0), key = (ref (TY + 2) + ty + 1) (TX + 2) + tx + 1: dense, so the sort
-// covers only the key's ceil(log2(V (TY + 2) (TX + 2))) low bits.  Sorting by
-// key orders the items by (reference view, tile row, tile column); the
-// partition cuts that order into `world` contiguous equal shares.
-__device__ __forceinline__ uint64_t tile_coord(double q, int64_t tmax)
-{
-    int64_t t = 0;
-    if (q > -2.0e9 && q < 2.0e9)
-        t = (int64_t)floor(q);
-    t = t < -1 ? -1 : t > tmax ? tmax : t;
-    return (uint64_t)(t + 1);
-}
-
-__global__ void tile_keys_kernel(const dpg::ViewDev *views, const dp_patch *items, int64_t n, double tile, int64_t tx_max,
-                                 int64_t ty_max, uint64_t *key, int64_t *iota, unsigned long long *stats)
-{
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i == 0) // the partition statistics' counters (partition_stats_kernel adds to them)
-        stats[0] = stats[1] = 0ull;
-    if (i >= n)
-        return;
-    iota[i] = i; // the sort's values: item indices
-    const dp_patch &p = items[i];
-    const dpg::ViewDev &v = views[p.ref];
-    double u, w;
-    dpg::project(v.P, (double)p.pos[0], (double)p.pos[1], (double)p.pos[2], u, w);
-    key[i] = ((uint64_t)p.ref * (uint64_t)(ty_max + 2) + tile_coord(w / tile, ty_max)) * (uint64_t)(tx_max + 2) +
-             tile_coord(u / tile, tx_max);
-}
-
-// partition statistics over the key-sorted items: stats[0] = distinct tiles,
-// stats[1] = items of the tiles a cut lo[r] (0 < lo[r] < n) splits between ranks
-__global__ void partition_stats_kernel(const uint64_t *key, int64_t n, int world, unsigned long long *stats)
-{
-    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    unsigned long long heads = 0, split = 0;
-    if (j < n) {
-        const uint64_t k = key[j];
-        heads = (j == 0 || key[j - 1] != k) ? 1ull : 0ull;
-        for (int r = 1; r < world; ++r) {
-            // the cut lo_r = floor(r n / world) (n < 2^31, world <= 64: no overflow)
-            const int64_t c = ((int64_t)r * n) / world;
-            if (c > 0 && c < n && key[c - 1] == key[c] && key[c] == k) {
-                split = 1;
-                break;
-            }
-        }
-    }
-    for (int o = 32; o > 0; o >>= 1) {
-        heads += __shfl_xor(heads, o);
-        split += __shfl_xor(split, o);
-    }
-    if ((threadIdx.x & 63) == 0 && (heads | split)) {
-        atomicAdd(&stats[0], heads);
-        atomicAdd(&stats[1], split);
-    }
-}
-
-hipError_t launch_tile_keys(const dpg::ViewDev *views, const dp_patch *items, int64_t n, double tile, int64_t tx_max,
-                            int64_t ty_max, uint64_t *key, int64_t *iota, unsigned long long *stats, hipStream_t s)
-{
-    if (n <= 0)
-        return hipSuccess;
-    hipLaunchKernelGGL(tile_keys_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, views, items, n, tile,
-                       tx_max, ty_max, key, iota, stats);
-    return hipGetLastError();
-}
-
-// (the counters were zeroed by tile_keys_kernel)
-hipError_t launch_partition_stats(const uint64_t *key, int64_t n, int world, unsigned long long *stats, hipStream_t s)
-{
-    if (n <= 0)
-        return hipSuccess;
-    hipLaunchKernelGGL(partition_stats_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, key, n, world,
-                       stats);
-    return hipGetLastError();
-}
-
-__global__ void gather_patches_kernel(const dp_patch *src, const int64_t *idx, int64_t n, dp_patch *dst)
-{
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n)
-        dst[i] = src[idx[i]];
-}
-
-hipError_t launch_gather_patches(const dp_patch *src, const int64_t *idx, int64_t n, dp_patch *dst, hipStream_t s)
-{
-    if (n <= 0)
-        return hipSuccess;
-    hipLaunchKernelGGL(gather_patches_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, src, idx, n, dst);
     return hipGetLastError();
 }
 

@@ -1,4 +1,4 @@
-"""Performance mode on the GPU (dp_fast.hip) against its specification, the
+"""Performance mode on the GPU (dp_fast_kernel.hip) against its specification, the
 oracle's or_fast.c, bit-exact on every field: gray planes, one fast
 evaluation, the CG refine -> InitRelatedImages -> fast filter sequence, and
 Expand::ExpandPatch children (expand.cpp:103-143) refined in performance mode,
@@ -101,11 +101,13 @@ def test_gray_planes_equal_spec(engine, orc):
 
 
 @pytest.mark.parametrize("gradient", [1, 0])
-@pytest.mark.parametrize("cell", [16, 11, 7, 5])
+@pytest.mark.parametrize("cell", [16, 11, 7, 5, 4, 6, 8, 9, 13])
 @pytest.mark.parametrize("mode", [N.MODE_FAST_EVAL, N.MODE_FAST_REFINE])
 def test_fast_modes_bit_exact(engine, orc, cell, mode, gradient):
     """Both refine specs: the analytic gradient (v4, default) and forward
-    differences (v3), at every pass shape (n = 16, 11, 7 with its tail sample, 5)."""
+    differences (v3), at every pass shape the dispatch selects: <G, slots> =
+    <1,4> (n = 16), <2,4> (11), <4,3> with the tail sample (7), <4,2> (5),
+    <4,1> (4), <4,3> without a tail (6), <4,4> (8), <2,3> (9), <1,3> (13)."""
     sc = scene("hf6")
     engine.set_views(sc.views)
     S = orc.Scene(sc.P, sc.imgs)

@@ -146,7 +146,7 @@ def test_seed_conversion_edge_points(engine, orc):
 
 
 @pytest.mark.parametrize("mode", [N.MODE_EVAL, N.MODE_FILTER, N.MODE_NM, N.MODE_SEED, N.MODE_EXPAND])
-@pytest.mark.parametrize("cell", [16, 11, 7])
+@pytest.mark.parametrize("cell", [16, 11, 7, 5])
 def test_refine_modes_bit_exact(engine, orc, mode, cell):
     sc = scene("hf6")
     engine.set_views(sc.views)

@@ -1,8 +1,10 @@
 #!/usr/bin/env bash
-# Parity-kernel LDS-staging study: the default library and
-# the diagnostic variants (DP_DIAG_LDS_PAD / DP_DIAG_LDS_TAPS builds under
-# densepoints_amd/lib/), each through bench.py's parity headline only; prints
-# rate, E and the time per evaluation.  Alternated twice.
+# A/B of library variants under densepoints_amd/lib/ (VARIANTS; default: the
+# default library alone), each through bench.py's parity headline only; prints
+# rate, E and the time per evaluation.  Alternated twice.  Written for the
+# parity-kernel LDS-staging study, whose diagnostic
+# variants were built from r05_parity_lds_tiles.patch; that patch applies to
+# dp_kernels.hip as of commit 35620e7, before it became dp_refine.hip.
 set -u
 cd "$(dirname "$0")/../.."
 mkdir -p gpurun_out

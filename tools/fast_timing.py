@@ -7,7 +7,7 @@ wave): share of the wave's cycles per phase, summed over every printed line.
 import re
 import sys
 
-# TMARK indices in dp_fast.hip
+# TMARK indices in dp_fast_kernel.hip
 NAMES = {
     0: "dequeue / child pose", 1: "frame", 2: "staging geometry", 3: "tile DMA issue", 4: "DMA wait",
     5: "CG bookkeeping", 6: "InitRelatedImages", 7: "filter frame", 8: "filter masks / finish",

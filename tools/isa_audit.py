@@ -7,7 +7,7 @@ the SGPR-spill reloads (v_readlane_b32 from the VGPRs the kernel's
 v_writelane_b32 spills use), quarter-rate integer multiplies and
 boolean round trips (v_cndmask 0/1 feeding a compare).
 
-    python tools/isa_audit.py [--src densepoints_amd/csrc/dp_kernels.hip]
+    python tools/isa_audit.py [--src densepoints_amd/csrc/dp_refine.hip]
                               [--kernel 'refine_kernelILi4ELi2E']
 
 Static counts: a block inside a loop counts once however often it runs.
@@ -84,7 +84,7 @@ def audit(body):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--src", default=os.path.join(ROOT, "densepoints_amd", "csrc", "dp_kernels.hip"))
+    ap.add_argument("--src", default=os.path.join(ROOT, "densepoints_amd", "csrc", "dp_refine.hip"))
     ap.add_argument("--kernel", default=r"refine_kernelILi4ELi2E")
     args = ap.parse_args()
     name, body = instance(disassemble(os.path.abspath(args.src)), args.kernel)

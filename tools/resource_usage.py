@@ -39,7 +39,7 @@ def usage(src, extra=()):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("sources", nargs="*", default=[os.path.join(B.CSRC, "dp_fast.hip")])
+    ap.add_argument("sources", nargs="*", default=[os.path.join(B.CSRC, "dp_fast_kernel.hip")])
     ap.add_argument("--filter", default="")
     ap.add_argument("-D", action="append", default=[], help="extra -D defines")
     a = ap.parse_args()
