@@ -48,6 +48,16 @@ __device__ __forceinline__ bool neighbours(const dp_patch &p, const dp_patch &q,
     return fabs(a) + fabs(b) < rho2;
 }
 
+// word w of V(p): the bits of vis that name one of the V views.  A bit at or
+// beyond V names no view (d_views holds V entries), so it is dropped here,
+// once per patch, and the bit loops below never see it.
+__device__ __forceinline__ uint64_t visible_word(const dp_patch &p, int w, int V)
+{
+    const int k = V - 64 * w; // views named by this word
+    const uint64_t m = k >= 64 ? ~0ull : (k <= 0 ? 0ull : (1ull << k) - 1ull);
+    return p.vis[w] & m;
+}
+
 __global__ void front_kernel(FilterArgs a)
 {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -55,7 +65,7 @@ __global__ void front_kernel(FilterArgs a)
         return;
     const dp_patch &p = a.patches[i];
     for (int w = 0; w < 2; ++w) {
-        uint64_t bits = p.vis[w];
+        uint64_t bits = visible_word(p, w, a.V);
         while (bits) {
             const int b = __builtin_ctzll(bits);
             bits &= bits - 1;
@@ -86,11 +96,11 @@ __global__ void visibility_kernel(FilterArgs a, uint8_t *keep)
     double sum = 0.0;
     int nv = 0;
     for (int w = 0; w < 2; ++w) {
-        uint64_t bits = p.vis[w];
+        uint64_t bits = visible_word(p, w, a.V);
         while (bits) {
             const int b = __builtin_ctzll(bits);
             bits &= bits - 1;
-            ++nv;
+            ++nv; // |V(p)|: masked bits only
             const dpg::ViewDev &v = a.views[w * 64 + b];
             int64_t row, col;
             if (!filter_cell(v, p.pos, a.grid_scale, row, col))
@@ -120,7 +130,7 @@ __global__ void neighbor_kernel(FilterArgs a, uint8_t *keep)
     const double rho2 = 2.0 * a.rho[i];
     int total = 0, near = 0;
     for (int w = 0; w < 2; ++w) {
-        uint64_t bits = p.vis[w];
+        uint64_t bits = visible_word(p, w, a.V);
         while (bits) {
             const int b = __builtin_ctzll(bits);
             bits &= bits - 1;

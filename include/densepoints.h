@@ -312,6 +312,15 @@ int dp_densify_commit_gathered_device(dp_ctx *ctx, dp_generation *gen, const dp_
  * with v in its visible set whose (f32 depth, index) is smallest there; depth =
  * third row of P [X;1].  rho(p) = grid_scale / dx(p) (dx as in ExpandPatch);
  * p, q are neighbours iff |(Xq-Xp).np| + |(Xq-Xp).nq| < 2 rho(p) (fp64).
+ * V(p) is the set of bits of vis below the context's V: a bit at or beyond V
+ * names no view and is ignored, so it counts in neither |V(p)|, the front map
+ * nor the 3x3 scan.  ref >= V gives rho(p) = 0 (no neighbours).  A patch is a
+ * front candidate of v only where its f32 depth is > 0 and its cell lies in
+ * v's grid (W / grid_scale by H / grid_scale whole cells; the coordinate is
+ * truncated toward zero, so (-grid_scale, 0) is cell 0); a depth that is <= 0
+ * or NaN never fronts a cell but the patch still reads the cell it projects
+ * to.  Scores are read as f32 and widened; the two tests are strict fp64
+ * comparisons, so a NaN on either side keeps the patch.
  *   DP_FILTER_VISIBILITY: U(p) = { front(v, c_v(p)) : v in V(p) } minus p and
  *     its neighbours (a multiset over views); p is removed iff
  *     |V(p)| * score(p) < sum_{q in U(p)} score(q).

@@ -1025,6 +1025,17 @@ static int or_fcell(const or_scene *s, const or_fgrid *g, int vi, const or_patch
     return *col >= 0 && *col < g[vi].gw && *row >= 0 && *row < g[vi].gh;
 }
 
+/* V(p): the bits of vis below the scene's V, ascending.  A bit at or beyond V
+ * names no view and is in neither |V(p)|, the front map nor the 3x3 scan. */
+static int or_fvis(const or_scene *s, const or_patch *p, int *list)
+{
+    int n = 0;
+    for (int v = 0; v < s->V; ++v)
+        if ((p->vis[v >> 6] >> (v & 63)) & 1u)
+            list[n++] = v;
+    return n;
+}
+
 static void or_build_front(const or_scene *s, const or_fgrid *g, const or_patch *p, int64_t n,
                            const uint8_t *alive, uint64_t *front, int64_t cells)
 {
@@ -1034,7 +1045,7 @@ static void or_build_front(const or_scene *s, const or_fgrid *g, const or_patch 
         if (!alive[i])
             continue;
         int vis[OR_MAX_VIEWS];
-        const int m = decode_mask(p[i].vis, vis);
+        const int m = or_fvis(s, &p[i], vis);
         double X[3];
         get_pos(&p[i], X);
         for (int k = 0; k < m; ++k) {
@@ -1114,7 +1125,7 @@ int or_filter_patches(const or_scene *s, const or_patch *p, int64_t n, int passe
         or_build_front(s, g, p, n, alive, front, cells);
         for (int64_t i = 0; i < n; ++i) {
             int vis[OR_MAX_VIEWS];
-            const int m = decode_mask(p[i].vis, vis);
+            const int m = or_fvis(s, &p[i], vis);
             double occ = 0.0;
             for (int k = 0; k < m; ++k) {
                 int64_t row, col;
@@ -1140,7 +1151,7 @@ int or_filter_patches(const or_scene *s, const or_patch *p, int64_t n, int passe
                 continue;
             }
             int vis[OR_MAX_VIEWS];
-            const int m = decode_mask(p[i].vis, vis);
+            const int m = or_fvis(s, &p[i], vis);
             int total = 0, near = 0;
             for (int k = 0; k < m; ++k) {
                 int64_t row, col;

@@ -381,7 +381,7 @@ def test_densify_on_pyramid_level_bit_exact(orc, level):
 def test_filter_bit_exact(orc, passes):
     """dp_filter_patches (front map by atomicMin, one thread per patch) equals
     the oracle's or_filter_patches on a densify result, with planted occluders."""
-    from test_filter_cpu import with_occluders
+    from filter_ref import with_occluders
 
     sc = scene("hf6")
     S = orc.Scene(sc.P, sc.imgs)
