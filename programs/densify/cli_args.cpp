@@ -1,0 +1,181 @@
+#include "cli_args.h"
+
+#include <cstdio>
+#include <cstdlib>
+#include <initializer_list>
+
+void usage()
+{
+    std::fprintf(stderr,
+                 "usage: densify -i scene.json [--seeds seeds.xyz] [-s settings.json] [-o points.ply]\n"
+                 "               [--device N] [--max-pops N] [--level L] [--filter] [--check-only]\n"
+                 "               [--iterations N]  (1..16 rounds of expansion then filter, each round\n"
+                 "                             re-expanding from the previous round's survivors with the\n"
+                 "                             store resident on the device; N > 1 implies --filter)\n"
+                 "               [--features N] [--fast-threshold T] [--epipolar-matching]\n"
+                 "               [--matcher knn|flann]  (MatcherType, matcher.h:12)\n"
+                 "               [--detector orb|akaze] [--akaze-threshold T]  (DetectorType, matcher.h:11)\n"
+                 "               [--gpus N]   (one context per GPU, generations partitioned by\n"
+                 "                             reference-view super-tile, accepted candidates\n"
+                 "                             all-gathered device to device; output identical to 1 GPU)\n"
+                 "               [--exchange auto|rccl|copy]  (auto: RCCL when every context has its\n"
+                 "                             own GPU, else peer copies; --multi: that protocol at 1 GPU)\n"
+                 "               [--replicate-below N]  (generations of fewer items run on every\n"
+                 "                             context, device-resident, no exchange; default 1024 x gpus)\n"
+                 "               [--mode parity|fast] [--fast-iters N] [--fast-gradient 0|1]\n"
+                 "                            (fast: the performance-mode refine -- LDS-staged gray\n"
+                 "                             tiles, fused CG -- for the seed stage and every expansion;\n"
+                 "                             gradient 1: analytic, 0: forward differences)\n"
+                 "               [--depth-maps DIR [--splat-scale S] [--depth-normals]]  (after the PLY:\n"
+                 "                             DIR/depth_%%04d.pfm, and normal_%%04d.pfm, of every view --\n"
+                 "                             the written patches as discs of radius S x rho, nearest\n"
+                 "                             per pixel: dp_render_maps)\n"
+                 "               [--fuse FILE.ply [--fuse-min-views K] [--fuse-depth-tol T]]  (after those:\n"
+                 "                             the depth and normal maps of every view, rendered and fused\n"
+                 "                             on the device into one cross-view-consistent cloud --\n"
+                 "                             dp_fuse_maps; K = 0..63 agreeing other views, default 2;\n"
+                 "                             T = relative depth tolerance, default 0.01)\n"
+                 "       densify --synthetic V,W,H,KIND --write-scene DIR\n");
+}
+
+Args::Args()
+{
+    dp_default_matcher_options(&matcher);
+    dp_default_fast_options(&fast);
+    fast.densify = 0;
+    dp_default_fuse_options(&fuse);
+}
+
+namespace {
+
+// The strict value parsers: the whole of `v` must be the value.  (Options read
+// with atoi / atof below take what those take: a leading number, else 0.)
+bool int_in_range(const std::string &v, long lo, long hi, long &out)
+{
+    char *end = nullptr;
+    out = std::strtol(v.c_str(), &end, 10);
+    return !v.empty() && !*end && out >= lo && out <= hi;
+}
+
+// a NaN fails both comparisons
+bool number_in_range(const std::string &v, double lo, double hi, double &out)
+{
+    char *end = nullptr;
+    out = std::strtod(v.c_str(), &end);
+    return !v.empty() && !*end && out >= lo && out <= hi;
+}
+
+// the index of `v` among `words`, -1 when it is none of them
+int one_of(const std::string &v, std::initializer_list<const char *> words)
+{
+    int k = 0;
+    for (const char *w : words) {
+        if (v == w)
+            return k;
+        ++k;
+    }
+    return -1;
+}
+
+// the options that take no value; false when `o` is not one of them
+bool set_flag(const std::string &o, Args &a)
+{
+    if (o == "--multi") a.force_multi = true;
+    else if (o == "--filter") a.do_filter = true;
+    else if (o == "--check-only") a.check_only = true;
+    else if (o == "--depth-normals") a.depth_normals = true;
+    else if (o == "--epipolar-matching") a.matcher.epipolar_matching = 1;
+    else return false;
+    return true;
+}
+
+} // namespace
+
+Parse parse_args(int argc, char **argv, Args &a, std::string &error)
+{
+    error.clear();
+    int fast_iters = -1, fast_gradient = -1; // < 0: the library's default
+    for (int i = 1; i < argc; ++i) {
+        const std::string o = argv[i];
+        if (o == "-h" || o == "--help")
+            return Parse::Help;
+        if (set_flag(o, a))
+            continue;
+        // every other option takes one value
+        if (i + 1 >= argc)
+            return Parse::UsageError;
+        const std::string v = argv[++i];
+        long k = 0;
+        double t = 0.0;
+        int w = 0;
+        if (o == "-i" || o == "--input") a.input = v;
+        else if (o == "-s" || o == "--settings") a.settings = v;
+        else if (o == "-o" || o == "--output") a.output = v;
+        else if (o == "--seeds") a.seeds_path = v;
+        else if (o == "--synthetic") a.synth = v;
+        else if (o == "--write-scene") a.scene_dir = v;
+        else if (o == "--depth-maps") a.depth_dir = v;
+        else if (o == "--fuse") a.fuse_path = v;
+        else if (o == "--device") a.device = std::atoi(v.c_str());
+        else if (o == "--gpus") a.gpus = std::atoi(v.c_str());
+        else if (o == "--replicate-below") a.replicate_below = std::atoll(v.c_str());
+        else if (o == "--max-pops") a.max_pops = std::atoll(v.c_str());
+        else if (o == "--level") a.level = std::atoi(v.c_str());
+        else if (o == "--features") a.matcher.n_features = std::atoi(v.c_str());
+        else if (o == "--fast-threshold") a.matcher.fast_threshold = std::atoi(v.c_str());
+        else if (o == "--akaze-threshold") a.matcher.akaze_threshold = (float)std::atof(v.c_str());
+        else if (o == "--fast-iters") fast_iters = std::atoi(v.c_str());
+        else if (o == "--fast-gradient") fast_gradient = std::atoi(v.c_str());
+        else if (o == "--iterations") {
+            a.iterations = std::atoi(v.c_str());
+            if (a.iterations < 1 || a.iterations > 16)
+                error = "--iterations expects 1..16";
+        } else if (o == "--splat-scale") {
+            a.splat_scale = std::atof(v.c_str());
+            if (!(a.splat_scale > 0.0))
+                error = "--splat-scale expects a positive number";
+        } else if (o == "--fuse-min-views") {
+            if (int_in_range(v, 0, 63, k))
+                a.fuse.min_views = (int32_t)k;
+            else
+                error = "--fuse-min-views expects 0..63";
+        } else if (o == "--fuse-depth-tol") {
+            if (number_in_range(v, 0.0, 3.0e38, t))
+                a.fuse.depth_tol = (float)t;
+            else
+                error = "--fuse-depth-tol expects a finite number >= 0";
+        } else if (o == "--exchange") {
+            a.exchange_mode = v;
+            if (one_of(v, {"auto", "rccl", "copy"}) < 0)
+                error = "--exchange expects auto, rccl or copy";
+        } else if (o == "--matcher") {
+            if ((w = one_of(v, {"knn", "flann"})) < 0)
+                error = "--matcher expects knn or flann";
+            else
+                a.matcher.matcher_type = w == 0 ? DP_MATCHER_KNN : DP_MATCHER_FLANN;
+        } else if (o == "--detector") {
+            if ((w = one_of(v, {"orb", "akaze"})) < 0)
+                error = "--detector expects orb or akaze";
+            else
+                a.matcher.detector_type = w == 0 ? DP_DETECTOR_ORB : DP_DETECTOR_AKAZE;
+        } else if (o == "--mode") {
+            if ((w = one_of(v, {"parity", "fast"})) < 0)
+                return Parse::UsageError;
+            a.fast.densify = w;
+        } else
+            return Parse::UsageError; // an option nobody knows
+        if (!error.empty())
+            return Parse::UsageError;
+    }
+    if (a.synth.empty() && a.input.empty())
+        return Parse::UsageError;
+    if (a.iterations > 1)
+        a.do_filter = true; // the filter is what tells the rounds apart
+    if (a.replicate_below < 0)
+        a.replicate_below = 1024 * (long long)a.gpus;
+    if (fast_iters >= 0)
+        a.fast.iters = fast_iters;
+    if (fast_gradient >= 0)
+        a.fast.gradient = fast_gradient;
+    return Parse::Run;
+}

@@ -1,0 +1,37 @@
+// cli_args.h -- the densify CLI's options and their parsing; no GPU dependency
+// (include/densepoints.h for the option structs and their defaults only).
+#pragma once
+
+#include "../../include/densepoints.h"
+
+#include <string>
+
+struct Args {
+    std::string input, settings, output = "points.ply", seeds_path;
+    std::string synth, scene_dir; // --synthetic V,W,H,KIND --write-scene DIR
+    int device = 0, gpus = 1;
+    bool force_multi = false; // --multi: the multi-GPU protocol at any --gpus
+    std::string exchange_mode = "auto";
+    long long replicate_below = -1; // parse_args resolves < 0 to 1024 x gpus
+    long long max_pops = -1;        // < 0: the settings' value
+    int level = 0;
+    bool check_only = false, do_filter = false;
+    int iterations = 1;
+    dp_matcher_options matcher; // MatcherOptions defaults (matcher.h:21-32), ORB::create(40000)
+    dp_fast_options fast;       // --mode fast: fast.densify = 1
+    std::string depth_dir, fuse_path;
+    double splat_scale = 1.0;
+    bool depth_normals = false;
+    dp_fuse_options fuse;
+
+    Args();
+};
+
+enum class Parse { Run, Help, UsageError };
+
+// Reads argv into `a`.  On UsageError `error` holds the message to print after
+// "densify: ", or is empty where the usage text is the message.
+Parse parse_args(int argc, char **argv, Args &a, std::string &error);
+
+// the usage text, to stderr
+void usage();

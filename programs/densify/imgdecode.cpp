@@ -15,17 +15,7 @@ int main(int argc, char **argv)
     }
     try {
         const dpio::Image im = dpio::load_image(argv[1]);
-        std::FILE *f = std::fopen(argv[2], "wb");
-        if (!f) {
-            std::fprintf(stderr, "cannot write %s\n", argv[2]);
-            return 1;
-        }
-        std::fprintf(f, "P6\n%d %d\n255\n", im.width, im.height);
-        for (size_t i = 0; i < im.bgr.size(); i += 3) {
-            const unsigned char rgb[3] = {im.bgr[i + 2], im.bgr[i + 1], im.bgr[i]};
-            std::fwrite(rgb, 1, 3, f);
-        }
-        std::fclose(f);
+        dpio::write_ppm(argv[2], im.width, im.height, im.bgr);
     } catch (const std::exception &e) {
         std::fprintf(stderr, "%s\n", e.what());
         return 1;

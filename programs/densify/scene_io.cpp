@@ -373,4 +373,34 @@ void write_ply(const std::string &path, const std::vector<CloudPoint> &pts)
         throw std::runtime_error("write failed: " + path);
 }
 
+void write_ppm(const std::string &path, int w, int h, const std::vector<uint8_t> &bgr)
+{
+    FILE *f = std::fopen(path.c_str(), "wb");
+    if (!f)
+        throw std::runtime_error("cannot write " + path);
+    std::fprintf(f, "P6\n%d %d\n255\n", w, h);
+    std::vector<uint8_t> rgb(bgr.size());
+    for (size_t i = 0; i < bgr.size(); i += 3) {
+        rgb[i] = bgr[i + 2];
+        rgb[i + 1] = bgr[i + 1];
+        rgb[i + 2] = bgr[i];
+    }
+    std::fwrite(rgb.data(), 1, rgb.size(), f);
+    std::fclose(f);
+}
+
+void write_pfm(const std::string &path, const float *px, int w, int h, int channels)
+{
+    std::FILE *f = std::fopen(path.c_str(), "wb");
+    if (!f)
+        throw std::runtime_error("cannot write " + path);
+    std::fprintf(f, "%s\n%d %d\n-1.0\n", channels == 3 ? "PF" : "Pf", w, h);
+    const size_t row = (size_t)w * (size_t)channels;
+    bool ok = true;
+    for (int y = h - 1; y >= 0 && ok; --y)
+        ok = std::fwrite(px + (size_t)y * row, sizeof(float), row, f) == row;
+    if (std::fclose(f) != 0 || !ok)
+        throw std::runtime_error("short write to " + path);
+}
+
 } // namespace dpio

@@ -1,6 +1,7 @@
 // scene_io.h -- host-side IO of the densify CLI: a small JSON reader (scene and
-// settings files), JPEG/PNG/PPM image decoding to BGR8, seed files and the ASCII
-// PLY writer.  Restates the reference's modules/io surface:
+// settings files), JPEG/PNG/PPM image decoding to BGR8, seed files, the ASCII
+// PLY writer and the PPM/PFM image writers.  Restates the reference's
+// modules/io surface:
 //   scene JSON  modules/io/json_reader.cpp:9-28 ({"imagesPath", "views": [{
 //               "filename", "projectionMatrix": 3x4}]})
 //   images      cv::imread BGR8 (modules/core/types.cpp:7-11)
@@ -73,5 +74,11 @@ struct CloudPoint {
 
 // ASCII PLY exactly as PrintCloud writes it (%g floats, uchar colours)
 void write_ply(const std::string &path, const std::vector<CloudPoint> &pts);
+
+// ---- image writers ----------------------------------------------------------
+// binary PPM (P6, RGB) of a BGR8 image
+void write_ppm(const std::string &path, int w, int h, const std::vector<uint8_t> &bgr);
+// little-endian PFM ("Pf" 1 channel, "PF" 3), rows bottom-up as the format requires
+void write_pfm(const std::string &path, const float *px, int w, int h, int channels);
 
 } // namespace dpio

@@ -128,6 +128,68 @@ def test_bad_inputs_fail_loudly(tmp_path, scene_dir):
     assert run(check=False).returncode == 2  # no arguments: usage
 
 
+def test_usage_errors_and_help_exit_codes():
+    """an option whose value is missing and an unknown flag: the usage text and
+    exit code 2; --synthetic without --write-scene: a message and exit code 1;
+    -h: the usage text on stderr and exit code 0"""
+    for bad in (("-i",), ("--no-such-flag",)):
+        r = run(*bad, check=False)
+        assert r.returncode == 2 and r.stderr.startswith("usage: densify -i scene.json") and r.stdout == ""
+    r = run("--synthetic", "2,32,24,0", check=False)
+    assert r.returncode == 1 and r.stderr == "densify: --synthetic needs --write-scene DIR\n" and r.stdout == ""
+    r = run("-h", check=False)
+    assert r.returncode == 0 and r.stderr.startswith("usage: densify -i scene.json") and r.stdout == ""
+
+
+@pytest.mark.gpu
+def test_cli_level_1_ply_equals_python_path(scene_dir, tmp_path):
+    """densify --level 1: the context set-up's pyramid branch (dp_build_pyramid(2),
+    dp_set_level(1)); the PLY equals write_ply of the same calls made through
+    the Python Engine, byte for byte."""
+    import densepoints_amd as dp
+    from densepoints_amd.pmvs import write_ply
+
+    out = tmp_path / "points.ply"
+    res = json.loads(run("-i", os.path.join(scene_dir, "scene.json"), "--seeds",
+                         os.path.join(scene_dir, "seeds.xyz"), "--level", "1", "-o", str(out)).stdout)
+    cfg = synth.config(4, 160, 120, 1)
+    P = synth.cameras(cfg)
+    with dp.Engine(device=0) as eng:
+        eng.set_views([dp.View(P[v], synth.render_host(cfg, P, v)) for v in range(4)])
+        eng.build_pyramid(2)
+        eng.set_level(1)
+        patches, st = eng.densify(synth.seeds(cfg, P))
+    assert res["patches"] == len(patches) > 0
+    ref = tmp_path / "python.ply"
+    write_ply(str(ref), patches)
+    assert out.read_bytes() == ref.read_bytes()
+    full = tmp_path / "level0.ply"
+    run("-i", os.path.join(scene_dir, "scene.json"), "--seeds", os.path.join(scene_dir, "seeds.xyz"), "-o", str(full))
+    assert out.read_bytes() != full.read_bytes()  # the level took effect
+
+
+@pytest.mark.gpu
+def test_cli_missing_device_exits_1(scene_dir):
+    """a device that does not exist: dp_ctx_create's argument error, returned
+    after the scene is loaded and before any kernel runs"""
+    r = run("-i", os.path.join(scene_dir, "scene.json"), "--seeds", os.path.join(scene_dir, "seeds.xyz"),
+            "--device", "9999", check=False)
+    assert r.returncode == 1 and "dp_ctx_create failed" in r.stderr and r.stdout == ""
+
+
+@pytest.mark.gpu
+def test_cli_rccl_on_a_shared_device_exits_1(scene_dir):
+    """--exchange rccl with two contexts wrapped onto one device: the exchange
+    refuses before any kernel runs, and both contexts are released"""
+    from densepoints_amd._native import lib
+
+    if lib.dp_device_count() != 1:
+        pytest.skip("--gpus 2 wraps onto one device only where one device is exposed")
+    r = run("-i", os.path.join(scene_dir, "scene.json"), "--seeds", os.path.join(scene_dir, "seeds.xyz"),
+            "--gpus", "2", "--exchange", "rccl", "--device", "0", check=False)
+    assert r.returncode == 1 and "--exchange rccl needs one device per context" in r.stderr
+
+
 @pytest.mark.gpu
 def test_cli_densify_ply_equals_oracle(scene_dir, tmp_path, orc):
     from densepoints_amd.pmvs import write_ply
