@@ -33,7 +33,7 @@ constexpr int kMapChunk = DP_MAP_CHUNK; // views whose window maps are built per
 // registers only hold short-lived values (the evaluation is fp64-heavy).
 struct WaveLds {
     // first: the texel loop addresses these with ds_read2 immediate offsets
-    double rowt[64][3];                         // per pass: window rows X0, Y0, W0/32 of slot j at j*(64/G)
+    double rowt[64][3];                         // per pass: window rows X0, Y0, W0/32 of slot j at j*(64/G) (G = 2: per 16-lane quarter)
     double colt[64][3];                         // per pass: window columns m0*x, m3*x, m6*x/32 (same slots)
     dpg::TexMap map[kMapChunk];                 // window maps of the current view chunk
     uint64_t roi[kMapChunk];                    // global address of each map's ROI origin
@@ -337,39 +337,85 @@ static_assert(kTexPerLane % 2 == 0, "texels are packed in u16 pairs");
 // selector that packs the two grays into u16 halves -- a dead texel (t >= N,
 // which re-loads texel N-1's address) gets a zero half, so it drops out of
 // every moment without a mask.
-struct TexDesc {
+template <int G>
+struct TexDescT {
     uint32_t ra[kTexPerLane], ca[kTexPerLane];
     uint32_t sel[kTexPerLane / 2];
     uint32_t anc; // LDS byte address of the lane's first texture-0 pair (L.anchor[anchor_slot(0, g)])
+    __device__ __forceinline__ uint32_t row(int i) const { return ra[i]; }
+    __device__ __forceinline__ uint32_t col(int i) const { return ca[i]; }
+};
+
+// G = 2 (two views of 32 lanes per narrow pass) also runs wide passes: four
+// views of kWideLP = 16 lanes, eight texels per lane t = g16 + 16 k, sampled
+// as two batches of four.  Narrow lane g32 = g16 + 16 b owns t = g32 + 32 i,
+// which are the wide lane's texels k = b + 2 i: its "own" batch (entries
+// 0..3); the texels of the other parity are entries 4..7.  One descriptor set
+// serves both pass shapes because every pass lays its tables out per 16-lane
+// quarter (views_pass fills a narrow slot's view into both of its quarters).
+// Row and column address share a register (both below 64 KiB), unpacked at use.
+constexpr int kWideLP = 16;
+template <>
+struct TexDescT<2> {
+    uint32_t rc[2 * kTexPerLane]; // row address | column address << 16
+    uint32_t sel[kTexPerLane];    // pair selectors: own batch 0..1, other batch 2..3
+    uint32_t anc;                 // &L.anchor[g32]: the own batch's first texture-0 pair
+    __device__ __forceinline__ uint32_t row(int i) const { return rc[i] & 0xffffu; }
+    __device__ __forceinline__ uint32_t col(int i) const { return rc[i] >> 16; }
 };
 
 template <int G>
-__device__ __forceinline__ TexDesc make_texdesc(const WaveLds &L, int cell)
+__device__ __forceinline__ TexDescT<G> make_texdesc(const WaveLds &L, int cell)
 {
-    constexpr int LP = kWave / G;
     const int lane = lane_id();
-    const int j = lane / LP, g = lane & (LP - 1);
     const int N = cell * cell;
     const uint32_t rb = lds_addr(&L.rowt[0][0]), cb = lds_addr(&L.colt[0][0]);
-    TexDesc td;
+    TexDescT<G> td;
+    if constexpr (G == 2) {
+        static_assert(sizeof(WaveLds) * kWavesPerBlock <= 65536, "LDS addresses fit 16 bits");
+        const int q16 = lane & ~(kWideLP - 1), g = lane & (kWideLP - 1), b = (lane / kWideLP) & 1;
 #pragma unroll
-    for (int i = 0; i < kTexPerLane; ++i) {
-        const int tl = g + LP * i;
-        const int t = tl < N ? tl : N - 1; // dead texels re-load a live address
-        const int py = t / cell, px = t - py * cell;
-        td.ra[i] = rb + (uint32_t)(j * (64 / G) + py) * (uint32_t)sizeof(double[3]);
-        td.ca[i] = cb + (uint32_t)(j * (64 / G) + px) * (uint32_t)sizeof(double[3]);
-        // opaque: keeps the whole address in one VGPR (no per-texel base add)
-        asm volatile("" : "+v"(td.ra[i]), "+v"(td.ca[i]));
-    }
+        for (int e = 0; e < 2 * kTexPerLane; ++e) {
+            const int par = e < kTexPerLane ? b : 1 - b;
+            const int tl = g + kWideLP * (par + 2 * (e % kTexPerLane));
+            const int t = tl < N ? tl : N - 1; // dead texels re-load a live address
+            const int py = t / cell, px = t - py * cell;
+            const uint32_t ra = rb + (uint32_t)(q16 + py) * (uint32_t)sizeof(double[3]);
+            const uint32_t ca = cb + (uint32_t)(q16 + px) * (uint32_t)sizeof(double[3]);
+            td.rc[e] = ra | (ca << 16);
+            asm volatile("" : "+v"(td.rc[e]));
+        }
 #pragma unroll
-    for (int p = 0; p < kTexPerLane / 2; ++p) {
-        // gray of texel 2p (bits 16-23 of its sum) -> bits 0-7, of texel 2p+1 -> bits 16-23
-        const bool l0 = g + LP * (2 * p) < N, l1 = g + LP * (2 * p + 1) < N;
-        td.sel[p] = 0x0c000c00u | (l0 ? 0x02u : 0x0cu) | ((l1 ? 0x06u : 0x0cu) << 16);
+        for (int p = 0; p < kTexPerLane; ++p) {
+            const int par = p < kTexPerLane / 2 ? b : 1 - b;
+            const int i0 = 2 * (p % (kTexPerLane / 2));
+            const bool l0 = g + kWideLP * (par + 2 * i0) < N, l1 = g + kWideLP * (par + 2 * (i0 + 1)) < N;
+            td.sel[p] = 0x0c000c00u | (l0 ? 0x02u : 0x0cu) | ((l1 ? 0x06u : 0x0cu) << 16);
+        }
+        td.anc = lds_addr(&L.anchor[lane & 31]);
+        asm volatile("" : "+v"(td.anc));
+    } else {
+        constexpr int LP = kWave / G;
+        const int j = lane / LP, g = lane & (LP - 1);
+#pragma unroll
+        for (int i = 0; i < kTexPerLane; ++i) {
+            const int tl = g + LP * i;
+            const int t = tl < N ? tl : N - 1; // dead texels re-load a live address
+            const int py = t / cell, px = t - py * cell;
+            td.ra[i] = rb + (uint32_t)(j * (64 / G) + py) * (uint32_t)sizeof(double[3]);
+            td.ca[i] = cb + (uint32_t)(j * (64 / G) + px) * (uint32_t)sizeof(double[3]);
+            // opaque: keeps the whole address in one VGPR (no per-texel base add)
+            asm volatile("" : "+v"(td.ra[i]), "+v"(td.ca[i]));
+        }
+#pragma unroll
+        for (int p = 0; p < kTexPerLane / 2; ++p) {
+            // gray of texel 2p (bits 16-23 of its sum) -> bits 0-7, of texel 2p+1 -> bits 16-23
+            const bool l0 = g + LP * (2 * p) < N, l1 = g + LP * (2 * p + 1) < N;
+            td.sel[p] = 0x0c000c00u | (l0 ? 0x02u : 0x0cu) | ((l1 ? 0x06u : 0x0cu) << 16);
+        }
+        td.anc = lds_addr(&L.anchor[g]);
+        asm volatile("" : "+v"(td.anc));
     }
-    td.anc = lds_addr(&L.anchor[g]);
-    asm volatile("" : "+v"(td.anc));
     return td;
 }
 
@@ -398,7 +444,7 @@ __device__ __forceinline__ void texel_coord_d(uint32_t ra, uint32_t ca, int32_t 
 // slot's view has the row pitch upitch (pixels), so the lower-row taps use the
 // SGPR base a.img_base + 4*upitch.
 template <int G, bool kAnchor, bool kNarrow, bool kUniPitch>
-__device__ __forceinline__ void group_sample_safe(const RefineArgs &a, WaveLds &L, const TexDesc &td, int j,
+__device__ __forceinline__ void group_sample_safe(const RefineArgs &a, WaveLds &L, const TexDescT<G> &td, int j,
                                                   uint64_t roi, int pitch, int upitch, int wm32, int hm32, int &s,
                                                   int &ss, int &sx)
 {
@@ -408,7 +454,7 @@ __device__ __forceinline__ void group_sample_safe(const RefineArgs &a, WaveLds &
 #pragma unroll
     for (int i = 0; i < kTexPerLane; ++i) {
         int32_t ix, iy;
-        texel_coord_d(td.ra[i], td.ca[i], ix, iy);
+        texel_coord_d(td.row(i), td.col(i), ix, iy);
         if (kNarrow)
             tl[i] = texel_fetch_n<kUniPitch>((gbyte_t)a.img_base, base1, (uint32_t)roi, pitch * 4, wm32, hm32, ix, iy);
         else
@@ -456,15 +502,15 @@ __device__ __forceinline__ void group_sample_safe(const RefineArgs &a, WaveLds &
 // point into slot 1's tables, filled with the same view), so every lane
 // samples two texels instead of four; the caller sums the moments over the
 // whole wave.  Texel pair j's texture-0 grays are the word anchor_slot(j, g).
-__device__ __forceinline__ void group_sample_split(const RefineArgs &a, const TexDesc &td, int j, uint64_t roi,
+__device__ __forceinline__ void group_sample_split(const RefineArgs &a, const TexDescT<2> &td, int j, uint64_t roi,
                                                    int pitch, int upitch, int wm32, int hm32, int &s, int &ss, int &sx)
 {
     typedef unsigned short us2 __attribute__((ext_vector_type(2)));
     static_assert(kTexPerLane == 4, "two texel pairs per lane");
     constexpr int LP = kWave / 2;
     const bool hi = j != 0;
-    const uint32_t ra0 = hi ? td.ra[2] : td.ra[0], ra1 = hi ? td.ra[3] : td.ra[1];
-    const uint32_t ca0 = hi ? td.ca[2] : td.ca[0], ca1 = hi ? td.ca[3] : td.ca[1];
+    const uint32_t rc0 = hi ? td.rc[2] : td.rc[0], rc1 = hi ? td.rc[3] : td.rc[1];
+    const uint32_t ra0 = rc0 & 0xffffu, ca0 = rc0 >> 16, ra1 = rc1 & 0xffffu, ca1 = rc1 >> 16;
     const uint32_t sel = hi ? td.sel[1] : td.sel[0];
     const gbyte_t base1 = (gbyte_t)a.img_base + (uint32_t)(upitch * 4);
     int32_t ix, iy;
@@ -492,7 +538,10 @@ struct Moments {
 // it does not add to the register pressure of the safe path.  Plain scalar
 // arguments only: a reference to the kernel arguments would force a private
 // copy of them.
-template <int G, bool kAnchor>
+// kWide (G = 4 lanes layout inside the G = 2 kernel, views_pass_wide): texel
+// i of lane g16 is texel i >> 1 of narrow lane g16 + 16 (i & 1), whose
+// texture-0 word it shares.
+template <int G, bool kAnchor, bool kWide = false>
 __device__ __attribute__((noinline)) Moments group_sample_clamped(WaveLds &L, int cell, int j, bool act, gpix_t roi,
                                                                   int pitch, int wm32, int hm32)
 {
@@ -513,7 +562,8 @@ __device__ __attribute__((noinline)) Moments group_sample_clamped(WaveLds &L, in
                 m.s += gv;
                 m.ss += gv * gv;
                 // u16 half (i & 1) of anchor pair word anchor_slot(i / 2, g)
-                uint16_t *ah = (uint16_t *)&L.anchor[anchor_slot<LP>(i >> 1, g)] + (i & 1);
+                uint16_t *ah = kWide ? (uint16_t *)&L.anchor[anchor_slot<2 * LP>(i >> 2, g + LP * (i & 1))] + ((i >> 1) & 1)
+                                     : (uint16_t *)&L.anchor[anchor_slot<LP>(i >> 1, g)] + (i & 1);
                 if (kAnchor && j == 0)
                     *ah = (uint16_t)gv;
                 else
@@ -526,13 +576,137 @@ __device__ __attribute__((noinline)) Moments group_sample_clamped(WaveLds &L, in
     return m;
 }
 
+// Moment sums of one packed gray pair against its texture-0 pair
+__device__ __forceinline__ void pair_moments(uint32_t gg, uint32_t aa, uint32_t &us, uint32_t &uss, uint32_t &usx)
+{
+    typedef unsigned short us2 __attribute__((ext_vector_type(2)));
+    const us2 ones = {1, 1};
+    const us2 vg = __builtin_bit_cast(us2, gg);
+    us = __builtin_amdgcn_udot2(vg, ones, us, false);
+    uss = __builtin_amdgcn_udot2(vg, vg, uss, false);
+    usx = __builtin_amdgcn_udot2(vg, __builtin_bit_cast(us2, aa), usx, false);
+}
+
+// The wide pass of the G = 2 kernel (narrow addressing, safe windows): four
+// views of kWideLP lanes, each lane sampling its eight texels as two batches
+// of four -- gather four, consume, gather four, consume -- so a pass keeps as
+// many loads in flight as a narrow one.  Batch 0 is the lane's own texels
+// (those it owns in a narrow pass), batch 1 the other parity (TexDescT<2>);
+// the texture-0 pairs are the words narrow lanes g16 + 16 * parity use, so
+// narrow, split and wide passes of one evaluation share L.anchor.  kAnchor:
+// slot 0 is texture 0; its two batches reach the other slots by ds_bpermute
+// after the second batch (lanes of odd quarters run the parities in the
+// opposite order, hence the select) and go to LDS for the later passes.
+template <bool kAnchor, bool kUniPitch>
+__device__ __forceinline__ void group_sample_wide(const RefineArgs &a, const TexDescT<2> &td, int j, uint32_t roi,
+                                                  int pitch, int upitch, int wm32, int hm32, int &s, int &ss, int &sx)
+{
+    static_assert(kTexPerLane == 4, "two texel pairs per batch");
+    const gbyte_t base1 = (gbyte_t)a.img_base + (uint32_t)(upitch * 4);
+    const int lane = lane_id();
+    const bool odd = (lane & kWideLP) != 0;
+    // the other batch's pairs: narrow lane g32 ^ 16
+    const uint32_t anc1 = odd ? td.anc - 4u * kWideLP : td.anc + 4u * kWideLP;
+    uint32_t us = 0, uss = 0, usx = 0;
+    uint32_t keep[kTexPerLane / 2];
+#pragma unroll
+    for (int b = 0; b < 2; ++b) {
+        TexelLoad tl[kTexPerLane];
+#pragma unroll
+        for (int i = 0; i < kTexPerLane; ++i) {
+            int32_t ix, iy;
+            texel_coord_d(td.row(kTexPerLane * b + i), td.col(kTexPerLane * b + i), ix, iy);
+            tl[i] = texel_fetch_n<kUniPitch>((gbyte_t)a.img_base, base1, roi, pitch * 4, wm32, hm32, ix, iy);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+#pragma unroll
+        for (int p = 0; p < kTexPerLane / 2; ++p) {
+            const uint32_t r0 = texel_gray_hi(tl[2 * p]);
+            const uint32_t r1 = texel_gray_hi(tl[2 * p + 1]);
+            const uint32_t gg = __builtin_amdgcn_perm(r1, r0, td.sel[(kTexPerLane / 2) * b + p]);
+            if (kAnchor) {
+                if (b == 0) {
+                    keep[p] = gg;
+                } else {
+                    const int src = (lane & (kWideLP - 1)) << 2; // slot 0's lane g16
+                    const uint32_t x0 = (uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)keep[p]); // parity 0
+                    const uint32_t x1 = (uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)gg);      // parity 1
+                    pair_moments(keep[p], odd ? x1 : x0, us, uss, usx);
+                    pair_moments(gg, odd ? x0 : x1, us, uss, usx);
+                    if (j == 0) {
+                        *(lds_u32_t)(uintptr_t)(td.anc + 4u * (uint32_t)(p * 32)) = keep[p];
+                        *(lds_u32_t)(uintptr_t)(anc1 + 4u * (uint32_t)(p * 32)) = gg;
+                    }
+                }
+            } else {
+                const uint32_t aa = *(lds_u32_t)(uintptr_t)((b ? anc1 : td.anc) + 4u * (uint32_t)(p * 32));
+                pair_moments(gg, aa, us, uss, usx);
+            }
+        }
+        // the second batch's gathers start after the first is consumed
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    s = (int)us;
+    ss = (int)uss;
+    sx = (int)usx;
+}
+
+// One wide pass: the four chunk slots in q (all present; with kAnchor, pass
+// slot 0 is texture 0), moments into L.mom[slot] as views_pass does.
+template <bool kAnchor>
+__device__ __forceinline__ void views_pass_wide(const RefineArgs &a, WaveLds &L, const TexDescT<2> &td, uint64_t q,
+                                                int &sa, int &saa)
+{
+    constexpr int LP = kWideLP;
+    const int lane = lane_id();
+    const int cell = a.cell;
+    const int j = (int)((uint32_t)lane / (uint32_t)LP);
+    const int slot = pick8(j, q);
+    {
+        const int r = lane & (LP - 1);
+        if (r < cell)
+            fill_tables(L, lane & ~(LP - 1), L.map[slot], r);
+    }
+    const int wm32 = (L.map[slot].w - 1) * 32, hm32 = (L.map[slot].h - 1) * 32;
+    const bool all_safe = __ballot(L.map[slot].safe == 0) == 0ull;
+    const int pitch = L.pitch[slot];
+    const int upitch = uni(pitch);
+    const bool uni_pitch = __ballot(pitch != upitch) == 0ull;
+    const uint32_t roi = (uint32_t)L.roi[slot]; // byte offset from a.img_base
+    wave_sync();
+    int s = 0, ss = 0, sx = 0;
+    if (all_safe) {
+        if (uni_pitch)
+            group_sample_wide<kAnchor, true>(a, td, j, roi, pitch, upitch, wm32, hm32, s, ss, sx);
+        else
+            group_sample_wide<kAnchor, false>(a, td, j, roi, pitch, upitch, wm32, hm32, s, ss, sx);
+    } else {
+        const Moments mm = group_sample_clamped<kWave / LP, kAnchor, true>(L, cell, j, true, (gpix_t)(a.img_base + roi),
+                                                                         pitch, wm32, hm32);
+        s = mm.s;
+        ss = mm.ss;
+        sx = mm.sx;
+    }
+    group_total3<kWave / LP>(s, ss, sx); // row_shr steps only: the total of slot j in lane 16 j + 15
+    if (kAnchor) {
+        sa = __builtin_amdgcn_readlane(s, LP - 1);
+        saa = __builtin_amdgcn_readlane(ss, LP - 1);
+    }
+    if ((lane & (LP - 1)) == LP - 1 && !(kAnchor && j == 0)) {
+        L.mom[slot][0] = s;
+        L.mom[slot][1] = ss;
+        L.mom[slot][2] = sx;
+    }
+    wave_sync();
+}
+
 // Integer moments of up to G views (chunk slots in q; with kAnchor, pass slot
 // 0 is texture 0 and its Sa, Saa are returned in sa/saa) into L.mom[slot].
 // kSplit (G = 2, not the anchor pass, narrow addressing): q names the same
 // view in both slots -- group_sample_split's half-texel pass, moments summed
 // over the wave (the clamped fallback samples it on slot 0's lanes only).
 template <int G, bool kAnchor, bool kSplit = false>
-__device__ __forceinline__ void views_pass(const RefineArgs &a, WaveLds &L, const TexDesc &td, int base, uint64_t q, int &sa, int &saa)
+__device__ __forceinline__ void views_pass(const RefineArgs &a, WaveLds &L, const TexDescT<G> &td, int base, uint64_t q, int &sa, int &saa)
 {
     static_assert(!kSplit || (G == 2 && !kAnchor), "split passes: G = 2, no anchor");
     constexpr int LP = kWave / G;
@@ -546,9 +720,11 @@ __device__ __forceinline__ void views_pass(const RefineArgs &a, WaveLds &L, cons
     const int sl = act ? slot : pick8(0, q);
     // row/column tables: lane r of pass slot j fills row r and column r
     {
-        const int r = lane & (LP - 1);
+        // (G = 2: into both 16-lane quarters of the slot, see TexDescT<2>)
+        constexpr int FP = G == 2 ? kWideLP : LP;
+        const int r = lane & (FP - 1);
         if (act && r < cell)
-            fill_tables(L, j * LP, L.map[slot], r);
+            fill_tables(L, lane & ~(FP - 1), L.map[slot], r);
     }
     // BORDER_REPLICATE clamp bounds of the ROI in 1/32 px (texel_fetch)
     const int wm32 = (L.map[sl].w - 1) * 32, hm32 = (L.map[sl].h - 1) * 32;
@@ -562,14 +738,16 @@ __device__ __forceinline__ void views_pass(const RefineArgs &a, WaveLds &L, cons
     const uint64_t roi = L.roi[sl]; // narrow: byte offset from a.img_base
     wave_sync();
     int s = 0, ss = 0, sx = 0;
-    if (kSplit && all_safe) {
-        group_sample_split(a, td, j, roi, pitch, upitch, wm32, hm32, s, ss, sx);
-    } else if (kSplit) {
-        const gpix_t roip = (gpix_t)(a.img_base + (uint32_t)roi);
-        const Moments mm = group_sample_clamped<G, false>(L, a.cell, j, act && j == 0, roip, pitch, wm32, hm32);
-        s = mm.s;
-        ss = mm.ss;
-        sx = mm.sx;
+    if constexpr (kSplit) {
+        if (all_safe) {
+            group_sample_split(a, td, j, roi, pitch, upitch, wm32, hm32, s, ss, sx);
+        } else {
+            const gpix_t roip = (gpix_t)(a.img_base + (uint32_t)roi);
+            const Moments mm = group_sample_clamped<G, false>(L, a.cell, j, act && j == 0, roip, pitch, wm32, hm32);
+            s = mm.s;
+            ss = mm.ss;
+            sx = mm.sx;
+        }
     } else if (all_safe) {
         if (a.narrow && uni_pitch)
             group_sample_safe<G, kAnchor, true, true>(a, L, td, j, roi, pitch, upitch, wm32, hm32, s, ss, sx);
@@ -602,9 +780,30 @@ __device__ __forceinline__ void views_pass(const RefineArgs &a, WaveLds &L, cons
 
 // all valid views of chunk bits `todo`, G at a time (texture 0 first if kAnchor)
 template <int G>
-__device__ __forceinline__ void views_all(const RefineArgs &a, WaveLds &L, const TexDesc &td, int base, uint64_t todo, bool anchor, int &sa, int &saa)
+__device__ __forceinline__ void views_all(const RefineArgs &a, WaveLds &L, const TexDescT<G> &td, int base, uint64_t todo, bool anchor, int &sa, int &saa)
 {
     bool first = anchor;
+    if constexpr (G == 2) {
+        // wide passes while four slots are full (an empty slot would cost more
+        // texel work than a pass's set-up saves); the remainder -- three, two
+        // or one view -- goes through the narrow and split passes below.
+        // Wide passes use narrow addressing only.
+        while (a.narrow && __popcll(todo) + (first ? 1 : 0) >= 4) {
+            uint64_t q = 0;
+#pragma unroll
+            for (int s = 0; s < 4; ++s) {
+                if (s == 0 && first)
+                    continue; // pass slot 0 = chunk slot 0 (texture 0)
+                q |= (uint64_t)__builtin_ctzll(todo) << (8 * s);
+                todo &= todo - 1;
+            }
+            if (first)
+                views_pass_wide<true>(a, L, td, q, sa, saa);
+            else
+                views_pass_wide<false>(a, L, td, q, sa, saa);
+            first = false;
+        }
+    }
     while (todo || first) {
         uint64_t q = ~0ull;
         int i = 0;
@@ -620,14 +819,18 @@ __device__ __forceinline__ void views_all(const RefineArgs &a, WaveLds &L, const
                 q = (q & ~(0xffull << (8 * s))) | (b << (8 * s));
             }
         }
-        if (first) {
-            views_pass<G, true>(a, L, td, base, q, sa, saa);
-        } else if (G == 2 && (q >> 8 & 0xffull) == 0xffull && a.narrow) {
-            // one view left: split its texels over both slots
-            views_pass<2, false, true>(a, L, td, base, (q & ~0xff00ull) | ((q & 0xffull) << 8), sa, saa);
-        } else {
-            views_pass<G, false>(a, L, td, base, q, sa, saa);
+        bool split = false;
+        if constexpr (G == 2) {
+            if (!first && (q >> 8 & 0xffull) == 0xffull && a.narrow) {
+                // one view left: split its texels over both slots
+                views_pass<2, false, true>(a, L, td, base, (q & ~0xff00ull) | ((q & 0xffull) << 8), sa, saa);
+                split = true;
+            }
         }
+        if (first)
+            views_pass<G, true>(a, L, td, base, q, sa, saa);
+        else if (!split)
+            views_pass<G, false>(a, L, td, base, q, sa, saa);
         first = false;
     }
 }
@@ -827,7 +1030,7 @@ __device__ __forceinline__ double wave_ncc_finish(int N, int Sa, int Saa, const 
 // wavefront (texture 0 first, kept in LDS), each reduced to exact integer
 // moments with DPP.  Returns the number of scores; sets *degen on dx == 0.
 template <int G>
-__device__ __forceinline__ int wave_scores(const RefineArgs &a, WaveLds &L, const TexDesc &td, const double *nn, const double *pp, bool &degen)
+__device__ __forceinline__ int wave_scores(const RefineArgs &a, WaveLds &L, const TexDescT<G> &td, const double *nn, const double *pp, bool &degen)
 {
     const int lane = lane_id();
     STAMP_BEGIN;
@@ -901,7 +1104,7 @@ __device__ __forceinline__ int wave_scores(const RefineArgs &a, WaveLds &L, cons
 
 // functor calc (optimization_opencv.cpp:14-39): mean of (1 - NCC), 2 if none
 template <int G>
-__device__ __forceinline__ double wave_objective(const RefineArgs &a, WaveLds &L, const TexDesc &td, double x0, double x1, double x2, bool &degen)
+__device__ __forceinline__ double wave_objective(const RefineArgs &a, WaveLds &L, const TexDescT<G> &td, double x0, double x1, double x2, bool &degen)
 {
     double nn[3], pp[3];
     {
@@ -940,7 +1143,7 @@ __device__ __forceinline__ double pick_y(const double *yy, int i)
 // innerDownhillSimplex, tryNewPoint).  One objective call site; the simplex
 // lives in LDS.  Writes back the f32 pose into L.X / L.n.
 template <int G>
-__device__ __forceinline__ int wave_nelder_mead(const RefineArgs &a, WaveLds &L, const TexDesc &td, bool &degen)
+__device__ __forceinline__ int wave_nelder_mead(const RefineArgs &a, WaveLds &L, const TexDescT<G> &td, bool &degen)
 {
     const double step[3] = {DP_KARG(RefineArgs, double, opt.nm_step[0]), DP_KARG(RefineArgs, double, opt.nm_step[1]),
                             DP_KARG(RefineArgs, double, opt.nm_step[2])};
@@ -1100,7 +1303,7 @@ __device__ __forceinline__ int wave_nelder_mead(const RefineArgs &a, WaveLds &L,
 // Optimization::FilterByErrorMeasurement (optimization.cpp:98-132) with the
 // off-by-one erase: score k (texture k+1) < thr removes ORIGINAL index k.
 template <int G>
-__device__ __forceinline__ bool wave_filter(const RefineArgs &a, WaveLds &L, const TexDesc &td, float &score, bool &degen)
+__device__ __forceinline__ bool wave_filter(const RefineArgs &a, WaveLds &L, const TexDescT<G> &td, float &score, bool &degen)
 {
     const int lane = lane_id();
     int nv;
@@ -1210,7 +1413,7 @@ __global__ DP_REFINE_BOUNDS void refine_kernel(RefineArgs a)
     for (int c = 0; c < 8; ++c)
         L.stamp[c] = 0;
 #endif
-    const TexDesc td = make_texdesc<G>(L, a.cell);
+    const TexDescT<G> td = make_texdesc<G>(L, a.cell);
     const uint32_t gs = a.parents ? 4u : 1u;                     // LPT group size
     const int npos = a.order ? (int)(((uint32_t)n + gs - 1) / gs * gs) : n; // dequeue positions
     for (;;) {
