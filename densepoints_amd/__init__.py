@@ -27,6 +27,7 @@ from .pmvs import (  # noqa: F401
     Options,
     View,
     check_fuse_args,
+    check_mapref_args,
     empty_patches,
     mask_from_list,
     ncc_score,

@@ -192,6 +192,35 @@ FUSED_DTYPE = np.dtype(
 assert FUSED_DTYPE.itemsize == 40
 
 
+class DpMaprefOptions(ctypes.Structure):
+    """dp_mapref_options: the knobs of dp_refine_maps (include/densepoints.h)."""
+    _fields_ = [
+        ("window", ctypes.c_int32),
+        ("sweep", ctypes.c_int32),
+        ("step_px", ctypes.c_float),
+        ("reach", ctypes.c_int32 * 2),
+        ("max_sources", ctypes.c_int32),
+        ("top_k", ctypes.c_int32),
+        ("min_ncc", ctypes.c_float),
+        ("flags", ctypes.c_int32),
+    ]
+
+
+class DpMaprefStats(ctypes.Structure):
+    _fields_ = [
+        ("depth_pixels_in", ctypes.c_int64),
+        ("candidates", ctypes.c_int64),
+        ("source_scores", ctypes.c_int64),
+        ("kept", ctypes.c_int64),
+        ("filled", ctypes.c_int64),
+        ("moved", ctypes.c_int64),
+        ("refine_ms", ctypes.c_double),
+    ]
+
+
+MAPREF_KEEP_UNSCORED = 1
+
+
 class DpSynthConfig(ctypes.Structure):
     _fields_ = [
         ("n_views", ctypes.c_int32),
@@ -318,6 +347,9 @@ SIGNATURES = [
     ("dp_default_fuse_options", None, [_P]),
     ("dp_fuse_maps", _I, [_P, _P, _I, _P, _P, _P, _P, _P, _P]),
     ("dp_fuse_maps_device", _I, [_P, _P, _I, _P, _P, _P, _P, ctypes.c_int64, _P, _P, _P]),
+    ("dp_default_mapref_options", None, [_P]),
+    ("dp_refine_maps", _I, [_P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    ("dp_refine_maps_device", _I, [_P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     ("dp_last_kernel_ms", _I, [_P, _P]),
     ("dp_default_matcher_options", None, [_P]),
     ("dp_orb_pattern", _I, [_P]),

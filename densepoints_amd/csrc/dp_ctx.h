@@ -4,7 +4,7 @@
 // engine; dp_fast.hip: performance mode; dp_synth.hip: synthetic scenes and
 // probes; dp_seeds_capi.hip, dp_seeds_orb.hip, dp_seeds_akaze.hip: seed
 // generation (their own state is dp_seedgen.h); dp_render.hip: maps;
-// dp_fuse.hip: their fusion).  Every member that owns a device or pinned
+// dp_fuse.hip: their fusion; dp_mapref.hip: their refinement).  Every member that owns a device or pinned
 // allocation or an event has an owning type (dp_buf.h), so deleting the
 // context frees them; only the views and the pyramid (free_views) and the
 // stream, which must outlive them all, are released by hand.
@@ -115,6 +115,13 @@ struct dp_ctx {
     HostBuf<dp_fused_point> u_res;
     HostBuf<unsigned long long> u_hcount;
     Event u_e0, u_e1;
+    // dp_refine_maps: the view table, striped counters and their host copy,
+    // the host form's staged input and output planes, timing events
+    DevBuf<dpk::MaprefView> m_tab;
+    DevBuf<unsigned long long> m_count;
+    HostBuf<unsigned long long> m_hcount;
+    DevBuf<unsigned char> m_io;
+    Event m_e0, m_e1;
     HostBuf<dp_patch> result; // dp_densify / dp_densify_result output (pinned)
     // dp_densify_iterate: per iteration {evaluations, filter survivors} on the
     // device (read once, at the end) and the filters' timing events

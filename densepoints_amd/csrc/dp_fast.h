@@ -77,3 +77,7 @@ hipError_t launch_grad_q24_probe(const double *x, int n, int32_t *out);
 hipError_t launch_recip_probe(const float *x, int n, float *out);
 
 } // namespace dpk
+
+// the gray planes of the current level, built on demand exactly as the first
+// performance-mode call builds them (dp_fast.hip); used by dp_mapref.hip
+int dp_gray_planes(dp_ctx *c, std::vector<dpk::GrayPlane> &out);

@@ -100,6 +100,21 @@ int ensure_gray(dp_ctx *c)
 
 } // namespace
 
+int dp_gray_planes(dp_ctx *c, std::vector<dpk::GrayPlane> &out)
+{
+    int rc = ensure_gray(c);
+    if (rc != DP_OK)
+        return rc;
+    out.resize((size_t)c->V);
+    size_t off = 0;
+    for (int v = 0; v < c->V; ++v) {
+        const int pitch = gray_pitch(c->hv[v].W);
+        out[(size_t)v] = dpk::GrayPlane{(const __half *)c->gray_pool.p + off, c->hv[v].W, c->hv[v].H, pitch, 0};
+        off += (size_t)pitch * (size_t)c->hv[v].H;
+    }
+    return DP_OK;
+}
+
 int dp_fast_launch(dp_ctx *c, const dpk::RefineJob &job, hipStream_t s)
 {
     int rc = ensure_gray(c);

@@ -318,6 +318,34 @@ hipError_t launch_fuse_mask(const FuseArgs &a, unsigned gx, hipStream_t s);
 hipError_t launch_fuse_count(const FuseArgs &a, unsigned gx, hipStream_t s);
 hipError_t launch_fuse_emit(const FuseArgs &a, unsigned gx, hipStream_t s);
 
+// depth-map refinement (dp_mapref.hip; spec in include/densepoints.h, dp_refine_maps)
+constexpr int kMaprefMaxSources = 8;
+constexpr int kMaprefCounters = 6; // depth pixels in, candidates, source scores, kept, filled, moved
+constexpr int kMaprefStripes = 64; // each counter kept kMaprefStripes times (summed by the host)
+struct MaprefView { // one requested view; indexed wave-uniformly (scalar loads)
+    double P[12];
+    double A[9], det;       // adjugate and determinant of the left 3x3 of P
+    double C[3], xr[3];     // camera centre, unit x-axis
+    const float *depth;     // inputs: W x H, W x H x 3
+    const float *normal;
+    float *odepth;          // outputs, any may be null
+    float *onormal;
+    float *oscore;
+    int32_t *ochoice;
+    const uint16_t *gray;   // biased fp16 gray plane (0x6400 | gray), rows of gpitch
+    int32_t W, H, gpitch, nsrc;
+    int32_t src[kMaprefMaxSources]; // the source views as ranks into the table
+};
+struct MaprefArgs {
+    const MaprefView *tab;
+    int32_t K, window, sweep, nreach; // nreach: the non-zero reaches, compacted into reach[]
+    int32_t reach[2], top_k, keep_unscored;
+    double step, min_ncc, dmin; // (double)step_px, (double)min_ncc, the NCC denominator floor
+    unsigned long long *count;  // kMaprefStripes x kMaprefCounters
+};
+// gx 16 x 16 tiles per view (the largest plane's), K views
+hipError_t launch_mapref(const MaprefArgs &a, unsigned gx, hipStream_t s);
+
 hipError_t launch_refine(const RefineArgs &a, hipStream_t s);
 hipError_t launch_pyr_down(const PyrPlane *d_src, const PyrPlane *d_dst, int V, int max_dw, int max_dh,
                            hipStream_t s);

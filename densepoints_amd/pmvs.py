@@ -36,6 +36,7 @@ __all__ = [
     "write_ply",
     "write_pfm",
     "check_fuse_args",
+    "check_mapref_args",
     "read_pfm",
     "empty_patches",
     "visible_list",
@@ -679,6 +680,150 @@ class Engine:
         return int(n.value), {name: getattr(st, name) for name, _ in N.DpFuseStats._fields_}
 
 
+    # ---- depth-map refinement (include/densepoints.h dp_refine_maps) ----
+    def refine_maps(self, depth, normal, views=None, sources=None, **options) -> dict:
+        """dp_refine_maps: one Jacobi pass over the depth and normal planes of
+        `views` (None = all), as render_maps returns them.  `sources`: per view a
+        list of source view ids (None = the nearest max_sources requested
+        views); options: the fields of dp_mapref_options (window, sweep, step_px,
+        reach, max_sources, top_k, min_ncc, keep_unscored).  Returns {"views",
+        "depth", "normal", "score", "choice" (lists of planes), "stats"}."""
+        mo, vid, src = check_mapref_args(self.num_views(), views, sources, **options)
+        sizes = self.view_sizes(vid)
+
+        def planes(arrs, name, tail):
+            if arrs is None or len(arrs) != len(vid):
+                raise ValueError("refine_maps: one %s plane per view" % name)
+            out = [np.ascontiguousarray(a, dtype=np.float32) for a in arrs]
+            for a, (w, h) in zip(out, sizes):
+                if a.shape != (h, w) + tail:
+                    raise ValueError("refine_maps: a %s plane of shape %s, expected %s" % (name, a.shape, (h, w) + tail))
+            return out, (ctypes.c_void_p * len(vid))(*[a.ctypes.data for a in out])
+
+        depth, dtab = planes(depth, "depth", ())
+        normal, ntab = planes(normal, "normal", (3,))
+        out = {"views": [int(v) for v in vid],
+               "depth": [np.zeros((h, w), np.float32) for w, h in sizes],
+               "normal": [np.zeros((h, w, 3), np.float32) for w, h in sizes],
+               "score": [np.zeros((h, w), np.float32) for w, h in sizes],
+               "choice": [np.zeros((h, w), np.int32) for w, h in sizes]}
+
+        def table(key):
+            return (ctypes.c_void_p * len(vid))(*[a.ctypes.data for a in out[key]])
+
+        st = N.DpMaprefStats()
+        self._check(lib.dp_refine_maps(self._ctx, ptr(vid), len(vid), ctypes.byref(mo), ptr(src), dtab, ntab,
+                                       table("depth"), table("normal"), table("score"), table("choice"),
+                                       ctypes.byref(st)))
+        out["stats"] = {name: getattr(st, name) for name, _ in N.DpMaprefStats._fields_}
+        return out
+
+    def refine_maps_device(self, views, d_depth, d_normal, d_depth_out=None, d_normal_out=None, d_score_out=None,
+                           d_choice_out=None, sources=None, stream: int | None = None, stats: bool = True,
+                           **options) -> dict | None:
+        """dp_refine_maps_device: device planes (lists of device addresses, one
+        per entry of `views`; an output list or entry None or 0 = not wanted).
+        Queued on `stream`; waits only for the statistics (stats=False: no wait,
+        returns None)."""
+        mo, vid, src = check_mapref_args(self.num_views(), views, sources, **options)
+
+        def table(addrs, required):
+            if addrs is None:
+                if required:
+                    raise ValueError("refine_maps_device: depth and normal planes must be given")
+                return None
+            if len(addrs) != len(vid) or (required and not all(addrs)):
+                raise ValueError("refine_maps_device: one plane address per view")
+            return (ctypes.c_void_p * len(vid))(*[int(a) if a else None for a in addrs])
+
+        ins = [int(a) for a in list(d_depth or []) + list(d_normal or []) if a]
+        for outs in (d_depth_out, d_normal_out, d_score_out, d_choice_out):
+            if outs is not None and any(a and int(a) in ins for a in outs):
+                raise ValueError("refine_maps_device: an output plane is an input plane")
+        st = N.DpMaprefStats()
+        self._check(lib.dp_refine_maps_device(self._ctx, ptr(vid), len(vid), ctypes.byref(mo), ptr(src),
+                                              table(d_depth, True), table(d_normal, True), table(d_depth_out, False),
+                                              table(d_normal_out, False), table(d_score_out, False),
+                                              table(d_choice_out, False), ctypes.byref(st) if stats else None,
+                                              ctypes.c_void_p(stream) if stream else None))
+        return {name: getattr(st, name) for name, _ in N.DpMaprefStats._fields_} if stats else None
+
+
+MAPREF_DEFAULTS = dict(window=7, sweep=2, step_px=1.0, reach=(1, 4), max_sources=4, top_k=2, min_ncc=0.5,
+                       keep_unscored=False)
+
+
+def check_mapref_args(V: int, views=None, sources=None, **options):
+    """Argument validation of Engine.refine_maps[_device] (the limits of
+    dp_refine_maps, raised as ValueError before any device call); returns
+    (dp_mapref_options, view ids as int32, the sources table as K x max_sources
+    int32 or None)."""
+    unknown = set(options) - set(MAPREF_DEFAULTS)
+    if unknown:
+        raise ValueError("refine_maps: unknown options %s" % sorted(unknown))
+    o = dict(MAPREF_DEFAULTS, **options)
+
+    def number(x):
+        return isinstance(x, (int, float, np.integer, np.floating)) and not isinstance(x, bool)
+
+    def whole(x, lo, hi):
+        return number(x) and int(x) == x and lo <= int(x) <= hi
+
+    if not (whole(o["window"], 3, 11) and int(o["window"]) % 2 == 1):
+        raise ValueError("refine_maps: window must be odd and in 3..11")
+    if not whole(o["sweep"], 0, 8):
+        raise ValueError("refine_maps: sweep must be in 0..8")
+    if not (number(o["step_px"]) and np.isfinite(o["step_px"]) and o["step_px"] > 0):
+        raise ValueError("refine_maps: step_px must be finite and > 0")
+    reach = o["reach"]
+    if not (isinstance(reach, (tuple, list)) and len(reach) == 2 and all(whole(d, 0, 16) for d in reach)):
+        raise ValueError("refine_maps: reach must be two distances in 0..16")
+    if not whole(o["max_sources"], 1, 8):
+        raise ValueError("refine_maps: max_sources must be in 1..8")
+    if not whole(o["top_k"], 1, int(o["max_sources"])):
+        raise ValueError("refine_maps: top_k must be in 1..max_sources")
+    if not (number(o["min_ncc"]) and -1 <= o["min_ncc"] <= 1):
+        raise ValueError("refine_maps: min_ncc must be in -1..1")
+    vid = np.arange(V, dtype=np.int64) if views is None else np.asarray(list(views), dtype=np.int64)
+    if vid.ndim != 1 or not 1 <= len(vid) <= 64:
+        raise ValueError("refine_maps: 1..64 views")
+    if (vid < 0).any() or (vid >= V).any() or len(set(vid.tolist())) != len(vid):
+        raise ValueError("refine_maps: view ids must be unique and < %d" % V)
+    src = None
+    if sources is not None:
+        ms = int(o["max_sources"])
+        rows = [list(r) for r in sources]
+        if len(rows) != len(vid):
+            raise ValueError("refine_maps: one sources row per view")
+        src = np.full((len(vid), ms), -1, dtype=np.int32)
+        for k, row in enumerate(rows):
+            while row and row[-1] == -1:
+                row.pop()
+            if len(row) > ms:
+                raise ValueError("refine_maps: a sources row holds more than max_sources ids")
+            ids = [int(s) for s in row]
+            if any(s not in vid.tolist() or s == int(vid[k]) for s in ids) or len(set(ids)) != len(ids):
+                raise ValueError("refine_maps: a sources row must hold requested views other than its own, "
+                                 "without repeats")
+            src[k, :len(ids)] = ids
+    mo = N.DpMaprefOptions(int(o["window"]), int(o["sweep"]), float(o["step_px"]),
+                           (ctypes.c_int32 * 2)(int(reach[0]), int(reach[1])), int(o["max_sources"]), int(o["top_k"]),
+                           float(o["min_ncc"]), N.MAPREF_KEEP_UNSCORED if o["keep_unscored"] else 0)
+    return mo, np.ascontiguousarray(vid, dtype=np.int32), src
+
+
+def split_refine_args(who: str, refine, kw: dict):
+    """(passes, the dp_refine_maps options among kw, the rest of kw) for
+    PMVS.depth_maps / fused_cloud; the options need refine > 0"""
+    if isinstance(refine, bool) or int(refine) != refine or not 0 <= int(refine) <= 64:
+        raise ValueError("%s: refine must be a pass count in 0..64" % who)
+    names = set(MAPREF_DEFAULTS) | {"sources"}
+    mkw = {k: v for k, v in kw.items() if k in names}
+    if mkw and not refine:
+        raise ValueError("%s: %s given without refine > 0" % (who, sorted(mkw)))
+    return int(refine), mkw, {k: v for k, v in kw.items() if k not in names}
+
+
 def check_fuse_args(V: int, views, depth_tol: float, min_views: int, min_normal_cos: float, suppress: bool):
     """Argument validation of Engine.fuse_maps[_device] (the limits of
     dp_fuse_maps, raised as ValueError before any device call); returns
@@ -838,29 +983,52 @@ class PMVS:
     def get_point_cloud(self) -> np.ndarray:
         return self.patches
 
-    def depth_maps(self, **kw) -> dict:
+    def depth_maps(self, refine: int = 0, **kw) -> dict:
         """Per-view depth / index (and normal, score) maps of the last run()'s
         result -- the survivors after run(iterations=N) or filter_passes != 0 --
-        by Engine.render_maps, whose keyword arguments pass through."""
+        by Engine.render_maps, whose keyword arguments pass through.  refine = N
+        > 0 runs N passes of Engine.refine_maps on the rendered planes (its
+        options -- window, sweep, ..., sources -- pass through too): "depth",
+        "normal" and "score" are then the refined planes, "choice" the last
+        pass's, "index" still names the rendered patch, and "refine_stats" lists
+        each pass's statistics."""
         if not self._ran:
             raise ValueError("depth_maps: call run() first")
+        refine, mkw, kw = split_refine_args("depth_maps", refine, kw)
         with Engine(self.options, self.device) as eng:
             eng.set_views(self.views)
-            return eng.render_maps(self.patches, **kw)
+            if not refine:
+                return eng.render_maps(self.patches, **kw)
+            check_mapref_args(eng.num_views(), kw.get("views"), **mkw)
+            out = eng.render_maps(self.patches, **dict(kw, normals=True))
+            out["refine_stats"] = []
+            for _ in range(refine):
+                ref = eng.refine_maps(out["depth"], out["normal"], views=out["views"], **mkw)
+                for key in ("depth", "normal", "score", "choice"):
+                    out[key] = ref[key]
+                out["refine_stats"].append(ref["stats"])
+            return out
 
     def fused_cloud(self, views=None, splat_scale: float = 1.0, max_radius_px: int = 32, all_facing: bool = False,
-                    normals: bool = True, **fuse_kw) -> np.ndarray:
+                    normals: bool = True, refine: int = 0, **fuse_kw) -> np.ndarray:
         """The last run()'s result as a dense fused cloud (a FUSED_DTYPE array):
         its depth and normal maps rendered on the device (Engine.render_maps_device)
         and fused there (Engine.fuse_maps_device, whose keyword arguments pass
-        through) -- the planes never visit the host.  The statistics of both
-        calls are left in self.stats["render"] and self.stats["fused"]."""
+        through) -- the planes never visit the host.  refine = N > 0 runs N
+        passes of Engine.refine_maps_device between the two (its options pass
+        through; it needs normals).  The statistics of the calls are left in
+        self.stats["render"], self.stats["refine"] (a list) and self.stats["fused"]."""
         if not self._ran:
             raise ValueError("fused_cloud: call run() first")
+        refine, mkw, fuse_kw = split_refine_args("fused_cloud", refine, fuse_kw)
+        if refine and not normals:
+            raise ValueError("fused_cloud: refine needs normals")
         import torch
 
         with Engine(self.options, self.device) as eng:
             eng.set_views(self.views)
+            if refine:
+                check_mapref_args(eng.num_views(), views, **mkw)
             _, vid = check_fuse_args(eng.num_views(), views, fuse_kw.get("depth_tol", 0.01),
                                      fuse_kw.get("min_views", 2), fuse_kw.get("min_normal_cos", 0.5),
                                      fuse_kw.get("suppress", True))
@@ -875,6 +1043,18 @@ class PMVS:
                                          splat_scale=splat_scale, max_radius_px=max_radius_px, all_facing=all_facing)
             # an empty pixel is never emitted: the covered pixels bound the cloud
             cap = int(rst["covered_pixels"])
+            mst = []
+            for _ in range(refine):
+                depth2 = [torch.empty_like(t) for t in depth]
+                normal2 = [torch.empty_like(t) for t in normal]
+                torch.cuda.synchronize(dev)
+                mst.append(eng.refine_maps_device(vid, [t.data_ptr() for t in depth], [t.data_ptr() for t in normal],
+                                                  [t.data_ptr() for t in depth2], [t.data_ptr() for t in normal2],
+                                                  **mkw))
+                depth, normal = depth2, normal2
+                cap = int(mst[-1]["kept"])
+            if refine:
+                self.stats["refine"] = mst
             pts = torch.empty((max(cap, 1), FUSED_DTYPE.itemsize), dtype=torch.uint8, device=dev)
             torch.cuda.synchronize(dev)
             n, fst = eng.fuse_maps_device(vid, [t.data_ptr() for t in depth],

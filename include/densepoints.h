@@ -587,6 +587,134 @@ int dp_fuse_maps_device(dp_ctx *ctx, const int32_t *views, int n_views, const dp
                         const float *const *d_depth, const float *const *d_normal, dp_fused_point *d_points,
                         int64_t cap, int64_t *n_out, dp_fuse_stats *stats, void *stream);
 
+/* ---- depth-map refinement: per-pixel photometric choice among a few candidate
+ * planes, with hole filling and a confidence -------------------------------------
+ * No reference counterpart.  Every pixel of the requested views builds a short
+ * list of candidate planes (its own, a depth sweep of its own, its neighbours'),
+ * scores each against a few source views through the performance mode's sampler
+ * and keeps the best.  The call reads the input planes only and writes the
+ * output planes only (Jacobi), so the result depends on neither pixel order nor
+ * launch geometry; feeding the output back in propagates further.  All fp64
+ * arithmetic is one IEEE rounding per operation in exactly the order written
+ * (-ffp-contract=off); dot, row_r, project are dp_render_maps's, the view table
+ * (A, det), backproject and "is a depth" are dp_fuse_maps's.  backproject_d is
+ * backproject with an fp64 depth zd in place of (double)z.
+ *
+ * Inputs: views[0..K-1] (unique ids < V, 1 <= K <= 64) at the CURRENT level;
+ * per requested view, in the order of `views`, an f32 depth plane W x H and a
+ * 3 x f32 normal plane (both required); the level's P, W, H, the views' C and
+ * xr (dp_render_maps's xr_v) and the context's fp16 gray planes (dp_build_gray;
+ * built on demand as by the first performance-mode call); gray_v(x, y) is the
+ * 8-bit gray of view v.  `sources`: K rows of max_sources view ids, row k the
+ * source views of views[k] in order, -1 padded at the end; each id a requested
+ * view other than views[k], no repeats.  sources == NULL: row k = the other
+ * requested views s by ascending d2 = dot(e, e), e_j = C_s[j] - C_r[j] (ties to
+ * the lower view id), the first max_sources of them.
+ *
+ * Candidates of pixel (k, x, y), r = views[k], z = depth_r[y][x], n =
+ * normal_r[y][x] widened to fp64 (never renormalised); a pixel HAS A PLANE iff z
+ * is a depth and dot(n, n) > 0.  Candidate indices are fixed:
+ *   0            the pixel's own plane: X0 = backproject(r, x, y, z), normal n;
+ *                void unless the pixel has a plane;
+ *   1..2*sweep   hypotheses h = -sweep..-1, +1..+sweep in this order: (cu, cv) =
+ *                project(P_r, X0), (qu, qv) = project(P_r, X0 + xr_r), du = qu -
+ *                cu, dv = qv - cv, dx = sqrt(du*du + dv*dv); e_j = X0[j] - C_r[j],
+ *                len = sqrt(dot(e, e)); t = ((double)h * (double)step_px) / dx;
+ *                the plane through X_h[j] = X0[j] + (t * e_j) / len with normal n;
+ *                void unless the pixel has a plane, dx > 0 and len > 0;
+ *   then, for each non-zero reach[i] = d in the order i = 0, 1, four indices for
+ *                the offsets (-d, 0), (+d, 0), (0, -d), (0, +d): the plane of the
+ *                input pixel (x', y') = (x, y) + offset (X0 = backproject(r, x',
+ *                y', z'), normal n'); void unless (x', y') is inside the image
+ *                and has a plane.  A zero reach takes no indices.
+ * The plane (X0, n) as seen from r: m_j = (A[j]*n_0 + A[3+j]*n_1) + A[6+j]*n_2,
+ * c = det * dot(n, X0) + dot(m, (P[3], P[7], P[11])); its depth at pixel (u, v):
+ * zeta(u, v) = c / ((m_0*u + m_1*v) + m_2), its point there: backproject_d(r, u,
+ * v, zeta(u, v)).  zc = zeta(x, y), zf = (float)zc; the candidate is void unless
+ * zf is a depth (this rejects NaN, a zero or wrong-signed denominator, overflow).
+ *
+ * Score of a non-void candidate against source s (W_s, H_s its plane size), with
+ * Xc, Xi, Xj the plane's points at (x, y), (x+1, y), (x, y+1):
+ *   1. dc = row_2(P_s, Xc), di, dj the same; require dc > 0, di > 0, dj > 0;
+ *   2. (uc, vc) = (row_0/dc, row_1/dc) of Xc, (ui, vi), (uj, vj) of Xi, Xj with
+ *      their own divisors; U0 = (float)(32.0*uc), V0 = (float)(32.0*vc), Ui =
+ *      (float)(32.0*(ui - uc)), Vi = (float)(32.0*(vi - vc)), Uj, Vj the same
+ *      from (uj, vj): the first-order window map in 1/32 px;
+ *   3. h = (window - 1)/2; for the four corners (i, j) = (+-h, +-h): a = ((double)
+ *      U0 + (double)i*(double)Ui) + (double)j*(double)Uj, b the same from V;
+ *      require 0 <= a <= 32*(W_s - 1) and 0 <= b <= 32*(H_s - 1) (NaN fails);
+ *      otherwise the source is INVALID for this candidate;
+ *   4. sample (i, j), i, j = -h..h, exactly as the performance mode's: in fp32,
+ *      U = fmaf((float)j, Uj, fmaf((float)i, Ui, U0)) + 8388608.0f, clamped to
+ *      [8388608, 8388608 + 32*(W_s - 1)], iu = (int)(U - 8388608.0f), xs = iu >>
+ *      5, fx = iu & 31; yv, fy the same from V and H_s; the taps p00 = gray_s(xs,
+ *      yv), p01 = gray_s(min(xs+1, W_s-1), yv), p10 = gray_s(xs, min(yv+1,
+ *      H_s-1)), p11; b = ((32-fx)*(32-fy)*p00 + fx*(32-fy)*p01 + (32-fx)*fy*p10
+ *      + fx*fy*p11 + 32) >> 6, in 1/16 gray levels;
+ *   5. the reference sample a = 16 * gray_r(clamp(x+i, 0, W_r-1), clamp(y+j, 0,
+ *      H_r-1));
+ *   6. exact integer moments over the N = window^2 samples: Sa, Saa, Sb, Sbb,
+ *      Sab; num = N*Sab - Sa*Sb, va = N*Saa - Sa*Sa, vb = N*Sbb - Sb*Sb (exact
+ *      integers, each below 2^53); den = sqrt((double)va * (double)vb), dmin =
+ *      ((ncc_denom_min * 256.0) * N) * N (dp_options.ncc_denom_min, the floor of
+ *      DP_MODE_FAST_EVAL in these units); ncc = (double)num / (den > dmin ? den
+ *      : dmin).
+ * Candidate score: the ncc of its valid sources, sorted descending (equal values
+ * in source-list order), S = the first, S = S + the next, ... over the first
+ * top_k of them, score = S / (double)top_k.  With fewer than top_k valid sources
+ * the candidate is void.
+ *
+ * Selection: the non-void candidate of the greatest score wins, ties to the
+ * lowest index.  If score >= (double)min_ncc the pixel is KEPT: depth = zf of
+ * the winner, normal = the winner's stored f32 normal, score = (float)score,
+ * choice = its index.  Otherwise the pixel is empty: depth 0, normal 0, score 0,
+ * choice -1.  With DP_MAPREF_KEEP_UNSCORED a pixel whose z is a depth and that
+ * has no non-void candidate keeps its input depth and normal (bit for bit) with
+ * score 0 and choice -2.
+ *
+ * Outputs: per requested view depth f32, normal 3 x f32, score f32, choice int32
+ * planes; an array or an entry may be NULL.  Statistics, counted on the device:
+ * depth_pixels_in (pixels whose z is a depth), candidates (non-void), source_scores
+ * ((candidate, valid source) pairs scored, of candidates not void by their
+ * plane), kept, filled (kept, z not a depth), moved (kept, choice != 0);
+ * refine_ms = device time of the call's kernel.
+ * Host form: host planes.  Device form: device planes, everything queued on
+ * `stream` (NULL = the context's); it waits only for the statistics read, and
+ * not at all with stats == NULL.  mo NULL = the defaults, which are design
+ * choices that nobody has tuned.
+ * Errors (DP_E_ARG): window even or outside 3..11, sweep outside 0..8, step_px
+ * not > 0 or not finite, a reach outside 0..16, max_sources outside 1..8, top_k
+ * outside 1..max_sources, min_ncc outside -1..1, unknown flag bits; n_views
+ * outside 1..min(V, 64), a view id repeated or >= V, a singular left 3x3; a
+ * sources row with an id that is not requested, the row's own, repeated, below
+ * -1, or after a -1; depth or normal NULL or a NULL entry; an output plane
+ * pointer equal to an input plane pointer; no views set: DP_E_STATE. */
+#define DP_MAPREF_KEEP_UNSCORED 1
+typedef struct dp_mapref_options {
+    int32_t window;       /* 7    side of the scored window, reference pixels (odd, 3..11) */
+    int32_t sweep;        /* 2    depth hypotheses on each side of the own plane (0..8)    */
+    float step_px;        /* 1.0  sweep step in reference-pixel footprints (> 0)           */
+    int32_t reach[2];     /* 1, 4 distances of the propagation offsets (0..16, 0 = off)   */
+    int32_t max_sources;  /* 4    source views per reference view (1..8)                   */
+    int32_t top_k;        /* 2    best sources averaged into a score (1..max_sources)      */
+    float min_ncc;        /* 0.5  least score for a pixel to be kept (-1..1)               */
+    int32_t flags;        /* DP_MAPREF_* bits (default 0)                                  */
+} dp_mapref_options;
+typedef struct dp_mapref_stats {
+    int64_t depth_pixels_in, candidates, source_scores, kept, filled, moved;
+    double refine_ms;
+} dp_mapref_stats;
+
+void dp_default_mapref_options(dp_mapref_options *mo);
+int dp_refine_maps(dp_ctx *ctx, const int32_t *views, int n_views, const dp_mapref_options *mo,
+                   const int32_t *sources /* NULL = nearest */, const float *const *depth,
+                   const float *const *normal, float *const *depth_out, float *const *normal_out,
+                   float *const *score_out, int32_t *const *choice_out, dp_mapref_stats *stats);
+int dp_refine_maps_device(dp_ctx *ctx, const int32_t *views, int n_views, const dp_mapref_options *mo,
+                          const int32_t *sources, const float *const *d_depth, const float *const *d_normal,
+                          float *const *d_depth_out, float *const *d_normal_out, float *const *d_score_out,
+                          int32_t *const *d_choice_out, dp_mapref_stats *stats, void *stream);
+
 /* ---- seed generation: Features::Matcher::GenerateSeeds ---
  * modules/features/matcher.cpp:18-43 with the default MatcherOptions
  * (matcher.h:21-32: ORB detector, kNN matcher, no direct epipolar matching,

@@ -35,6 +35,11 @@ void usage()
                  "                             on the device into one cross-view-consistent cloud --\n"
                  "                             dp_fuse_maps; K = 0..63 agreeing other views, default 2;\n"
                  "                             T = relative depth tolerance, default 0.01)\n"
+                 "               [--refine-maps N [--refine-window W] [--refine-min-ncc T]]  (N passes of the\n"
+                 "                             per-pixel photometric refinement, dp_refine_maps, on the\n"
+                 "                             rendered maps before --depth-maps writes them -- then also\n"
+                 "                             score_%%04d.pfm -- and before --fuse fuses them; W = odd\n"
+                 "                             window side 3..11, default 7; T = least score, default 0.5)\n"
                  "       densify --synthetic V,W,H,KIND --write-scene DIR\n");
 }
 
@@ -144,6 +149,21 @@ Parse parse_args(int argc, char **argv, Args &a, std::string &error)
                 a.fuse.depth_tol = (float)t;
             else
                 error = "--fuse-depth-tol expects a finite number >= 0";
+        } else if (o == "--refine-maps") {
+            if (int_in_range(v, 0, 64, k))
+                a.refine_passes = (int)k;
+            else
+                error = "--refine-maps expects 0..64";
+        } else if (o == "--refine-window") {
+            if (int_in_range(v, 3, 11, k) && (k & 1))
+                a.refine_window = (int)k;
+            else
+                error = "--refine-window expects an odd number in 3..11";
+        } else if (o == "--refine-min-ncc") {
+            if (number_in_range(v, -1.0, 1.0, t))
+                a.refine_min_ncc = t;
+            else
+                error = "--refine-min-ncc expects a number in -1..1";
         } else if (o == "--exchange") {
             a.exchange_mode = v;
             if (one_of(v, {"auto", "rccl", "copy"}) < 0)

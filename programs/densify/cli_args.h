@@ -23,6 +23,10 @@ struct Args {
     double splat_scale = 1.0;
     bool depth_normals = false;
     dp_fuse_options fuse;
+    // --refine-maps N: dp_refine_maps passes between the render and its users
+    int refine_passes = 0;
+    int refine_window = 0;        // 0: the library's default
+    double refine_min_ncc = -2.0; // < -1: the library's default
 
     Args();
 };

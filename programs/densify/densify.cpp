@@ -275,6 +275,93 @@ dp_render_options render_options(const Args &args)
     return ro;
 }
 
+dp_mapref_options mapref_options(const Args &args)
+{
+    dp_mapref_options mo;
+    dp_default_mapref_options(&mo);
+    if (args.refine_window > 0)
+        mo.window = args.refine_window;
+    if (args.refine_min_ncc >= -1.0)
+        mo.min_ncc = (float)args.refine_min_ncc;
+    return mo;
+}
+
+// the report's member of the last --refine-maps pass
+std::string refined_report(const char *name, int passes, const dp_mapref_stats &ms, double total_ms)
+{
+    char buf[320];
+    std::snprintf(buf, sizeof buf,
+                  ", \"%s\": {\"passes\": %d, \"kept\": %lld, \"filled\": %lld, \"moved\": %lld, \"candidates\": %lld, "
+                  "\"refine_ms\": %.3f}",
+                  name, passes, (long long)ms.kept, (long long)ms.filled, (long long)ms.moved,
+                  (long long)ms.candidates, total_ms);
+    return buf;
+}
+
+// --depth-maps with --refine-maps N: the refinement reads every view's planes,
+// so all views are rendered first (with normals, which it needs), refined N
+// times on the host form, then written: depth, score, and normal when asked.
+std::string write_refined_depth_maps(dp_ctx *ctx, const Args &args, int32_t V, const std::vector<dp_patch> &kept)
+{
+    const dp_render_options ro = render_options(args);
+    const dp_mapref_options mo = mapref_options(args);
+    std::vector<int32_t> vid((size_t)V), ws((size_t)V), hs((size_t)V);
+    std::vector<std::vector<float>> depth[2], normal[2];
+    std::vector<std::vector<float>> score((size_t)V);
+    for (int b = 0; b < 2; ++b) {
+        depth[b].resize((size_t)V);
+        normal[b].resize((size_t)V);
+    }
+    std::vector<float *> pd[2], pn[2], ps((size_t)V);
+    for (int b = 0; b < 2; ++b) {
+        pd[b].resize((size_t)V);
+        pn[b].resize((size_t)V);
+    }
+    for (int32_t v = 0; v < V; ++v) {
+        check(ctx, dp_level_info(ctx, args.level, v, &ws[(size_t)v], &hs[(size_t)v], nullptr), "dp_level_info");
+        const size_t px = (size_t)ws[(size_t)v] * hs[(size_t)v];
+        vid[(size_t)v] = v;
+        for (int b = 0; b < 2; ++b) {
+            depth[b][(size_t)v].assign(px, 0.0f);
+            normal[b][(size_t)v].assign(px * 3, 0.0f);
+            pd[b][(size_t)v] = depth[b][(size_t)v].data();
+            pn[b][(size_t)v] = normal[b][(size_t)v].data();
+        }
+        score[(size_t)v].assign(px, 0.0f);
+        ps[(size_t)v] = score[(size_t)v].data();
+    }
+    dp_render_stats rs;
+    check(ctx,
+          dp_render_maps(ctx, kept.data(), (int64_t)kept.size(), nullptr, vid.data(), V, &ro, pd[0].data(), nullptr,
+                         pn[0].data(), nullptr, &rs),
+          "dp_render_maps");
+    dp_mapref_stats ms{};
+    double refine_ms = 0.0;
+    int cur = 0;
+    for (int pass = 0; pass < args.refine_passes; ++pass, cur ^= 1) {
+        check(ctx,
+              dp_refine_maps(ctx, vid.data(), V, &mo, nullptr, pd[cur].data(), pn[cur].data(), pd[cur ^ 1].data(),
+                             pn[cur ^ 1].data(), ps.data(), nullptr, &ms),
+              "dp_refine_maps");
+        refine_ms += ms.refine_ms;
+    }
+    for (int32_t v = 0; v < V; ++v) {
+        char name[64];
+        std::snprintf(name, sizeof name, "/depth_%04d.pfm", (int)v);
+        dpio::write_pfm(args.depth_dir + name, pd[cur][(size_t)v], ws[(size_t)v], hs[(size_t)v], 1);
+        std::snprintf(name, sizeof name, "/score_%04d.pfm", (int)v);
+        dpio::write_pfm(args.depth_dir + name, ps[(size_t)v], ws[(size_t)v], hs[(size_t)v], 1);
+        if (args.depth_normals) {
+            std::snprintf(name, sizeof name, "/normal_%04d.pfm", (int)v);
+            dpio::write_pfm(args.depth_dir + name, pn[cur][(size_t)v], ws[(size_t)v], hs[(size_t)v], 3);
+        }
+    }
+    char buf[160];
+    std::snprintf(buf, sizeof buf, ", \"depth_maps\": {\"views\": %zu, \"covered_pixels\": %lld, \"render_ms\": %.3f}",
+                  (size_t)V, (long long)rs.covered_pixels, rs.render_ms);
+    return buf + refined_report("refined_maps", args.refine_passes, ms, refine_ms);
+}
+
 // --depth-maps: the written patches as per-view depth (and normal) maps of
 // the level the densify ran on (dp_render_maps), one view at a time; with
 // --gpus N this context (rank 0) renders, the store being replicated.
@@ -283,6 +370,8 @@ std::string write_depth_maps(dp_ctx *ctx, const Args &args, int32_t V, const std
 {
     if (mkdir(args.depth_dir.c_str(), 0777) != 0 && errno != EEXIST)
         throw std::runtime_error("cannot create " + args.depth_dir);
+    if (args.refine_passes > 0)
+        return write_refined_depth_maps(ctx, args, V, kept);
     const dp_render_options ro = render_options(args);
     int64_t covered = 0;
     double render_ms = 0.0;
@@ -351,6 +440,32 @@ std::string write_fused(dp_ctx *ctx, const Args &args, int32_t V, const std::vec
                                 dd.data(), nullptr, dn.data(), nullptr, &rs, nullptr),
           "dp_render_maps_device");
     int64_t cap = rs.covered_pixels, n_fused = 0;
+    // --refine-maps N: N passes between the render and the fusion, into a
+    // second set of planes and back; a pixel that is not kept is never emitted
+    std::string refined;
+    if (args.refine_passes > 0) {
+        const dp_mapref_options mo = mapref_options(args);
+        std::vector<float *> dd2((size_t)V), dn2((size_t)V);
+        for (int32_t v = 0; v < V; ++v) {
+            int32_t w = 0, h = 0;
+            check(ctx, dp_level_info(ctx, args.level, v, &w, &h, nullptr), "dp_level_info");
+            dd2[(size_t)v] = (float *)device_bytes((size_t)w * h * 4);
+            dn2[(size_t)v] = (float *)device_bytes((size_t)w * h * 12);
+        }
+        dp_mapref_stats ms{};
+        double refine_ms = 0.0;
+        for (int pass = 0; pass < args.refine_passes; ++pass) {
+            check(ctx,
+                  dp_refine_maps_device(ctx, vid.data(), V, &mo, nullptr, dd.data(), dn.data(), dd2.data(), dn2.data(),
+                                        nullptr, nullptr, &ms, nullptr),
+                  "dp_refine_maps_device");
+            refine_ms += ms.refine_ms;
+            dd.swap(dd2);
+            dn.swap(dn2);
+        }
+        cap = ms.kept;
+        refined = refined_report("refined", args.refine_passes, ms, refine_ms);
+    }
     dp_fuse_stats fs;
     dp_fused_point *d_pts = nullptr;
     for (int attempt = 0; attempt < 2; ++attempt) {
@@ -374,7 +489,7 @@ std::string write_fused(dp_ctx *ctx, const Args &args, int32_t V, const std::vec
     std::snprintf(buf, sizeof buf,
                   ", \"fused\": {\"points\": %lld, \"fusable\": %lld, \"depth_pixels\": %lld, \"fuse_ms\": %.3f}",
                   (long long)n_fused, (long long)fs.fusable, (long long)fs.depth_pixels, fs.fuse_ms);
-    return buf;
+    return refined + buf;
 }
 
 using Clock = std::chrono::steady_clock;
