@@ -19,6 +19,7 @@ from ._native import (  # noqa: F401
     DensePointsError,
     FUSED_DTYPE,
     LIB_PATH,
+    MESH_VERTEX_DTYPE,
 )
 from .pmvs import (  # noqa: F401
     PMVS,
@@ -28,6 +29,7 @@ from .pmvs import (  # noqa: F401
     View,
     check_fuse_args,
     check_mapref_args,
+    check_tsdf_args,
     empty_patches,
     mask_from_list,
     ncc_score,
@@ -35,6 +37,7 @@ from .pmvs import (  # noqa: F401
     read_scene_json,
     visible_list,
     write_pfm,
+    write_mesh_ply,
     write_ply,
 )
 from . import synth  # noqa: F401

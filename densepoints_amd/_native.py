@@ -221,6 +221,42 @@ class DpMaprefStats(ctypes.Structure):
 MAPREF_KEEP_UNSCORED = 1
 
 
+class DpTsdfOptions(ctypes.Structure):
+    """dp_tsdf_options: the volume of dp_tsdf_integrate / dp_tsdf_mesh (include/densepoints.h)."""
+    _fields_ = [
+        ("origin", ctypes.c_float * 3),
+        ("voxel", ctypes.c_float),
+        ("dim", ctypes.c_int32 * 3),
+        ("trunc", ctypes.c_float),
+        ("min_weight", ctypes.c_int32),
+        ("flags", ctypes.c_int32),
+    ]
+
+
+class DpTsdfStats(ctypes.Structure):
+    _fields_ = [
+        ("voxels", ctypes.c_int64),
+        ("observations", ctypes.c_int64),
+        ("observed_voxels", ctypes.c_int64),
+        ("near_voxels", ctypes.c_int64),
+        ("integrate_ms", ctypes.c_double),
+    ]
+
+
+class DpMeshStats(ctypes.Structure):
+    _fields_ = [
+        ("active_cells", ctypes.c_int64),
+        ("vertices", ctypes.c_int64),
+        ("triangles", ctypes.c_int64),
+        ("mesh_ms", ctypes.c_double),
+    ]
+
+
+# dp_mesh_vertex (include/densepoints.h) -- 16 bytes
+MESH_VERTEX_DTYPE = np.dtype([("pos", "<f4", 3), ("rgb", "u1", 3), ("pad", "u1")])
+assert MESH_VERTEX_DTYPE.itemsize == 16
+
+
 class DpSynthConfig(ctypes.Structure):
     _fields_ = [
         ("n_views", ctypes.c_int32),
@@ -350,6 +386,11 @@ SIGNATURES = [
     ("dp_default_mapref_options", None, [_P]),
     ("dp_refine_maps", _I, [_P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     ("dp_refine_maps_device", _I, [_P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    ("dp_default_tsdf_options", None, [_P]),
+    ("dp_tsdf_integrate", _I, [_P, _P, _I, _P, _P, _P, _P, _P, _P]),
+    ("dp_tsdf_integrate_device", _I, [_P, _P, _I, _P, _P, _P, _P, _P, _P, _P]),
+    ("dp_tsdf_mesh", _I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    ("dp_tsdf_mesh_device", _I, [_P, _P, _P, _P, _P, _P, ctypes.c_int64, _P, _P, ctypes.c_int64, _P, _P, _P]),
     ("dp_last_kernel_ms", _I, [_P, _P]),
     ("dp_default_matcher_options", None, [_P]),
     ("dp_orb_pattern", _I, [_P]),

@@ -4,7 +4,8 @@
 // engine; dp_fast.hip: performance mode; dp_synth.hip: synthetic scenes and
 // probes; dp_seeds_capi.hip, dp_seeds_orb.hip, dp_seeds_akaze.hip: seed
 // generation (their own state is dp_seedgen.h); dp_render.hip: maps;
-// dp_fuse.hip: their fusion; dp_mapref.hip: their refinement).  Every member that owns a device or pinned
+// dp_fuse.hip: their fusion; dp_mapref.hip: their refinement; dp_tsdf.hip:
+// their volume and mesh).  Every member that owns a device or pinned
 // allocation or an event has an owning type (dp_buf.h), so deleting the
 // context frees them; only the views and the pyramid (free_views) and the
 // stream, which must outlive them all, are released by hand.
@@ -122,6 +123,23 @@ struct dp_ctx {
     HostBuf<unsigned long long> m_hcount;
     DevBuf<unsigned char> m_io;
     Event m_e0, m_e1;
+    // dp_tsdf_integrate / dp_tsdf_mesh: the view table, striped counters and the
+    // statistics read, the host forms' staged inputs and volume; the mesh's edge
+    // flags (one byte per lattice point, in 32-bit words), per-cell triangle
+    // counts, per-point first vertex numbers, per-block counts and their scans,
+    // the host form's device and pinned results, timing events (the host form
+    // of the mesh times its two phases apart)
+    DevBuf<dpk::TsdfView> t_tab;
+    DevBuf<unsigned long long> t_count, t_bcount, t_boff;
+    HostBuf<unsigned long long> t_hcount;
+    DevBuf<unsigned char> t_in, t_vol;
+    DevBuf<uint32_t> t_flags, t_vbase;
+    DevBuf<uint8_t> t_tcount;
+    DevBuf<dp_mesh_vertex> t_verts;
+    DevBuf<int32_t> t_tris;
+    HostBuf<dp_mesh_vertex> t_hverts;
+    HostBuf<int32_t> t_htris;
+    Event t_e0, t_e1, t_e2, t_e3;
     HostBuf<dp_patch> result; // dp_densify / dp_densify_result output (pinned)
     // dp_densify_iterate: per iteration {evaluations, filter survivors} on the
     // device (read once, at the end) and the filters' timing events

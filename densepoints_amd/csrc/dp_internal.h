@@ -346,6 +346,59 @@ struct MaprefArgs {
 // gx 16 x 16 tiles per view (the largest plane's), K views
 hipError_t launch_mapref(const MaprefArgs &a, unsigned gx, hipStream_t s);
 
+// TSDF volume and mesh (dp_tsdf.hip; spec in include/densepoints.h, dp_tsdf_integrate / dp_tsdf_mesh)
+struct TsdfView { // one requested view; indexed wave-uniformly (scalar loads)
+    double P[12];
+    double g;             // sqrt(dot(m2, m2)), m2 = P[8..10]
+    const float *depth;   // W x H
+    const uint32_t *img;  // BGRA8 plane of the current level
+    int32_t W, H, pitch, view;
+};
+constexpr int kTsdfRows = 4;       // an integrate block: 64 consecutive x of kTsdfRows rows j (one wave each)
+constexpr int kTsdfCounters = 4;   // voxels, observations, observed voxels, near voxels
+constexpr int kTsdfStripes = 64;   // each counter kept kTsdfStripes times (summed by the host)
+constexpr int kMeshBlock = 256;    // lattice points per block, consecutive in (k, j, i) order
+struct TsdfVolume {
+    double origin[3], voxel; // widened from the options' floats
+    int32_t nx, ny, nz;
+};
+struct TsdfArgs {
+    const TsdfView *tab;
+    int32_t K;
+    TsdfVolume vol;
+    double trunc;
+    float *tsdf;                // outputs, any may be null
+    int32_t *weight;
+    uint32_t *rgb;
+    unsigned long long *count;  // kTsdfStripes x kTsdfCounters
+};
+hipError_t launch_tsdf_integrate(const TsdfArgs &a, hipStream_t s);
+struct MeshArgs {
+    TsdfVolume vol;
+    int32_t min_weight;
+    int64_t points;                    // nx * ny * nz; cell (i, j, k) is indexed by its corner p
+    const float *tsdf;
+    const int32_t *weight;
+    const uint32_t *rgb;               // may be null
+    uint32_t *flags;                   // one byte per lattice point (7 edge bits), set by 32-bit atomicOr
+    uint8_t *tcount;                   // per cell: its triangles (0 where inactive or no cell)
+    uint32_t *vbase;                   // per lattice point: the number of its first vertex
+    unsigned long long *bcount;        // [0, blocks]: vertices per block, then 0;
+    const unsigned long long *boff;    //   [blocks + 1, 2 blocks + 1]: triangles per block, then 0; boff their scans
+    unsigned long long *active;        // active cells
+    int64_t blocks;
+    dp_mesh_vertex *verts;
+    int32_t *tris;
+    int64_t vcap, tcap;
+};
+// the flags must be zero before launch_mesh_count; launch_mesh_vertices needs
+// the vertex scan, launch_mesh_triangles the triangle scan and the vbase of
+// launch_mesh_vertices
+hipError_t launch_mesh_count(const MeshArgs &a, hipStream_t s);
+hipError_t launch_mesh_vcount(const MeshArgs &a, hipStream_t s);
+hipError_t launch_mesh_vertices(const MeshArgs &a, hipStream_t s);
+hipError_t launch_mesh_triangles(const MeshArgs &a, hipStream_t s);
+
 hipError_t launch_refine(const RefineArgs &a, hipStream_t s);
 hipError_t launch_pyr_down(const PyrPlane *d_src, const PyrPlane *d_dst, int V, int max_dw, int max_dh,
                            hipStream_t s);

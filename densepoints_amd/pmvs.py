@@ -37,6 +37,9 @@ __all__ = [
     "write_pfm",
     "check_fuse_args",
     "check_mapref_args",
+    "check_tsdf_args",
+    "mesh_volume",
+    "write_mesh_ply",
     "read_pfm",
     "empty_patches",
     "visible_list",
@@ -748,6 +751,169 @@ class Engine:
                                               ctypes.c_void_p(stream) if stream else None))
         return {name: getattr(st, name) for name, _ in N.DpMaprefStats._fields_} if stats else None
 
+    # ---- TSDF volume and mesh (include/densepoints.h dp_tsdf_integrate / dp_tsdf_mesh) ----
+    def tsdf_integrate(self, depth, views=None, *, origin, voxel, dim, trunc) -> dict:
+        """dp_tsdf_integrate: the depth planes of `views` (None = all), as
+        render_maps or refine_maps return them, integrated into one dense volume
+        of dim = (nx, ny, nz) voxels of side `voxel` with its low corner at
+        `origin`.  Returns {"tsdf" f32, "weight" int32, "rgb" uint32 (R | G << 8 |
+        B << 16), each [nz][ny][nx], "origin", "voxel", "dim", "trunc" (the volume,
+        as tsdf_mesh reads it), "views", "stats"}."""
+        to, vid = check_tsdf_args(self.num_views(), views, origin, voxel, dim, trunc)
+        sizes = self.view_sizes(vid)
+        if depth is None or len(depth) != len(vid):
+            raise ValueError("tsdf_integrate: one depth plane per view")
+        planes = [np.ascontiguousarray(a, dtype=np.float32) for a in depth]
+        for a, (w, h) in zip(planes, sizes):
+            if a.shape != (h, w):
+                raise ValueError("tsdf_integrate: a depth plane of shape %s, expected %s" % (a.shape, (h, w)))
+        dtab = (ctypes.c_void_p * len(vid))(*[a.ctypes.data for a in planes])
+        shape = (to.dim[2], to.dim[1], to.dim[0])
+        out = {"tsdf": np.zeros(shape, np.float32), "weight": np.zeros(shape, np.int32),
+               "rgb": np.zeros(shape, np.uint32)}
+        st = N.DpTsdfStats()
+        self._check(lib.dp_tsdf_integrate(self._ctx, ptr(vid), len(vid), ctypes.byref(to), dtab, ptr(out["tsdf"]),
+                                          ptr(out["weight"]), ptr(out["rgb"]), ctypes.byref(st)))
+        out.update(origin=tuple(to.origin), voxel=to.voxel, dim=tuple(to.dim), trunc=to.trunc,
+                   views=[int(v) for v in vid],
+                   stats={name: getattr(st, name) for name, _ in N.DpTsdfStats._fields_})
+        return out
+
+    def tsdf_integrate_device(self, views, d_depth, d_tsdf, d_weight, d_rgb, *, origin, voxel, dim, trunc,
+                              stream: int | None = None, stats: bool = True) -> dict | None:
+        """dp_tsdf_integrate_device: device depth planes (a list of device
+        addresses, one per entry of `views`) into device volumes (addresses;
+        None or 0 = not wanted).  Queued on `stream`; waits only for the
+        statistics (stats=False: no wait, returns None)."""
+        to, vid = check_tsdf_args(self.num_views(), views, origin, voxel, dim, trunc)
+        if d_depth is None or len(d_depth) != len(vid) or not all(d_depth):
+            raise ValueError("tsdf_integrate_device: one depth plane address per view")
+        dtab = (ctypes.c_void_p * len(vid))(*[int(a) for a in d_depth])
+        st = N.DpTsdfStats()
+        self._check(lib.dp_tsdf_integrate_device(self._ctx, ptr(vid), len(vid), ctypes.byref(to), dtab,
+                                                 ctypes.c_void_p(d_tsdf) if d_tsdf else None,
+                                                 ctypes.c_void_p(d_weight) if d_weight else None,
+                                                 ctypes.c_void_p(d_rgb) if d_rgb else None,
+                                                 ctypes.byref(st) if stats else None,
+                                                 ctypes.c_void_p(stream) if stream else None))
+        return {name: getattr(st, name) for name, _ in N.DpTsdfStats._fields_} if stats else None
+
+    def tsdf_mesh(self, volume: dict, min_weight: int = 1):
+        """dp_tsdf_mesh: the zero surface of a volume as tsdf_integrate returns it
+        ("rgb" may be missing or None: vertex colour 0), by marching tetrahedra
+        over the cells whose eight corners have weight >= min_weight.  Returns
+        (vertices as a MESH_VERTEX_DTYPE array, triangles as n x 3 int32, stats)."""
+        to, _ = check_tsdf_args(1, None, volume["origin"], volume["voxel"], volume["dim"], volume["trunc"], min_weight)
+        shape = (to.dim[2], to.dim[1], to.dim[0])
+
+        def plane(key, dtype):
+            a = np.ascontiguousarray(volume[key], dtype=dtype)
+            if a.shape != shape:
+                raise ValueError("tsdf_mesh: a %s volume of shape %s, expected %s" % (key, a.shape, shape))
+            return a
+
+        tsdf, weight = plane("tsdf", np.float32), plane("weight", np.int32)
+        rgb = plane("rgb", np.uint32) if volume.get("rgb") is not None else None
+        pv, pt, nv, nt, st = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_int64(), ctypes.c_int64(), N.DpMeshStats()
+        self._check(lib.dp_tsdf_mesh(self._ctx, ctypes.byref(to), ptr(tsdf), ptr(weight), ptr(rgb), ctypes.byref(pv),
+                                     ctypes.byref(nv), ctypes.byref(pt), ctypes.byref(nt), ctypes.byref(st)))
+        verts = np.zeros(nv.value, dtype=N.MESH_VERTEX_DTYPE)
+        tris = np.zeros((nt.value, 3), dtype=np.int32)
+        if nv.value:
+            ctypes.memmove(verts.ctypes.data, pv.value, verts.nbytes)
+        if nt.value:
+            ctypes.memmove(tris.ctypes.data, pt.value, tris.nbytes)
+        return verts, tris, {name: getattr(st, name) for name, _ in N.DpMeshStats._fields_}
+
+    def tsdf_mesh_device(self, d_tsdf, d_weight, d_rgb, d_vertices, vertex_cap: int, d_triangles, triangle_cap: int,
+                         *, origin, voxel, dim, trunc, min_weight: int = 1, stream: int | None = None):
+        """dp_tsdf_mesh_device: device volumes (addresses; d_rgb None or 0 = vertex
+        colour 0) into at most vertex_cap dp_mesh_vertex records at d_vertices and
+        triangle_cap int32 triples at d_triangles.  Queued on `stream`; one wait.
+        Returns (the full vertex count, the full triangle count -- above a cap:
+        an overflow --, stats)."""
+        to, _ = check_tsdf_args(1, None, origin, voxel, dim, trunc, min_weight)
+        if not d_tsdf or not d_weight:
+            raise ValueError("tsdf_mesh_device: the tsdf and weight volumes must be given")
+        for cap, buf in ((vertex_cap, d_vertices), (triangle_cap, d_triangles)):
+            if int(cap) != cap or cap < 0 or (cap > 0 and not buf):
+                raise ValueError("tsdf_mesh_device: a cap must be >= 0, with its buffer given when > 0")
+        nv, nt, st = ctypes.c_int64(), ctypes.c_int64(), N.DpMeshStats()
+        self._check(lib.dp_tsdf_mesh_device(self._ctx, ctypes.byref(to), ctypes.c_void_p(d_tsdf),
+                                            ctypes.c_void_p(d_weight), ctypes.c_void_p(d_rgb) if d_rgb else None,
+                                            ctypes.c_void_p(d_vertices) if d_vertices else None, int(vertex_cap),
+                                            ctypes.byref(nv), ctypes.c_void_p(d_triangles) if d_triangles else None,
+                                            int(triangle_cap), ctypes.byref(nt), ctypes.byref(st),
+                                            ctypes.c_void_p(stream) if stream else None))
+        return int(nv.value), int(nt.value), {name: getattr(st, name) for name, _ in N.DpMeshStats._fields_}
+
+
+def check_tsdf_args(V: int, views, origin, voxel, dim, trunc, min_weight: int = 1):
+    """Argument validation of Engine.tsdf_integrate[_device] and tsdf_mesh[_device]
+    (the limits of dp_tsdf_options and the view rules of dp_tsdf_integrate,
+    raised as ValueError before any device call); returns (dp_tsdf_options, view
+    ids as int32)."""
+    def number(x):
+        return isinstance(x, (int, float, np.integer, np.floating)) and not isinstance(x, bool)
+
+    def f32(x):
+        with np.errstate(over="ignore"):
+            return float(np.float32(x))
+
+    try:
+        origin = tuple(origin)
+    except TypeError:
+        origin = ()
+    if len(origin) != 3 or not all(number(c) and np.isfinite(f32(c)) for c in origin):
+        raise ValueError("tsdf: origin must be three finite numbers")
+    if not (number(voxel) and np.isfinite(f32(voxel)) and f32(voxel) > 0):
+        raise ValueError("tsdf: voxel must be finite and > 0")
+    if not (number(trunc) and np.isfinite(f32(trunc)) and f32(trunc) > 0):
+        raise ValueError("tsdf: trunc must be finite and > 0")
+    try:
+        dim = tuple(dim)
+    except TypeError:
+        dim = ()
+    if len(dim) != 3 or not all(number(d) and int(d) == d and 2 <= int(d) <= 1024 for d in dim):
+        raise ValueError("tsdf: dim must be three sizes in 2..1024")
+    if int(dim[0]) * int(dim[1]) * int(dim[2]) > 2**30:
+        raise ValueError("tsdf: at most 2^30 voxels")
+    if not (number(min_weight) and int(min_weight) == min_weight and 1 <= int(min_weight) <= 64):
+        raise ValueError("tsdf: min_weight must be in 1..64")
+    vid = np.arange(V, dtype=np.int64) if views is None else np.asarray(list(views), dtype=np.int64)
+    if vid.ndim != 1 or not 1 <= len(vid) <= 64:
+        raise ValueError("tsdf: 1..64 views")
+    if (vid < 0).any() or (vid >= V).any() or len(set(vid.tolist())) != len(vid):
+        raise ValueError("tsdf: view ids must be unique and < %d" % V)
+    to = N.DpTsdfOptions((ctypes.c_float * 3)(*[float(c) for c in origin]), float(voxel),
+                         (ctypes.c_int32 * 3)(*[int(d) for d in dim]), float(trunc), int(min_weight), 0)
+    return to, np.ascontiguousarray(vid, dtype=np.int32)
+
+
+def mesh_volume(positions: np.ndarray, voxel=None, dim: int = 256, trunc=None) -> dict:
+    """The volume PMVS.mesh integrates into: the bounding box of `positions`
+    (n x 3) padded by trunc on every side.  voxel defaults to the box's longest
+    side / dim, trunc to 4 * voxel; the sizes are ceil(padded side / voxel),
+    clipped to 2..1024.  Returns dict(origin, voxel, dim, trunc)."""
+    pos = np.asarray(positions, dtype=np.float64).reshape(-1, 3)
+    pos = pos[np.isfinite(pos).all(axis=1)]
+    if len(pos) == 0:
+        raise ValueError("mesh: no patch positions to bound the volume")
+    if isinstance(dim, bool) or int(dim) != dim or not 2 <= int(dim) <= 1024:
+        raise ValueError("mesh: dim must be in 2..1024")
+    lo, hi = pos.min(axis=0), pos.max(axis=0)
+    if voxel is None:
+        voxel = float((hi - lo).max()) / int(dim)
+    if not (np.isfinite(voxel) and voxel > 0):
+        raise ValueError("mesh: voxel must be finite and > 0 (a single point bounds no volume: give voxel)")
+    if trunc is None:
+        trunc = 4.0 * voxel
+    if not (np.isfinite(trunc) and trunc > 0):
+        raise ValueError("mesh: trunc must be finite and > 0")
+    sizes = np.ceil((hi - lo + 2.0 * trunc) / voxel)
+    return dict(origin=tuple(float(c) for c in lo - trunc), voxel=float(voxel),
+                dim=tuple(int(min(max(s, 2), 1024)) for s in sizes), trunc=float(trunc))
+
 
 MAPREF_DEFAULTS = dict(window=7, sweep=2, step_px=1.0, reach=(1, 4), max_sources=4, top_k=2, min_ncc=0.5,
                        keep_unscored=False)
@@ -1064,6 +1230,32 @@ class PMVS:
         self.stats["render"], self.stats["fused"] = rst, fst
         return out
 
+    def mesh(self, refine: int = 0, voxel=None, dim: int = 256, trunc=None, min_weight: int = 2, **kw):
+        """The last run()'s result as a triangle mesh: (vertices as a
+        MESH_VERTEX_DTYPE array, triangles as n x 3 int32).  The depth maps of
+        depth_maps(refine, **kw) -- kw: its render and refinement options --
+        are integrated into one TSDF volume (Engine.tsdf_integrate) around the
+        patches (mesh_volume: their bounding box padded by trunc; voxel defaults
+        to its longest side / dim, trunc to 4 * voxel) and the volume's zero
+        surface is extracted (Engine.tsdf_mesh) over the voxels that at least
+        min_weight views observed.  The volume and the statistics of the two
+        calls are left in self.stats["mesh"]."""
+        if not self._ran:
+            raise ValueError("mesh: call run() first")
+        refine, mkw, kw = split_refine_args("mesh", refine, kw)
+        vol = mesh_volume(self.patches["pos"], voxel, dim, trunc)
+        check_tsdf_args(max(len(self.views), 1), kw.get("views"), min_weight=min_weight, **vol)
+        with Engine(self.options, self.device) as eng:
+            eng.set_views(self.views)
+            maps = eng.render_maps(self.patches, **dict(kw, normals=bool(refine) or kw.get("normals", False)))
+            for _ in range(refine):
+                ref = eng.refine_maps(maps["depth"], maps["normal"], views=maps["views"], **mkw)
+                maps["depth"], maps["normal"] = ref["depth"], ref["normal"]
+            volume = eng.tsdf_integrate(maps["depth"], maps["views"], **vol)
+            verts, tris, mst = eng.tsdf_mesh(volume, min_weight)
+        self.stats["mesh"] = dict(vol, min_weight=int(min_weight), integrate=volume["stats"], mesh=mst)
+        return verts, tris
+
 
 def ncc_score(a: np.ndarray, b: np.ndarray, denom_min: float = 0.1) -> float:
     """NCCScore (error_measurements.cpp:36-60) on integer-valued textures: exact
@@ -1110,3 +1302,26 @@ def write_ply(path: str, patches: np.ndarray) -> None:
             r, g, b = (int(v) for v in p["rgb"])
             nx, ny, nz = (float(v) for v in p["normal"])
             f.write(f"{x:g} {y:g} {z:g} {r} {g} {b} {nx:g} {ny:g} {nz:g}\n")
+
+
+def write_mesh_ply(path: str, vertices: np.ndarray, triangles: np.ndarray) -> None:
+    """A triangle mesh (Engine.tsdf_mesh's vertices and triangles) as an ASCII
+    PLY: vertex x y z (float, %.9g: an f32 round-trips) red green blue (uchar),
+    face vertex_indices (list uchar int)."""
+    triangles = np.asarray(triangles).reshape(-1, 3)
+    with open(path, "w") as f:
+        f.write("ply\nformat ascii 1.0\n")
+        f.write(f"element vertex {len(vertices)}\n")
+        for n in ("x", "y", "z"):
+            f.write(f"property float {n}\n")
+        for n in ("red", "green", "blue"):
+            f.write(f"property uchar {n}\n")
+        f.write(f"element face {len(triangles)}\n")
+        f.write("property list uchar int vertex_indices\n")
+        f.write("end_header\n")
+        for v in vertices:
+            x, y, z = (float(c) for c in v["pos"])
+            r, g, b = (int(c) for c in v["rgb"])
+            f.write(f"{x:.9g} {y:.9g} {z:.9g} {r} {g} {b}\n")
+        for t in triangles:
+            f.write(f"3 {int(t[0])} {int(t[1])} {int(t[2])}\n")

@@ -715,6 +715,140 @@ int dp_refine_maps_device(dp_ctx *ctx, const int32_t *views, int n_views, const 
                           float *const *d_depth_out, float *const *d_normal_out, float *const *d_score_out,
                           int32_t *const *d_choice_out, dp_mapref_stats *stats, void *stream);
 
+/* ---- TSDF volume and triangle mesh: per-view depth maps integrated into one
+ * dense truncated-signed-distance volume, and its zero surface extracted by
+ * marching tetrahedra -----------------------------------------------------------
+ * No reference counterpart (modules/surface/ is an empty stub).  One dense
+ * volume per call: nothing is accumulated between calls.  All fp64 arithmetic is
+ * one IEEE rounding per operation in exactly the order written
+ * (-ffp-contract=off); dot, row_r and project are dp_render_maps's; "is a depth"
+ * and the rules of the requested views (unique ids < V, 1 <= K <= 64, the CURRENT
+ * level's P, W, H and BGRA8 planes) are dp_fuse_maps's.
+ *
+ * The volume (dp_tsdf_options): nx x ny x nz voxels of side `voxel`, the low
+ * corner of voxel (0, 0, 0) at `origin`; every plane of it is [nz][ny][nx], x
+ * fastest.  The centre of voxel idx = (i, j, k) is X_a = (double)origin[a] +
+ * ((double)idx_a + 0.5) * (double)voxel, a = 0, 1, 2.
+ *
+ * dp_tsdf_integrate.  Per requested view v, once on the host in fp64: m2 =
+ * (P[8], P[9], P[10]), g_v = sqrt(dot(m2, m2)); g_v not finite or not > 0:
+ * DP_E_ARG.  Dividing a projective depth difference by g_v makes it a distance
+ * along the optical axis, so `trunc` is in world units whatever the scale of P.
+ * Voxel (i, j, k), X its centre: tsum = 0.0, w = 0, integers sr = sg = sb = 0;
+ * then for the requested views in the order of `views`:
+ *   1. d = row_2(P_v, X); require d > 0;
+ *   2. u = row_0 / d, v = row_1 / d; require |u| < 2e9 and |v| < 2e9 (NaN fails);
+ *      xi = rint(u), yi = rint(v), round-half-even; require 0 <= xi < W_v and
+ *      0 <= yi < H_v                      -- steps 2-3 of dp_fuse_maps's observe;
+ *   3. z = depth_v[yi][xi]; require that z is a depth;
+ *   4. sdf = ((double)z - d) / g_v;
+ *   5. if sdf < -(double)trunc the view does not count (the voxel is occluded);
+ *   6. otherwise t = sdf >= (double)trunc ? 1.0 : sdf / (double)trunc, tsum =
+ *      tsum + t, w += 1, and sr, sg, sb add the R, G, B of the BGRA8 texel (xi,
+ *      yi) of view v at the current level.
+ * Outputs: weight = w; tsdf = w > 0 ? (float)(tsum / (double)w) : 1.0f; rgb = w >
+ * 0 ? R | G << 8 | B << 16, each channel (s + w/2) / w in integers : 0.  One
+ * voxel's result is a function of the voxel alone, the views walked in order: it
+ * depends on neither the launch geometry nor on atomics.  An output pointer may
+ * be NULL.  Statistics, counted on the device: voxels, observations (the sum of
+ * w), observed_voxels (w > 0), near_voxels (w > 0 and fabsf(tsdf) < 1);
+ * integrate_ms = device time of the call's kernel.
+ * Host form: host planes and host outputs.  Device form: device planes and
+ * outputs, everything queued on `stream` (NULL = the context's); it waits only
+ * for the statistics read, and not at all with stats == NULL.
+ *
+ * dp_tsdf_mesh.  Inputs: the tsdf, weight and (optionally, NULL = vertex colour
+ * 0) rgb planes of a volume described by `opts`; tsdf values are expected to be
+ * finite (the integration writes [-1, 1] only): a vertex of an edge with a NaN
+ * or infinite end has an unspecified position and colour, nothing else changes.
+ * Lattice point p = (i, j, k) sits at the centre of voxel p.  A point is INSIDE
+ * iff tsdf < 0 (0, -0, 1 and NaN are outside).  Cell (i, j, k), 0 <= i < nx - 1,
+ * 0 <= j < ny - 1, 0 <= k < nz - 1, has the corners p + {0,1}^3 and is ACTIVE iff
+ * all eight have weight >= min_weight.
+ * Kuhn split: every cell is cut into six tetrahedra, one per permutation (a, b,
+ * c) of the axes (0, 1, 2) in lexicographic order (012, 021, 102, 120, 201,
+ * 210); tetrahedron (a, b, c) has the corners q0 = p, q1 = p + e_a, q2 = p + e_a
+ * + e_b, q3 = p + (1, 1, 1).  The split is the same in every cell, so
+ * neighbouring cells agree on their common faces and the mesh is watertight
+ * wherever active cells meet.  An edge (q_m, q_n), m < n, of a tetrahedron runs
+ * from the lattice point q_m in the direction q_n - q_m, one of (1,0,0) (0,1,0)
+ * (0,0,1) (1,1,0) (1,0,1) (0,1,1) (1,1,1), numbered dir = 0..6 in this order.
+ * Edge (p, dir) CARRIES A VERTEX iff its ends differ in INSIDE and at least one
+ * ACTIVE cell has both ends among its corners.  Vertices are numbered in
+ * ascending (k, j, i, dir).  With A at p, B at p + dir, a, b their tsdf widened
+ * to fp64 and ca, cb a colour channel of their rgb words: s = a / (a - b), pos_c
+ * = (float)(XA_c + s * (XB_c - XA_c)), channel = (uint8)rint((double)ca + s *
+ * ((double)cb - (double)ca)); pad = 0.
+ * Triangles: each tetrahedron of an active cell emits the triangles of its 4-bit
+ * inside mask (bit m set iff q_m is INSIDE), each corner the vertex of the named
+ * edge "mn" = (q_m, q_n).  For an EVEN permutation (012, 120, 201):
+ *    1: 01 02 03           2: 01 13 12           4: 02 12 23
+ *    8: 03 23 13           7: 03 13 23          11: 02 23 12
+ *   13: 01 12 13          14: 01 03 02
+ *    3: 02 03 13, 02 13 12         5: 01 23 03, 01 12 23
+ *    6: 01 13 23, 01 23 02         9: 01 02 23, 01 23 13
+ *   10: 01 23 12, 01 03 23        12: 02 12 13, 02 13 03
+ * and nothing for 0 and 15; for an ODD permutation (021, 102, 210) the second
+ * and third corner of every triangle are exchanged.  The rule reads the
+ * permutation and the mask only, never a coordinate; with it cross(v1 - v0, v2 -
+ * v0) points from inside to outside, which is towards the cameras.  A triangle
+ * is three vertex numbers (int32).  Order: ascending cell (k, j, i), then
+ * tetrahedron, then triangle.  Zero-area triangles are kept (a tsdf of exactly 0
+ * puts a vertex on a lattice point).
+ * Statistics, counted on the device: active_cells, vertices, triangles; mesh_ms
+ * = device time of the call's kernels.
+ * Host form: host planes; *vertices and *triangles are context-owned, valid until
+ * the next dp_tsdf_mesh or destroy (NULL when the count is 0).  Device form:
+ * device planes; writes the first min(vertex_cap, vertices) vertices and the
+ * first min(triangle_cap, triangles) triangles and nothing beyond them (a buffer
+ * may be NULL with cap 0); *n_vertices and *n_triangles are the full counts, so a
+ * caller sees an overflow; everything is queued on `stream` (NULL = the
+ * context's) and the call waits once, for the counts.  stats may be NULL.
+ *
+ * Errors (DP_E_ARG): opts NULL, an origin, voxel or trunc that is not finite,
+ * voxel or trunc not > 0, a dim outside 2..1024, nx*ny*nz > 2^30, min_weight
+ * outside 1..64, flags != 0; a NULL input plane or array; for the integration
+ * the view rules above and a g_v as above; for the mesh a NULL count or result
+ * pointer, a negative cap, a cap > 0 without its buffer, and a volume whose mesh
+ * has more than 2^31 - 1 vertices or triangles.  No views set, for the
+ * integration: DP_E_STATE (the mesh reads no view). */
+typedef struct dp_tsdf_options {
+    float origin[3];     /* world position of the volume's low corner (no default)      */
+    float voxel;         /* voxel side, world units (> 0, finite; no default)           */
+    int32_t dim[3];      /* nx, ny, nz: each 2..1024, nx*ny*nz <= 2^30 (no default)     */
+    float trunc;         /* truncation distance, world units (> 0, finite; no default)  */
+    int32_t min_weight;  /* 1  least observations for a voxel to take part in the mesh (1..64) */
+    int32_t flags;       /* none defined; non-zero is DP_E_ARG                          */
+} dp_tsdf_options;
+typedef struct dp_mesh_vertex {
+    float pos[3];
+    uint8_t rgb[3];
+    uint8_t pad;         /* 0 */
+} dp_mesh_vertex;
+typedef struct dp_tsdf_stats {
+    int64_t voxels, observations, observed_voxels, near_voxels;
+    double integrate_ms;
+} dp_tsdf_stats;
+typedef struct dp_mesh_stats {
+    int64_t active_cells, vertices, triangles;
+    double mesh_ms;
+} dp_mesh_stats;
+
+/* min_weight = 1, flags = 0, everything else 0: an unfilled struct is rejected */
+void dp_default_tsdf_options(dp_tsdf_options *to);
+int dp_tsdf_integrate(dp_ctx *ctx, const int32_t *views, int n_views, const dp_tsdf_options *opts,
+                      const float *const *depth, float *tsdf, int32_t *weight, uint32_t *rgb, dp_tsdf_stats *stats);
+int dp_tsdf_integrate_device(dp_ctx *ctx, const int32_t *views, int n_views, const dp_tsdf_options *opts,
+                             const float *const *d_depth, float *d_tsdf, int32_t *d_weight, uint32_t *d_rgb,
+                             dp_tsdf_stats *stats, void *stream);
+int dp_tsdf_mesh(dp_ctx *ctx, const dp_tsdf_options *opts, const float *tsdf, const int32_t *weight,
+                 const uint32_t *rgb /* NULL: vertex colour 0 */, const dp_mesh_vertex **vertices,
+                 int64_t *n_vertices, const int32_t **triangles, int64_t *n_triangles, dp_mesh_stats *stats);
+int dp_tsdf_mesh_device(dp_ctx *ctx, const dp_tsdf_options *opts, const float *d_tsdf, const int32_t *d_weight,
+                        const uint32_t *d_rgb, dp_mesh_vertex *d_vertices, int64_t vertex_cap, int64_t *n_vertices,
+                        int32_t *d_triangles, int64_t triangle_cap, int64_t *n_triangles, dp_mesh_stats *stats,
+                        void *stream);
+
 /* ---- seed generation: Features::Matcher::GenerateSeeds ---
  * modules/features/matcher.cpp:18-43 with the default MatcherOptions
  * (matcher.h:21-32: ORB detector, kNN matcher, no direct epipolar matching,

@@ -40,6 +40,15 @@ void usage()
                  "                             rendered maps before --depth-maps writes them -- then also\n"
                  "                             score_%%04d.pfm -- and before --fuse fuses them; W = odd\n"
                  "                             window side 3..11, default 7; T = least score, default 0.5)\n"
+                 "               [--mesh FILE.ply [--mesh-dim N] [--mesh-voxel S] [--mesh-trunc T]\n"
+                 "                [--mesh-min-weight M]]  (after those: the depth maps of every view,\n"
+                 "                             rendered -- and refined, with --refine-maps -- on the device,\n"
+                 "                             integrated into one TSDF volume around the written patches\n"
+                 "                             and meshed by marching tetrahedra -- dp_tsdf_integrate,\n"
+                 "                             dp_tsdf_mesh; N = voxels along the patches' longest side,\n"
+                 "                             2..1024, default 256; S = voxel side, default that side / N;\n"
+                 "                             T = truncation, default 4 S; M = least views per voxel,\n"
+                 "                             1..64, default 2)\n"
                  "       densify --synthetic V,W,H,KIND --write-scene DIR\n");
 }
 
@@ -164,6 +173,28 @@ Parse parse_args(int argc, char **argv, Args &a, std::string &error)
                 a.refine_min_ncc = t;
             else
                 error = "--refine-min-ncc expects a number in -1..1";
+        } else if (o == "--mesh") {
+            a.mesh_path = v;
+        } else if (o == "--mesh-dim") {
+            if (int_in_range(v, 2, 1024, k))
+                a.mesh_dim = (int)k;
+            else
+                error = "--mesh-dim expects 2..1024";
+        } else if (o == "--mesh-voxel") {
+            if (number_in_range(v, 0.0, 3.0e38, t) && t > 0.0)
+                a.mesh_voxel = t;
+            else
+                error = "--mesh-voxel expects a finite number > 0";
+        } else if (o == "--mesh-trunc") {
+            if (number_in_range(v, 0.0, 3.0e38, t) && t > 0.0)
+                a.mesh_trunc = t;
+            else
+                error = "--mesh-trunc expects a finite number > 0";
+        } else if (o == "--mesh-min-weight") {
+            if (int_in_range(v, 1, 64, k))
+                a.mesh_min_weight = (int)k;
+            else
+                error = "--mesh-min-weight expects 1..64";
         } else if (o == "--exchange") {
             a.exchange_mode = v;
             if (one_of(v, {"auto", "rccl", "copy"}) < 0)

@@ -27,6 +27,12 @@ struct Args {
     int refine_passes = 0;
     int refine_window = 0;        // 0: the library's default
     double refine_min_ncc = -2.0; // < -1: the library's default
+    // --mesh FILE.ply: dp_tsdf_integrate + dp_tsdf_mesh on the (refined) maps
+    std::string mesh_path;
+    int mesh_dim = 256;           // voxels along the patches' longest side
+    double mesh_voxel = 0.0;      // 0: that side / mesh_dim
+    double mesh_trunc = 0.0;      // 0: 4 voxels
+    int mesh_min_weight = 2;
 
     Args();
 };

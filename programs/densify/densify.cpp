@@ -15,8 +15,10 @@
 
 #include <hip/hip_runtime_api.h>
 
+#include <algorithm>
 #include <cerrno>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <memory>
@@ -404,24 +406,37 @@ std::string write_depth_maps(dp_ctx *ctx, const Args &args, int32_t V, const std
     return buf;
 }
 
-// --fuse: depth and normal maps of every view rendered into device planes
-// (dp_render_maps_device, honouring --splat-scale) and fused there
-// (dp_fuse_maps_device); only the points come back.  An empty pixel is
-// never emitted, so the render's covered pixels size the point buffer;
-// should the fusion report more, it is reallocated once and re-run.
-// Returns the report's "fused" member.
-std::string write_fused(dp_ctx *ctx, const Args &args, int32_t V, const std::vector<dp_patch> &kept)
-{
+// The first stage of --fuse and --mesh alike: depth and normal maps of every
+// view rendered into device planes (dp_render_maps_device, honouring
+// --splat-scale) and, with --refine-maps N, refined there.  DeviceMaps owns the
+// planes (and whatever else its user allocates through bytes()); `cap` bounds
+// the pixels that hold a depth.
+struct DeviceMaps {
     std::vector<dpk::DevMem> mem;
-    auto device_bytes = [&mem](size_t bytes) {
+    std::vector<int32_t> vid;
+    std::vector<float *> depth, normal;
+    int64_t cap = 0;
+    std::string refined; // the report's member of --refine-maps, empty without it
+
+    void *bytes(size_t n, const char *who)
+    {
         mem.emplace_back();
-        if (mem.back().alloc(bytes ? bytes : 1) != hipSuccess)
-            throw std::runtime_error("--fuse: out of device memory");
+        if (mem.back().alloc(n ? n : 1) != hipSuccess)
+            throw std::runtime_error(std::string(who) + ": out of device memory");
         return mem.back().p;
-    };
+    }
+};
+
+void render_device_maps(dp_ctx *ctx, const Args &args, int32_t V, const std::vector<dp_patch> &kept, const char *who,
+                        const char *refined_name, DeviceMaps &m)
+{
+    auto device_bytes = [&m, who](size_t bytes) { return m.bytes(bytes, who); };
     check(ctx, hipSetDevice(args.device) == hipSuccess ? DP_OK : DP_E_HIP, "hipSetDevice");
-    std::vector<int32_t> vid((size_t)V);
-    std::vector<float *> dd((size_t)V), dn((size_t)V);
+    std::vector<int32_t> &vid = m.vid;
+    std::vector<float *> &dd = m.depth, &dn = m.normal;
+    vid.resize((size_t)V);
+    dd.resize((size_t)V);
+    dn.resize((size_t)V);
     for (int32_t v = 0; v < V; ++v) {
         int32_t w = 0, h = 0;
         check(ctx, dp_level_info(ctx, args.level, v, &w, &h, nullptr), "dp_level_info");
@@ -432,17 +447,16 @@ std::string write_fused(dp_ctx *ctx, const Args &args, int32_t V, const std::vec
     dp_patch *d_pat = (dp_patch *)device_bytes(kept.size() * sizeof(dp_patch));
     if (!kept.empty() &&
         hipMemcpy(d_pat, kept.data(), kept.size() * sizeof(dp_patch), hipMemcpyHostToDevice) != hipSuccess)
-        throw std::runtime_error("--fuse: copy of the patches failed");
+        throw std::runtime_error(std::string(who) + ": copy of the patches failed");
     const dp_render_options ro = render_options(args);
     dp_render_stats rs;
     check(ctx,
           dp_render_maps_device(ctx, kept.empty() ? nullptr : d_pat, (int64_t)kept.size(), nullptr, vid.data(), V, &ro,
                                 dd.data(), nullptr, dn.data(), nullptr, &rs, nullptr),
           "dp_render_maps_device");
-    int64_t cap = rs.covered_pixels, n_fused = 0;
-    // --refine-maps N: N passes between the render and the fusion, into a
-    // second set of planes and back; a pixel that is not kept is never emitted
-    std::string refined;
+    m.cap = rs.covered_pixels;
+    // --refine-maps N: N passes between the render and its user, into a
+    // second set of planes and back; a pixel that is not kept holds no depth
     if (args.refine_passes > 0) {
         const dp_mapref_options mo = mapref_options(args);
         std::vector<float *> dd2((size_t)V), dn2((size_t)V);
@@ -463,13 +477,27 @@ std::string write_fused(dp_ctx *ctx, const Args &args, int32_t V, const std::vec
             dd.swap(dd2);
             dn.swap(dn2);
         }
-        cap = ms.kept;
-        refined = refined_report("refined", args.refine_passes, ms, refine_ms);
+        m.cap = ms.kept;
+        m.refined = refined_report(refined_name, args.refine_passes, ms, refine_ms);
     }
+}
+
+// --fuse: the device maps fused there (dp_fuse_maps_device); only the points
+// come back.  An empty pixel is never emitted, so the pixels that hold a depth
+// size the point buffer; should the fusion report more, it is reallocated once
+// and re-run.  Returns the report's "fused" member.
+std::string write_fused(dp_ctx *ctx, const Args &args, int32_t V, const std::vector<dp_patch> &kept)
+{
+    DeviceMaps m;
+    render_device_maps(ctx, args, V, kept, "--fuse", "refined", m);
+    const std::vector<int32_t> &vid = m.vid;
+    const std::vector<float *> &dd = m.depth, &dn = m.normal;
+    const std::string &refined = m.refined;
+    int64_t cap = m.cap, n_fused = 0;
     dp_fuse_stats fs;
     dp_fused_point *d_pts = nullptr;
     for (int attempt = 0; attempt < 2; ++attempt) {
-        d_pts = (dp_fused_point *)device_bytes((size_t)cap * sizeof(dp_fused_point));
+        d_pts = (dp_fused_point *)m.bytes((size_t)cap * sizeof(dp_fused_point), "--fuse");
         check(ctx,
               dp_fuse_maps_device(ctx, vid.data(), V, &args.fuse, dd.data(), dn.data(), d_pts, cap, &n_fused, &fs,
                                   nullptr),
@@ -490,6 +518,88 @@ std::string write_fused(dp_ctx *ctx, const Args &args, int32_t V, const std::vec
                   ", \"fused\": {\"points\": %lld, \"fusable\": %lld, \"depth_pixels\": %lld, \"fuse_ms\": %.3f}",
                   (long long)n_fused, (long long)fs.fusable, (long long)fs.depth_pixels, fs.fuse_ms);
     return refined + buf;
+}
+
+// --mesh: the device maps integrated into one TSDF volume around the written
+// patches (dp_tsdf_integrate_device) and meshed there (dp_tsdf_mesh_device,
+// once for the counts and once into buffers of that size); only the mesh comes
+// back.  The volume is the patches' bounding box padded by the truncation;
+// the voxel defaults to the box's longest side / --mesh-dim, the truncation to
+// four voxels.  Returns the report's "mesh" member.
+std::string write_mesh(dp_ctx *ctx, const Args &args, int32_t V, const std::vector<dp_patch> &kept)
+{
+    double lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
+    bool any = false;
+    for (const dp_patch &p : kept) {
+        if (!(std::isfinite(p.pos[0]) && std::isfinite(p.pos[1]) && std::isfinite(p.pos[2])))
+            continue;
+        for (int a = 0; a < 3; ++a) {
+            lo[a] = any ? std::min(lo[a], (double)p.pos[a]) : (double)p.pos[a];
+            hi[a] = any ? std::max(hi[a], (double)p.pos[a]) : (double)p.pos[a];
+        }
+        any = true;
+    }
+    if (!any)
+        throw std::runtime_error("--mesh: no patches to bound the volume");
+    const double side = std::max(hi[0] - lo[0], std::max(hi[1] - lo[1], hi[2] - lo[2]));
+    const double voxel = args.mesh_voxel > 0.0 ? args.mesh_voxel : side / args.mesh_dim;
+    if (!(voxel > 0.0))
+        throw std::runtime_error("--mesh: the patches have no extent (give --mesh-voxel)");
+    const double trunc = args.mesh_trunc > 0.0 ? args.mesh_trunc : 4.0 * voxel;
+    dp_tsdf_options to;
+    dp_default_tsdf_options(&to);
+    to.voxel = (float)voxel;
+    to.trunc = (float)trunc;
+    to.min_weight = args.mesh_min_weight;
+    for (int a = 0; a < 3; ++a) {
+        to.origin[a] = (float)(lo[a] - trunc);
+        to.dim[a] = (int32_t)std::min(std::max(std::ceil((hi[a] - lo[a] + 2.0 * trunc) / voxel), 2.0), 1024.0);
+    }
+    DeviceMaps m;
+    render_device_maps(ctx, args, V, kept, "--mesh", "mesh_refined", m);
+    const size_t points = (size_t)to.dim[0] * to.dim[1] * to.dim[2];
+    float *d_tsdf = (float *)m.bytes(points * 4, "--mesh");
+    int32_t *d_weight = (int32_t *)m.bytes(points * 4, "--mesh");
+    uint32_t *d_rgb = (uint32_t *)m.bytes(points * 4, "--mesh");
+    dp_tsdf_stats ts;
+    check(ctx,
+          dp_tsdf_integrate_device(ctx, m.vid.data(), V, &to, m.depth.data(), d_tsdf, d_weight, d_rgb, &ts, nullptr),
+          "dp_tsdf_integrate_device");
+    int64_t nv = 0, nt = 0;
+    dp_mesh_stats ms;
+    check(ctx, dp_tsdf_mesh_device(ctx, &to, d_tsdf, d_weight, d_rgb, nullptr, 0, &nv, nullptr, 0, &nt, &ms, nullptr),
+          "dp_tsdf_mesh_device");
+    const int64_t vcap = nv, tcap = nt;
+    dp_mesh_vertex *d_verts = (dp_mesh_vertex *)m.bytes((size_t)vcap * sizeof(dp_mesh_vertex), "--mesh");
+    int32_t *d_tris = (int32_t *)m.bytes((size_t)tcap * 3 * sizeof(int32_t), "--mesh");
+    check(ctx,
+          dp_tsdf_mesh_device(ctx, &to, d_tsdf, d_weight, d_rgb, vcap ? d_verts : nullptr, vcap, &nv,
+                              tcap ? d_tris : nullptr, tcap, &nt, &ms, nullptr),
+          "dp_tsdf_mesh_device");
+    if (nv != vcap || nt != tcap)
+        throw std::runtime_error("--mesh: the counts changed between two runs");
+    std::vector<dp_mesh_vertex> verts((size_t)nv);
+    std::vector<int32_t> tris((size_t)nt * 3);
+    if ((nv > 0 && hipMemcpy(verts.data(), d_verts, verts.size() * sizeof(dp_mesh_vertex), hipMemcpyDeviceToHost) !=
+                       hipSuccess) ||
+        (nt > 0 && hipMemcpy(tris.data(), d_tris, tris.size() * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess))
+        throw std::runtime_error("--mesh: copy of the mesh failed");
+    std::vector<dpio::MeshPoint> out(verts.size());
+    for (size_t i = 0; i < verts.size(); ++i)
+        for (int k = 0; k < 3; ++k) {
+            out[i].pos[k] = verts[i].pos[k];
+            out[i].rgb[k] = verts[i].rgb[k];
+        }
+    dpio::write_mesh_ply(args.mesh_path, out, tris);
+    char buf[400];
+    std::snprintf(buf, sizeof buf,
+                  ", \"mesh\": {\"vertices\": %lld, \"triangles\": %lld, \"ms\": %.3f, \"dim\": [%d, %d, %d], "
+                  "\"voxel\": %.9g, \"trunc\": %.9g, \"observed_voxels\": %lld, \"active_cells\": %lld, "
+                  "\"integrate_ms\": %.3f, \"mesh_ms\": %.3f}",
+                  (long long)nv, (long long)nt, ts.integrate_ms + ms.mesh_ms, to.dim[0], to.dim[1], to.dim[2],
+                  (double)to.voxel, (double)to.trunc, (long long)ts.observed_voxels, (long long)ms.active_cells,
+                  ts.integrate_ms, ms.mesh_ms);
+    return m.refined + buf;
 }
 
 using Clock = std::chrono::steady_clock;
@@ -583,6 +693,8 @@ int main(int argc, char **argv)
             extra += write_depth_maps(ctx.get(), args, V, kept);
         if (!args.fuse_path.empty())
             extra += write_fused(ctx.get(), args, V, kept);
+        if (!args.mesh_path.empty())
+            extra += write_mesh(ctx.get(), args, V, kept);
         ctx.reset(); // wall_ms includes the context's teardown
         print_report(args, res, kept.size(), sc.seeds.size() / 3, sst, t0, extra);
         return 0;

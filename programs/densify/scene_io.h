@@ -75,6 +75,15 @@ struct CloudPoint {
 // ASCII PLY exactly as PrintCloud writes it (%g floats, uchar colours)
 void write_ply(const std::string &path, const std::vector<CloudPoint> &pts);
 
+struct MeshPoint {
+    float pos[3];
+    uint8_t rgb[3];
+};
+
+// a triangle mesh as an ASCII PLY: vertex x y z (%.9g) red green blue, face
+// vertex_indices (list uchar int); tris holds three vertex numbers per triangle
+void write_mesh_ply(const std::string &path, const std::vector<MeshPoint> &verts, const std::vector<int32_t> &tris);
+
 // ---- image writers ----------------------------------------------------------
 // binary PPM (P6, RGB) of a BGR8 image
 void write_ppm(const std::string &path, int w, int h, const std::vector<uint8_t> &bgr);
