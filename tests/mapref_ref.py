@@ -217,7 +217,7 @@ def refine(vw, depth, normal, views=None, sources=None, window=7, sweep=2, step_
                 Xc = backproject_d(vw, r, xd[q], yd[q], zc[q])
                 Xi = backproject_d(vw, r, xd[q] + 1.0, yd[q], zi[q])
                 Xj = backproject_d(vw, r, xd[q], yd[q] + 1.0, zj[q])
-            ncc = np.full((len(q), max(len(src[k]), 1)), -np.inf)
+            ncc = np.full((len(q), max(len(src[k]), top_k)), -np.inf)  # fewer sources than top_k: no candidate
             nvalid = np.zeros(len(q), np.int64)
             for si, s in enumerate(src[k]):
                 ok, v = source_ncc(vw, r, s, x[q], y[q], Xc, Xi, Xj, window, Sa[q], Saa[q], Aref[q], dmin)
