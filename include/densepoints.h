@@ -1055,6 +1055,10 @@ int dp_read_gray(dp_ctx *ctx, int view, uint16_t *fp16_out);
 int dp_fast_expand_batch(dp_ctx *ctx, const dp_patch *parents, int n, dp_patch *children, uint8_t *accept_out);
 /* Work counters of the most recent performance-mode launch (device-counted; a
  * batch of device-resident densify generations counts as one launch):
+ * patches = the launch's patches (four per parent of an expansion, whether the
+ * parent expands or not); evals = the sum of their evals fields after the
+ * launch (children and seeds start at 0, so the launch's evaluations; a patch
+ * refined again brings its earlier count along);
  * view_evals = sum over patches and evaluations of the staged views sampled,
  * i.e. algorithmic bytes = view_evals * (n+1)^2 * 2 (fp16 texels);
  * staged_bytes = bytes the tiles copy from the gray planes (the compulsory

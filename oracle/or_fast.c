@@ -150,6 +150,7 @@ typedef struct fast_view {
     int view;
     int x0t, y0t, tw, th;  /* tile origin and size (pixels)           */
     int bytes;             /* LDS footprint: tile + record             */
+    int xa, xb, ya, yb;    /* the window's pixel box, before the margin */
     float g[5][3];         /* H0, Hd, He1, He2, Hn over the centre depth */
     float vec[5][3];       /* the same, relative to the tile origin    */
     float umax, vmax;      /* 32 * (tw - 1), 32 * (th - 1)             */
@@ -164,7 +165,23 @@ typedef struct fast_patch {
     float u1[3], u2[3], un[3];      /* the same, unit length                     */
     float sd, st;                   /* scaled-variable units                     */
     int degenerate;
+    /* what the staging settled on (or_fast_stage_probe, the work counters) */
+    int M;                          /* the margin that fitted the budget          */
+    int m0;                         /* staged views before the budget prefix      */
+    int tile_bytes;                 /* the kept tiles' bytes, without the records */
 } fast_patch;
+
+/* Work counters of a batch, defined as the kernel's (dp_fast_stats,
+ * include/densepoints.h; dp_fast_kernel.hip fast_kernel's main loop and stage):
+ * a staging is one fast_stage call of a non-degenerate patch. */
+static or_fast_stats g_last_stats;
+
+static void count_staging(or_fast_stats *st, const fast_patch *fp, int margin)
+{
+    if (fp->degenerate) return; /* the kernel does not stage a degenerate frame */
+    st->staged_bytes += fp->tile_bytes;
+    st->clipped_stagings += (fp->M < margin || fp->m < fp->m0) ? 1 : 0;
+}
 
 /* the patch frame (fp32) from the stored pose; 0 if degenerate */
 static int fast_frame(const or_scene *s, const or_patch *p, int cell, fast_patch *fp)
@@ -314,6 +331,9 @@ static int fast_stage(const or_scene *s, const or_patch *p, int cell, const or_f
     }
     int tot = 0, mm = 0;
     while (mm < m && tot + fp->fv[mm].bytes <= fo->tile_budget) tot += fp->fv[mm++].bytes;
+    fp->M = M;
+    fp->m0 = m;
+    fp->tile_bytes = tot - FAST_REC_BYTES * mm;
     m = mm;
     for (int k = 0; k < m; ++k) {
         fast_view *t = &fp->fv[k];
@@ -326,6 +346,10 @@ static int fast_stage(const or_scene *s, const or_patch *p, int cell, const or_f
         }
         t->umax = (float)(32 * (t->tw - 1));
         t->vmax = (float)(32 * (t->th - 1));
+        t->xa = geo[k].xa;
+        t->xb = geo[k].xb;
+        t->ya = geo[k].ya;
+        t->yb = geo[k].yb;
         t->tile = (uint16_t *)malloc(sizeof(uint16_t) * (size_t)(t->tw + 1) * t->th);
         for (int y = 0; y < t->th; ++y)
             for (int x = 0; x <= t->tw; ++x)
@@ -728,11 +752,13 @@ static int fast_cg(const fast_patch *fp, int cell, double dmin0, const or_fast_o
 
 /* fast filter: stage at the stored pose (margin 0), one evaluation; drop the
  * visible views whose NCC is below the threshold or that cannot be staged */
-static int fast_filter(const or_scene *s, or_patch *p, int cell, const or_fast_options *fo)
+static int fast_filter(const or_scene *s, or_patch *p, int cell, const or_fast_options *fo, or_fast_stats *st)
 {
     fast_patch fp;
     fast_stage(s, p, cell, fo, 0, filter_views(fo), &fp);
+    count_staging(st, &fp, 0);
     p->evals += 1;
+    if (fp.m >= 2) st->view_evals += fp.m;
     if (fp.degenerate) p->flags |= OR_FLAG_DEGENERATE;
     if (fp.m < 2) {
         /* only the anchor (or nothing) could be staged: it stays, unscored */
@@ -798,10 +824,12 @@ static void fast_init_related(const or_scene *s, or_patch *p)
 
 /* DP_MODE_FAST_REFINE: CG refine on the current visible set ->
  * InitRelatedImages (patch.cpp:19-49) -> fast filter */
-static int fast_refine_one(const or_scene *s, or_patch *p, int cell, const or_fast_options *fo)
+static int fast_refine_one(const or_scene *s, or_patch *p, int cell, const or_fast_options *fo, or_fast_stats *st)
 {
     fast_patch fp;
-    fast_stage(s, p, cell, fo, fo->margin < 7 ? fo->margin : 7, fo->max_views, &fp);
+    const int margin = fo->margin < 7 ? fo->margin : 7;
+    fast_stage(s, p, cell, fo, margin, fo->max_views, &fp);
+    count_staging(st, &fp, margin);
     if (fp.degenerate) {
         p->flags |= OR_FLAG_DEGENERATE;
         p->flags &= (uint8_t)~OR_FLAG_ACCEPTED;
@@ -810,7 +838,9 @@ static int fast_refine_one(const or_scene *s, or_patch *p, int cell, const or_fa
     }
     if (fp.m >= 2) {
         float x[3];
-        p->evals += (uint32_t)fast_cg(&fp, cell, s->opt.ncc_denom_min, fo, x);
+        const int E = fast_cg(&fp, cell, s->opt.ncc_denom_min, fo, x);
+        p->evals += (uint32_t)E;
+        st->view_evals += (int64_t)E * fp.m;
         const float d = x[0] * fp.sd, a = x[1] * fp.st, b = x[2] * fp.st;
         /* X' = X0 + d (X0 - C_ref); n' = normalize(n + a e1 + b e2) */
         float nrm[3];
@@ -823,17 +853,19 @@ static int fast_refine_one(const or_scene *s, or_patch *p, int cell, const or_fa
     }
     fast_free(&fp);
     fast_init_related(s, p);
-    int ok = fast_filter(s, p, cell, fo);
+    int ok = fast_filter(s, p, cell, fo, st);
     if (ok) p->flags |= OR_FLAG_ACCEPTED;
     else p->flags &= (uint8_t)~OR_FLAG_ACCEPTED;
     return ok;
 }
 
-static int fast_eval_one(const or_scene *s, or_patch *p, int cell, const or_fast_options *fo)
+static int fast_eval_one(const or_scene *s, or_patch *p, int cell, const or_fast_options *fo, or_fast_stats *st)
 {
     fast_patch fp;
     fast_stage(s, p, cell, fo, 0, filter_views(fo), &fp);
+    count_staging(st, &fp, 0);
     p->evals += 1;
+    if (fp.m >= 2) st->view_evals += fp.m;
     if (fp.degenerate) p->flags |= OR_FLAG_DEGENERATE;
     int ok = fp.m >= 2;
     if (ok) {
@@ -874,17 +906,27 @@ int or_fast_refine_batch(const or_scene *s, or_patch *p, int n, int cell, int mo
         or_fast_default_options(&d);
         fo = &d;
     }
+    /* the counters: per thread, summed (integers: any order gives the same) */
+    int64_t c_ev = 0, c_vev = 0, c_by = 0, c_cl = 0;
 #ifdef _OPENMP
     if (nthreads <= 0) nthreads = omp_get_max_threads();
-#pragma omp parallel for schedule(dynamic, 1) num_threads(nthreads)
+#pragma omp parallel for schedule(dynamic, 1) num_threads(nthreads) reduction(+ : c_ev, c_vev, c_by, c_cl)
 #endif
     for (int i = 0; i < n; ++i) {
-        int ok = mode == OR_MODE_FAST_EVAL ? fast_eval_one(s, &p[i], cell, fo) : fast_refine_one(s, &p[i], cell, fo);
+        or_fast_stats st = {0, 0, 0, 0, 0};
+        int ok = mode == OR_MODE_FAST_EVAL ? fast_eval_one(s, &p[i], cell, fo, &st)
+                                           : fast_refine_one(s, &p[i], cell, fo, &st);
         if (ok > 0) p[i].flags |= OR_FLAG_ACCEPTED;
         else p[i].flags &= (uint8_t)~OR_FLAG_ACCEPTED;
         if (accept) accept[i] = (uint8_t)(ok > 0);
+        c_ev += p[i].evals; /* as the kernel: the patch's count, what it came with included */
+        c_vev += st.view_evals;
+        c_by += st.staged_bytes;
+        c_cl += st.clipped_stagings;
     }
     (void)nthreads;
+    const or_fast_stats tot = {n > 0 ? n : 0, c_ev, c_vev, c_by, c_cl};
+    g_last_stats = tot;
     return 0;
 }
 
@@ -900,11 +942,13 @@ int or_fast_expand_batch(const or_scene *s, const or_patch *parents, int n, cons
         fo = &d;
     }
     const int cell = s->opt.expand_cell_size;
+    int64_t c_ev = 0, c_vev = 0, c_by = 0, c_cl = 0;
 #ifdef _OPENMP
     if (nthreads <= 0) nthreads = omp_get_max_threads();
-#pragma omp parallel for schedule(dynamic, 1) num_threads(nthreads)
+#pragma omp parallel for schedule(dynamic, 1) num_threads(nthreads) reduction(+ : c_ev, c_vev, c_by, c_cl)
 #endif
     for (int i = 0; i < n; ++i) {
+        or_fast_stats st = {0, 0, 0, 0, 0};
         int vis[OR_MAX_VIEWS];
         const or_patch *par = &parents[i];
         const int live = decode_mask(par->vis, vis) >= s->opt.min_expand_visible;
@@ -918,12 +962,42 @@ int or_fast_expand_batch(const or_scene *s, const or_patch *parents, int n, cons
             int ok = 0;
             if (live) {
                 for (int k = 0; k < 3; ++k) c.pos[k] = (float)pos[dd][k];
-                ok = fast_refine_one(s, &c, cell, fo);
+                ok = fast_refine_one(s, &c, cell, fo, &st);
             }
             children[4 * i + dd] = c;
             acc[4 * i + dd] = (uint8_t)(ok > 0);
+            c_ev += c.evals;
         }
+        c_vev += st.view_evals;
+        c_by += st.staged_bytes;
+        c_cl += st.clipped_stagings;
     }
     (void)nthreads;
+    /* every child is a patch of the launch, a dead parent's four included */
+    const or_fast_stats tot = {n > 0 ? 4 * (int64_t)n : 0, c_ev, c_vev, c_by, c_cl};
+    g_last_stats = tot;
     return 0;
+}
+
+void or_fast_last_stats(or_fast_stats *out) { *out = g_last_stats; }
+
+/* The staging of one patch as fast_stage settles it: returns the kept views m
+ * (0 for a degenerate frame), *M the margin, *m0 the staged views before the
+ * budget prefix, tiles[k] the kept views' rectangles (k < m <= 32). */
+int or_fast_stage_probe(const or_scene *s, const or_patch *p, int cell, const or_fast_options *fo, int margin,
+                        int max_views, int32_t *M, int32_t *m0, or_fast_tile *tiles)
+{
+    if (cell < 2 || cell > 16 || !fo) return -1;
+    fast_patch fp;
+    fast_stage(s, p, cell, fo, margin, max_views, &fp);
+    const int m = fp.degenerate ? 0 : fp.m;
+    *M = fp.degenerate ? 0 : fp.M;
+    *m0 = fp.degenerate ? 0 : fp.m0;
+    for (int k = 0; k < m; ++k) {
+        const fast_view *t = &fp.fv[k];
+        const or_fast_tile o = {t->view, t->x0t, t->y0t, t->tw, t->th, t->bytes, t->xa, t->xb, t->ya, t->yb};
+        tiles[k] = o;
+    }
+    fast_free(&fp);
+    return m;
 }

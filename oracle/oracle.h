@@ -143,6 +143,33 @@ int or_fast_refine_batch(const or_scene *s, or_patch *p, int n, int cell, int mo
 int or_fast_expand_batch(const or_scene *s, const or_patch *parents, int n, const or_fast_options *fo,
                          or_patch *children, uint8_t *acc, int nthreads);
 
+/* Work counters of the most recent or_fast_refine_batch / or_fast_expand_batch
+ * (one "launch"), defined as the kernel's dp_fast_stats (include/densepoints.h):
+ *   patches           the batch's patches (4 per parent, dead parents included)
+ *   evals             the sum of the patches' evals after the batch (children and
+ *                     seeds start at 0: the batch's evaluations)
+ *   view_evals        E m per refine with m >= 2 staged views, plus m per
+ *                     scoring staging (filter, FAST_EVAL) with m >= 2
+ *   staged_bytes      over the stagings, the kept tiles' 4 ((tw+2)/2) (th+1)
+ *                     (without the 64-byte record)
+ *   clipped_stagings  stagings whose margin was reduced or whose budget prefix
+ *                     dropped a staged view
+ * Accumulated per thread and summed; not safe against concurrent batches. */
+typedef struct or_fast_stats {
+    int64_t patches, evals, view_evals, staged_bytes, clipped_stagings;
+} or_fast_stats;
+void or_fast_last_stats(or_fast_stats *out);
+/* One patch's staging (fast_stage itself): returns the kept views m, *M the
+ * margin that fitted, *m0 the staged views before the budget prefix, and per
+ * kept view its tile; bytes is the LDS footprint, tile + 64-byte record;
+ * (xa, xb, ya, yb) is the window's pixel box that the margin grows. */
+typedef struct or_fast_tile {
+    int32_t view, x0t, y0t, tw, th, bytes;
+    int32_t xa, xb, ya, yb;
+} or_fast_tile;
+int or_fast_stage_probe(const or_scene *s, const or_patch *p, int cell, const or_fast_options *fo, int margin,
+                        int max_views, int32_t *M, int32_t *m0, or_fast_tile *tiles);
+
 #ifdef __cplusplus
 }
 #endif

@@ -110,6 +110,8 @@ def _load():
         "or_fast_expand_batch": (ctypes.c_int, [P, P, ctypes.c_int, P, P, P, ctypes.c_int]),
         "or_fast_grad_probe": (ctypes.c_int, [P, P, ctypes.c_int, P, P, P]),
         "or_fast_grad_q24": (ctypes.c_int32, [ctypes.c_double]),
+        "or_fast_last_stats": (None, [P]),
+        "or_fast_stage_probe": (ctypes.c_int, [P, P, ctypes.c_int, P, ctypes.c_int, ctypes.c_int, P, P, P]),
         "or_trace_set": (None, [P, ctypes.c_int64]),
         "or_trace_count": (ctypes.c_int64, []),
         # seed generation (or_seeds.c)
@@ -276,6 +278,34 @@ def _scene_fast_grad_probe(self, patch, cell, fo=None):
     return m, f.value, g
 
 
+FAST_STATS = ("patches", "evals", "view_evals", "staged_bytes", "clipped_stagings")
+FAST_TILE_DTYPE = np.dtype([(k, "<i4") for k in ("view", "x0t", "y0t", "tw", "th", "bytes", "xa", "xb", "ya", "yb")])
+
+
+def fast_last_stats() -> dict:
+    """or_fast_stats of the most recent fast_refine / fast_expand: the work
+    counters as the kernel defines them (dp_fast_last_stats)."""
+    a = np.zeros(5, dtype=np.int64)
+    lib.or_fast_last_stats(_p(a))
+    return dict(zip(FAST_STATS, (int(x) for x in a)))
+
+
+def _scene_fast_stage_probe(self, patch, cell, fo=None, margin=0, max_views=32):
+    """One patch's staging by the oracle's fast_stage: (M, m0, tiles) -- the
+    margin that fitted, the staged views before the budget prefix and the kept
+    views' tiles (FAST_TILE_DTYPE; bytes = tile + 64-byte record; xa .. yb =
+    the window's pixel box before the margin)."""
+    fo = fast_options() if fo is None else fast_options(fo)
+    one = np.ascontiguousarray(np.asarray(patch).reshape(1))
+    M, m0 = ctypes.c_int32(), ctypes.c_int32()
+    tiles = np.zeros(32, dtype=FAST_TILE_DTYPE)
+    m = lib.or_fast_stage_probe(self._h, _p(one), cell, ctypes.byref(fo), margin, max_views, ctypes.byref(M),
+                                ctypes.byref(m0), _p(tiles))
+    if m < 0:
+        raise ValueError("or_fast_stage_probe failed")
+    return M.value, m0.value, tiles[:m].copy()
+
+
 def _scene_gray(self, view):
     W, H = self._keep[1][view], self._keep[2][view]
     out = np.zeros((H, W), dtype=np.uint8)
@@ -286,6 +316,7 @@ def _scene_gray(self, view):
 Scene.fast_refine = _scene_fast_refine
 Scene.fast_expand = _scene_fast_expand
 Scene.fast_grad_probe = _scene_fast_grad_probe
+Scene.fast_stage_probe = _scene_fast_stage_probe
 Scene.gray = _scene_gray
 
 
@@ -325,15 +356,22 @@ class GenerationEngine:
         self.org = None
         self._P = scene._keep[0]
         self.fast = None if fast is None else fast_options(fast)
+        # performance mode: the work counters of every refine call, in order
+        # (fast_last_stats; one entry per densify_refine / densify_refine_items)
+        self.fast_stats = []
 
     def _refine_seeds(self, r, cell):
         if self.fast is not None:
-            return self.S.fast_refine(r, cell, MODE_FAST_REFINE, self.fast, self.threads)
+            acc = self.S.fast_refine(r, cell, MODE_FAST_REFINE, self.fast, self.threads)
+            self.fast_stats.append(fast_last_stats())
+            return acc
         return self.S.refine(r, cell, 3, self.threads)  # MODE_SEED
 
     def _expand(self, parents):
         if self.fast is not None:
-            return self.S.fast_expand(parents, self.fast, self.threads)
+            out = self.S.fast_expand(parents, self.fast, self.threads)
+            self.fast_stats.append(fast_last_stats())
+            return out
         return self.S.expand(parents, self.threads)
 
     def densify_all(self, seeds):

@@ -93,12 +93,18 @@ def _i32(x):
     return ((int(x) + 2 ** 31) % 2 ** 32) - 2 ** 31
 
 
-def _fast_eval_numpy(orc, S, P, imgs, p, cell, fo, grad=False):
-    """Independent statement of DP_MODE_FAST_EVAL's score (include/densepoints.h
-    dp_fast_options, spec v3: fp32 frame and view geometry, margin 0): returns
-    the mean NCC or -1.  grad: spec v4's objective and analytic gradient at
-    the staged pose instead (or_fast.c fast_objective_grad), (m, f, g)."""
-    V = len(imgs)
+def _fast_stage_numpy(orc, P, sizes, p, cell, tile_budget, margin, cap):
+    """Independent statement of the staging (include/densepoints.h dp_fast_options
+    "staging"; or_fast.c fast_stage): the fp32 frame, the usable views in
+    ascending visible order (at most cap), the largest margin M <= margin whose
+    footprints fit tile_budget, then the longest fitting prefix of views.
+    sizes: [(W, H)] per view.  Returns None for a degenerate frame, else a dict:
+    M, m0 (staged views before the prefix), tiles [(view, x0t, y0t, tw, th,
+    bytes, xa, xb, ya, yb)] and g (the five columns) of the kept views, sd, st,
+    and dropped [(view, reason, miss_px)]: the visible views that were
+    considered and not staged ("inside": the window box fails IsPointInside by
+    miss_px pixels)."""
+    V = len(sizes)
     cams = [_fcam(orc, P, v) for v in range(V)]
     lo, hi = _f(2.0 ** -20), _f(2.0 ** 64)
 
@@ -116,12 +122,12 @@ def _fast_eval_numpy(orc, S, P, imgs, p, cell, fo, grad=False):
     n0 = p["normal"].astype(np.float32)
     a, b = proj(ref, X), proj(ref, (X + xr).astype(np.float32))
     if a is None or b is None:
-        return -1.0
+        return None
     du, dv = b[0] - a[0], b[1] - a[1]
     dx = np.sqrt(_fmaf(dv, dv, du * du))
     nl = np.sqrt(_fdot(n0, n0))
     if not (dx > 0 and dx <= 2.0 ** 100 and nl > 0):
-        return -1.0
+        return None
     ps = _f(32.0) / dx
     inl = _f(1.0) / nl
     nn = (n0 * inl).astype(np.float32)
@@ -129,22 +135,28 @@ def _fast_eval_numpy(orc, S, P, imgs, p, cell, fo, grad=False):
     e1 = np.array([_fmaf(-xn, nn[k], xr[k]) for k in range(3)], dtype=np.float32)
     el = np.sqrt(_fdot(e1, e1))
     if not el > 0:
-        return -1.0
+        return None
     e1 = (e1 * (_f(1.0) / el)).astype(np.float32)
     e2 = np.array([_fmaf(nn[1], e1[2], -(nn[2] * e1[1])), _fmaf(nn[2], e1[0], -(nn[0] * e1[2])),
                    _fmaf(nn[0], e1[1], -(nn[1] * e1[0]))], dtype=np.float32)
     r = (X - Cr).astype(np.float32)
-    sd = ps / np.sqrt(_fdot(r, r))
+    rl = np.sqrt(_fdot(r, r))
+    if not rl > 0:
+        return None
+    sd = ps / rl
     st = _f(2.0) / _f(cell - 1)
     ws = [r, (e1 * ps).astype(np.float32), (e2 * ps).astype(np.float32), (nn * ps).astype(np.float32)]
     c = _f(0.5) * _f(cell - 1)
     vis = [v for v in range(V) if (int(p["vis"][v >> 6]) >> (v & 63)) & 1][:64]
-    staged = []
+    usable, dropped = [], []
     for v in vis:
+        if len(usable) == min(cap, 32):
+            break
         Q = cams[v][0]
         H = [[_qpt(Q, k, X) for k in range(3)]] + [[_qdir(Q, k, w) for k in range(3)] for w in ws]
         s = H[0][2]
         if not (lo <= s <= hi):
+            dropped.append((v, "depth", 0.0))
             continue
         inv = _f(1.0) / s
         g = [np.array([h[0] * inv, h[1] * inv, h[2] * inv], dtype=np.float32) for h in H]
@@ -154,29 +166,59 @@ def _fast_eval_numpy(orc, S, P, imgs, p, cell, fo, grad=False):
         eu, ev = c * (abs(Ui) + abs(Uj)), c * (abs(Vi) + abs(Vj))
         ez = c * (abs(g[2][2]) + abs(g[3][2]))
         umin, umax, vmin, vmax = U0 - eu, U0 + eu, V0 - ev, V0 + ev
-        Hh, Ww = imgs[v].shape[:2]
+        Ww, Hh = sizes[v]
         if not (g[0][2] - ez > 0):
+            dropped.append((v, "corner depth", 0.0))
             continue
         if not (umin > 0 and umax < _f(32 * Ww) and vmin > 0 and vmax < _f(32 * Hh)):
+            miss = max(-float(umin), float(umax) - 32.0 * Ww, -float(vmin), float(vmax) - 32.0 * Hh) / 32.0
+            dropped.append((v, "inside", miss))
             continue
         xa, xb = int(np.floor(umin * _f(0.03125))), int(np.floor(umax * _f(0.03125))) + 1
         ya, yb = int(np.floor(vmin * _f(0.03125))), int(np.floor(vmax * _f(0.03125))) + 1
         if xb - xa + 1 > 48 or yb - ya + 1 > 48:
+            dropped.append((v, "box", 0.0))
             continue
-        x0, y0 = max(xa, 0) & ~1, max(ya, 0)  # even left edge (32-bit fp16 pairs on the device)
-        tw, th = min(xb, Ww - 1) - x0 + 1, min(yb, Hh - 1) - y0 + 1
-        staged.append((v, g, x0, y0, tw, th, 4 * ((tw + 2) // 2) * (th + 1) + 64))
-        # spec v5: the scoring staging (FAST_EVAL) takes up to filter_max_views
-        # views (0 = max_views), the refine's (the gradient probe) max_views
-        cap = fo.max_views if grad else (fo.filter_max_views or fo.max_views)
-        if len(staged) == cap:
-            break
+        usable.append((v, g, xa, xb, ya, yb))
+
+    def rects(M):
+        out = []
+        for v, g, xa, xb, ya, yb in usable:
+            Ww, Hh = sizes[v]
+            x0, y0 = max(xa - M, 0), max(ya - M, 0)
+            x0 -= x0 % 2  # even left edge (the device copies rows as 32-bit fp16 pairs)
+            tw, th = min(xb + M, Ww - 1) - x0 + 1, min(yb + M, Hh - 1) - y0 + 1
+            out.append((v, x0, y0, tw, th, 4 * ((tw + 2) // 2) * (th + 1) + 64, xa, xb, ya, yb))
+        return out
+
+    # the margin loop, then the budget prefix
+    M = margin
+    while sum(t[5] for t in rects(M)) > tile_budget and M > 0:
+        M -= 1
     tot, keep = 0, []
-    for t in staged:
-        if tot + t[6] > fo.tile_budget:
+    for t in rects(M):
+        if tot + t[5] > tile_budget:
             break
-        tot += t[6]
+        tot += t[5]
         keep.append(t)
+    return dict(M=M, m0=len(usable), tiles=keep, g=[u[1] for u in usable[:len(keep)]], sd=sd, st=st, dropped=dropped)
+
+
+def _fast_eval_numpy(orc, S, P, imgs, p, cell, fo, grad=False):
+    """Independent statement of DP_MODE_FAST_EVAL's score (include/densepoints.h
+    dp_fast_options, spec v3: fp32 frame and view geometry, margin 0): returns
+    the mean NCC or -1.  grad: spec v4's objective and analytic gradient at
+    the staged pose instead (or_fast.c fast_objective_grad), (m, f, g)."""
+    sizes = [(im.shape[1], im.shape[0]) for im in imgs]
+    # spec v5: the scoring staging (FAST_EVAL) takes up to filter_max_views
+    # views (0 = max_views), the refine's (the gradient probe) max_views
+    cap = fo.max_views if grad else (fo.filter_max_views or fo.max_views)
+    stg = _fast_stage_numpy(orc, P, sizes, p, cell, fo.tile_budget, 0, cap)
+    if stg is None:
+        return -1.0
+    sd, st = stg["sd"], stg["st"]
+    c = _f(0.5) * _f(cell - 1)
+    keep = [(t[0], g) + tuple(t[1:6]) for t, g in zip(stg["tiles"], stg["g"])]
     if len(keep) < 2:
         return (len(keep), None, None) if grad else -1.0
     N = cell * cell
