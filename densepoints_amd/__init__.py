@@ -19,6 +19,7 @@ from ._native import (  # noqa: F401
     DensePointsError,
     FUSED_DTYPE,
     LIB_PATH,
+    MESH_COMPONENT_DTYPE,
     MESH_VERTEX_DTYPE,
 )
 from .pmvs import (  # noqa: F401
@@ -29,6 +30,7 @@ from .pmvs import (  # noqa: F401
     View,
     check_fuse_args,
     check_mapref_args,
+    check_mesh_clean_args,
     check_tsdf_args,
     empty_patches,
     mask_from_list,

@@ -257,6 +257,37 @@ MESH_VERTEX_DTYPE = np.dtype([("pos", "<f4", 3), ("rgb", "u1", 3), ("pad", "u1")
 assert MESH_VERTEX_DTYPE.itemsize == 16
 
 
+class DpMeshCleanOptions(ctypes.Structure):
+    """dp_mesh_clean_options: the selection of dp_mesh_clean (include/densepoints.h)."""
+    _fields_ = [
+        ("min_triangles", ctypes.c_int64),
+        ("min_fraction", ctypes.c_float),
+        ("max_components", ctypes.c_int32),
+        ("flags", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
+    ]
+
+
+class DpMeshCleanStats(ctypes.Structure):
+    _fields_ = [
+        ("vertices_in", ctypes.c_int64),
+        ("triangles_in", ctypes.c_int64),
+        ("invalid_triangles", ctypes.c_int64),
+        ("unused_vertices", ctypes.c_int64),
+        ("components", ctypes.c_int64),
+        ("largest_triangles", ctypes.c_int64),
+        ("components_kept", ctypes.c_int64),
+        ("vertices_out", ctypes.c_int64),
+        ("triangles_out", ctypes.c_int64),
+        ("clean_ms", ctypes.c_double),
+    ]
+
+
+# dp_mesh_component (include/densepoints.h) -- 16 bytes
+MESH_COMPONENT_DTYPE = np.dtype([("root", "<i4"), ("vertices", "<i4"), ("triangles", "<i4"), ("rank", "<i4")])
+assert MESH_COMPONENT_DTYPE.itemsize == 16 and ctypes.sizeof(DpMeshCleanOptions) == 24
+
+
 class DpSynthConfig(ctypes.Structure):
     _fields_ = [
         ("n_views", ctypes.c_int32),
@@ -391,6 +422,12 @@ SIGNATURES = [
     ("dp_tsdf_integrate_device", _I, [_P, _P, _I, _P, _P, _P, _P, _P, _P, _P]),
     ("dp_tsdf_mesh", _I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     ("dp_tsdf_mesh_device", _I, [_P, _P, _P, _P, _P, _P, ctypes.c_int64, _P, _P, ctypes.c_int64, _P, _P, _P]),
+    ("dp_default_mesh_clean_options", None, [_P]),
+    ("dp_mesh_components", _I, [_P, _P, ctypes.c_int64, ctypes.c_int64, _P, _P, _P, _P, _P]),
+    ("dp_mesh_components_device", _I, [_P, _P, ctypes.c_int64, ctypes.c_int64, _P, _P, _P, ctypes.c_int64, _P, _P, _P]),
+    ("dp_mesh_clean", _I, [_P, _P, _P, ctypes.c_int64, _P, ctypes.c_int64, _P, _P, _P, _P, _P, _P, _P]),
+    ("dp_mesh_clean_device", _I, [_P, _P, _P, ctypes.c_int64, _P, ctypes.c_int64, _P, ctypes.c_int64, _P, _P,
+                                  ctypes.c_int64, _P, _P, _P, _P, _P]),
     ("dp_last_kernel_ms", _I, [_P, _P]),
     ("dp_default_matcher_options", None, [_P]),
     ("dp_orb_pattern", _I, [_P]),

@@ -5,7 +5,7 @@
 // probes; dp_seeds_capi.hip, dp_seeds_orb.hip, dp_seeds_akaze.hip: seed
 // generation (their own state is dp_seedgen.h); dp_render.hip: maps;
 // dp_fuse.hip: their fusion; dp_mapref.hip: their refinement; dp_tsdf.hip:
-// their volume and mesh).  Every member that owns a device or pinned
+// their volume and mesh; dp_meshclean.hip: the mesh's components).  Every member that owns a device or pinned
 // allocation or an event has an owning type (dp_buf.h), so deleting the
 // context frees them; only the views and the pyramid (free_views) and the
 // stream, which must outlive them all, are released by hand.
@@ -140,6 +140,25 @@ struct dp_ctx {
     HostBuf<dp_mesh_vertex> t_hverts;
     HostBuf<int32_t> t_htris;
     Event t_e0, t_e1, t_e2, t_e3;
+    // dp_mesh_components / dp_mesh_clean: the union-find parents (the labels
+    // after the flatten), used flags, per-root triangle and vertex counts,
+    // component numbers (at roots), kept flags (by component number), the rank
+    // sort's keys, the new vertex numbers, per-block counts and their scans,
+    // striped counters, Tmax, the statistics read; the host forms' staged
+    // inputs, device results and pinned results; timing events (the host forms
+    // time their phases apart)
+    DevBuf<int32_t> c_parent, c_tcnt, c_vcnt, c_cnum, c_vmap, c_tmax;
+    DevBuf<uint8_t> c_used, c_keptc;
+    DevBuf<unsigned long long> c_keys, c_keys_sorted, c_bcount, c_boff, c_count;
+    HostBuf<unsigned long long> c_hcount;
+    DevBuf<unsigned char> c_in;
+    DevBuf<int32_t> c_maps, c_tris;
+    DevBuf<dp_mesh_vertex> c_verts;
+    DevBuf<dp_mesh_component> c_comps;
+    HostBuf<int32_t> c_htris;
+    HostBuf<dp_mesh_vertex> c_hverts;
+    HostBuf<dp_mesh_component> c_hcomps;
+    Event c_e[6];
     HostBuf<dp_patch> result; // dp_densify / dp_densify_result output (pinned)
     // dp_densify_iterate: per iteration {evaluations, filter survivors} on the
     // device (read once, at the end) and the filters' timing events

@@ -38,6 +38,7 @@ __all__ = [
     "check_fuse_args",
     "check_mapref_args",
     "check_tsdf_args",
+    "check_mesh_clean_args",
     "mesh_volume",
     "write_mesh_ply",
     "read_pfm",
@@ -847,6 +848,140 @@ class Engine:
                                             ctypes.c_void_p(stream) if stream else None))
         return int(nv.value), int(nt.value), {name: getattr(st, name) for name, _ in N.DpMeshStats._fields_}
 
+    # ---- mesh clean-up (include/densepoints.h dp_mesh_components / dp_mesh_clean) ----
+    def mesh_components(self, triangles, n_vertices: int) -> dict:
+        """dp_mesh_components: the connected components (by shared vertices) of
+        `triangles` (n x 3 int32) over n_vertices vertices.  Returns
+        {"vertex_component" int32 (-1: unused), "triangle_component" int32 (-1:
+        invalid), "components" as a MESH_COMPONENT_DTYPE array in ascending root
+        order, "stats"}."""
+        tris = _mesh_triangles("mesh_components", triangles)
+        nv = _mesh_count("mesh_components", n_vertices)
+        vc, tc = np.full(nv, -1, np.int32), np.full(len(tris), -1, np.int32)
+        pc, nc, st = ctypes.c_void_p(), ctypes.c_int64(), N.DpMeshCleanStats()
+        self._check(lib.dp_mesh_components(self._ctx, ptr(tris) if len(tris) else None, len(tris), nv,
+                                           ptr(vc) if nv else None, ptr(tc) if len(tris) else None, ctypes.byref(pc),
+                                           ctypes.byref(nc), ctypes.byref(st)))
+        comps = np.zeros(nc.value, dtype=N.MESH_COMPONENT_DTYPE)
+        if nc.value:
+            ctypes.memmove(comps.ctypes.data, pc.value, comps.nbytes)
+        return dict(vertex_component=vc, triangle_component=tc, components=comps, stats=_mesh_clean_stats(st))
+
+    def mesh_components_device(self, d_triangles, n_triangles: int, n_vertices: int, d_vertex_component=None,
+                               d_triangle_component=None, d_components=None, component_cap: int = 0,
+                               stream: int | None = None):
+        """dp_mesh_components_device: device triangles (an address) into the
+        device arrays given (addresses, None = not wanted) and at most
+        component_cap table rows at d_components.  Queued on `stream`; one wait.
+        Returns (the full component count, stats)."""
+        nt, nv = _mesh_count("mesh_components_device", n_triangles), _mesh_count("mesh_components_device", n_vertices)
+        _mesh_cap("mesh_components_device", component_cap, d_components)
+        if nt and not d_triangles:
+            raise ValueError("mesh_components_device: the triangles must be given")
+        nc, st = ctypes.c_int64(), N.DpMeshCleanStats()
+        self._check(lib.dp_mesh_components_device(self._ctx, _addr(d_triangles), nt, nv, _addr(d_vertex_component),
+                                                  _addr(d_triangle_component), _addr(d_components), int(component_cap),
+                                                  ctypes.byref(nc), ctypes.byref(st), _addr(stream)))
+        return int(nc.value), _mesh_clean_stats(st)
+
+    def mesh_clean(self, vertices, triangles, min_triangles: int = 1, min_fraction: float = 0.0,
+                   max_components: int = 0, maps: bool = False):
+        """dp_mesh_clean: the mesh without its small components -- those of fewer
+        than min_triangles triangles, of less than min_fraction of the largest
+        component's triangles, or (max_components > 0) not among the first
+        max_components by triangle count.  Returns (vertices, triangles, stats),
+        and with maps=True also (vertex_map, triangle_map): the new index of every
+        input vertex and triangle, or -1."""
+        mco = check_mesh_clean_args(min_triangles, min_fraction, max_components)
+        verts = np.ascontiguousarray(vertices, dtype=N.MESH_VERTEX_DTYPE).reshape(-1)
+        tris = _mesh_triangles("mesh_clean", triangles)
+        nv, nt = len(verts), len(tris)
+        vm = np.full(nv, -1, np.int32) if maps else None
+        tm = np.full(nt, -1, np.int32) if maps else None
+        pv, pt, no, to, st = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_int64(), ctypes.c_int64(), N.DpMeshCleanStats()
+        self._check(lib.dp_mesh_clean(self._ctx, ctypes.byref(mco), ptr(verts) if nv else None, nv,
+                                      ptr(tris) if nt else None, nt, ctypes.byref(pv), ctypes.byref(no),
+                                      ctypes.byref(pt), ctypes.byref(to), ptr(vm) if maps and nv else None,
+                                      ptr(tm) if maps and nt else None, ctypes.byref(st)))
+        vout = np.zeros(no.value, dtype=N.MESH_VERTEX_DTYPE)
+        tout = np.zeros((to.value, 3), dtype=np.int32)
+        if no.value:
+            ctypes.memmove(vout.ctypes.data, pv.value, vout.nbytes)
+        if to.value:
+            ctypes.memmove(tout.ctypes.data, pt.value, tout.nbytes)
+        out = (vout, tout, _mesh_clean_stats(st))
+        return out + (vm, tm) if maps else out
+
+    def mesh_clean_device(self, d_vertices, n_vertices: int, d_triangles, n_triangles: int, d_vertices_out,
+                          vertex_cap: int, d_triangles_out, triangle_cap: int, d_vertex_map=None, d_triangle_map=None,
+                          min_triangles: int = 1, min_fraction: float = 0.0, max_components: int = 0,
+                          stream: int | None = None):
+        """dp_mesh_clean_device: a device mesh (addresses; tsdf_mesh_device's
+        output) into at most vertex_cap records at d_vertices_out and
+        triangle_cap triples at d_triangles_out, and the maps (None = not wanted).
+        Queued on `stream`; one wait.  Returns (the full vertex count, the full
+        triangle count -- above a cap: an overflow --, stats)."""
+        mco = check_mesh_clean_args(min_triangles, min_fraction, max_components)
+        nv, nt = _mesh_count("mesh_clean_device", n_vertices), _mesh_count("mesh_clean_device", n_triangles)
+        _mesh_cap("mesh_clean_device", vertex_cap, d_vertices_out)
+        _mesh_cap("mesh_clean_device", triangle_cap, d_triangles_out)
+        if (nv and not d_vertices) or (nt and not d_triangles):
+            raise ValueError("mesh_clean_device: the vertices and triangles must be given")
+        no, to, st = ctypes.c_int64(), ctypes.c_int64(), N.DpMeshCleanStats()
+        self._check(lib.dp_mesh_clean_device(self._ctx, ctypes.byref(mco), _addr(d_vertices), nv, _addr(d_triangles), nt,
+                                             _addr(d_vertices_out), int(vertex_cap), ctypes.byref(no),
+                                             _addr(d_triangles_out), int(triangle_cap), ctypes.byref(to),
+                                             _addr(d_vertex_map), _addr(d_triangle_map), ctypes.byref(st),
+                                             _addr(stream)))
+        return int(no.value), int(to.value), _mesh_clean_stats(st)
+
+
+def _addr(a):
+    return ctypes.c_void_p(a) if a else None
+
+
+def _mesh_clean_stats(st) -> dict:
+    return {name: getattr(st, name) for name, _ in N.DpMeshCleanStats._fields_}
+
+
+def _mesh_count(who: str, n) -> int:
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 0 <= int(n) <= 2**31 - 1:
+        raise ValueError("%s: a count must be a whole number in 0..2^31 - 1" % who)
+    return int(n)
+
+
+def _mesh_cap(who: str, cap, buf) -> None:
+    if isinstance(cap, bool) or not isinstance(cap, (int, np.integer)) or cap < 0 or (cap > 0 and not buf):
+        raise ValueError("%s: a cap must be >= 0, with its buffer given when > 0" % who)
+
+
+def _mesh_triangles(who: str, triangles) -> np.ndarray:
+    tris = np.asarray(triangles)
+    if tris.size == 0:
+        return np.zeros((0, 3), np.int32)
+    if tris.ndim != 2 or tris.shape[1] != 3 or not np.issubdtype(tris.dtype, np.integer):
+        raise ValueError("%s: triangles must be an n x 3 integer array" % who)
+    if tris.dtype != np.int32 and ((tris < -2**31).any() or (tris > 2**31 - 1).any()):
+        raise ValueError("%s: a triangle index does not fit int32" % who)
+    return np.ascontiguousarray(tris, dtype=np.int32)
+
+
+def check_mesh_clean_args(min_triangles=1, min_fraction=0.0, max_components=0):
+    """Argument validation of Engine.mesh_clean[_device] (the limits of
+    dp_mesh_clean_options, raised as ValueError before any device call); returns
+    the dp_mesh_clean_options."""
+    def whole(x, hi):
+        return isinstance(x, (int, np.integer)) and not isinstance(x, bool) and 0 <= int(x) <= hi
+
+    if not whole(min_triangles, 2**63 - 1):
+        raise ValueError("mesh_clean: min_triangles must be a whole number >= 0")
+    if (isinstance(min_fraction, bool) or not isinstance(min_fraction, (int, float, np.integer, np.floating))
+            or not 0.0 <= float(np.float32(min_fraction)) <= 1.0):
+        raise ValueError("mesh_clean: min_fraction must be in 0..1")
+    if not whole(max_components, 2**31 - 1):
+        raise ValueError("mesh_clean: max_components must be a whole number in 0..2^31 - 1")
+    return N.DpMeshCleanOptions(int(min_triangles), float(min_fraction), int(max_components), 0, 0)
+
 
 def check_tsdf_args(V: int, views, origin, voxel, dim, trunc, min_weight: int = 1):
     """Argument validation of Engine.tsdf_integrate[_device] and tsdf_mesh[_device]
@@ -1230,7 +1365,7 @@ class PMVS:
         self.stats["render"], self.stats["fused"] = rst, fst
         return out
 
-    def mesh(self, refine: int = 0, voxel=None, dim: int = 256, trunc=None, min_weight: int = 2, **kw):
+    def mesh(self, refine: int = 0, voxel=None, dim: int = 256, trunc=None, min_weight: int = 2, clean=None, **kw):
         """The last run()'s result as a triangle mesh: (vertices as a
         MESH_VERTEX_DTYPE array, triangles as n x 3 int32).  The depth maps of
         depth_maps(refine, **kw) -- kw: its render and refinement options --
@@ -1238,10 +1373,15 @@ class PMVS:
         patches (mesh_volume: their bounding box padded by trunc; voxel defaults
         to its longest side / dim, trunc to 4 * voxel) and the volume's zero
         surface is extracted (Engine.tsdf_mesh) over the voxels that at least
-        min_weight views observed.  The volume and the statistics of the two
-        calls are left in self.stats["mesh"]."""
+        min_weight views observed.  clean: a dict of Engine.mesh_clean's options
+        (min_triangles, min_fraction, max_components) drops the mesh's small
+        components; None (the default) leaves the mesh as extracted.  The volume
+        and the statistics of the calls are left in self.stats["mesh"] (the
+        clean-up's under "clean")."""
         if not self._ran:
             raise ValueError("mesh: call run() first")
+        if clean is not None:
+            check_mesh_clean_args(**dict(clean))
         refine, mkw, kw = split_refine_args("mesh", refine, kw)
         vol = mesh_volume(self.patches["pos"], voxel, dim, trunc)
         check_tsdf_args(max(len(self.views), 1), kw.get("views"), min_weight=min_weight, **vol)
@@ -1253,7 +1393,11 @@ class PMVS:
                 maps["depth"], maps["normal"] = ref["depth"], ref["normal"]
             volume = eng.tsdf_integrate(maps["depth"], maps["views"], **vol)
             verts, tris, mst = eng.tsdf_mesh(volume, min_weight)
+            if clean is not None:
+                verts, tris, cst = eng.mesh_clean(verts, tris, **dict(clean))
         self.stats["mesh"] = dict(vol, min_weight=int(min_weight), integrate=volume["stats"], mesh=mst)
+        if clean is not None:
+            self.stats["mesh"]["clean"] = cst
         return verts, tris
 
 

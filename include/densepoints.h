@@ -849,6 +849,100 @@ int dp_tsdf_mesh_device(dp_ctx *ctx, const dp_tsdf_options *opts, const float *d
                         int32_t *d_triangles, int64_t triangle_cap, int64_t *n_triangles, dp_mesh_stats *stats,
                         void *stream);
 
+/* ---- mesh clean-up: the connected components of a triangle mesh, and the mesh
+ * without its small components --------------------------------------------------
+ * No reference counterpart.  A mesh of real depth maps is the surface plus a
+ * cloud of small closed "floaters" wherever a few wrong depth pixels agreed in
+ * min_weight views; this labels the components and drops the small ones.  Every
+ * quantity is an integer or a byte copy; the only floating-point operation is
+ * the one comparison with min_fraction.  Neither call reads a view, so a
+ * context without dp_set_views works.
+ *
+ * Inputs: n_triangles triangles of three int32 vertex indices each, over
+ * n_vertices vertices (dp_mesh_clean also reads the 16-byte vertex records).
+ * A triangle is VALID iff its three indices lie in [0, n_vertices).  An invalid
+ * triangle joins nothing, has component -1, is never written, and counts in
+ * invalid_triangles; its indices are never used as an address.  A triangle with
+ * repeated indices is valid.
+ * A vertex is USED iff a valid triangle names it.  Every valid triangle (a, b, c)
+ * joins a, b and c; label(v) is the smallest vertex index in v's connected set.
+ * So two triangles that share only one vertex are in one component (vertex
+ * connectivity: it needs no edge table, and it never splits what marching
+ * tetrahedra emitted as one surface).
+ * Components: a component's root is its label; components are numbered 0..C-1
+ * by ascending root.  vertex_component[v] = that number, or -1 for an unused
+ * vertex; triangle_component[t] = the number of its first index's component, or
+ * -1 for an invalid triangle.  Table row c (dp_mesh_component) holds root,
+ * vertices (the used vertices of c), triangles T_c and rank; rank(c) = the number
+ * of components c' with T_c' > T_c, or with T_c' = T_c and c' < c.
+ * Selection (dp_mesh_clean_options): Tmax = max T_c (largest_triangles; 0 when
+ * C = 0).  c is KEPT iff T_c >= min_triangles, and (double)T_c >=
+ * (double)min_fraction * (double)Tmax, and max_components = 0 or rank(c) <
+ * max_components.
+ * Clean output: the kept vertices are the used vertices of kept components, in
+ * ascending input order, each 16-byte record copied byte for byte (the pad byte
+ * included); the kept triangles are the valid triangles of kept components, in
+ * input order, their indices remapped to the new numbering.  vertex_map[v] and
+ * triangle_map[t] hold the new index, or -1.  Hence the result of a clean,
+ * cleaned again with the same options, is itself.
+ * The labels are minima and the counts are integers, so nothing depends on the
+ * order in which lanes or blocks run.
+ * Statistics: vertices_in, triangles_in (the counts given), invalid_triangles,
+ * unused_vertices, components = C, largest_triangles = Tmax, components_kept,
+ * vertices_out, triangles_out; clean_ms = device time of the call's kernels.
+ * dp_mesh_components selects nothing: it reports components_kept = C,
+ * vertices_out = the used vertices and triangles_out = the valid triangles.
+ *
+ * Host form: host arrays; vertex_component / triangle_component and vertex_map /
+ * triangle_map are the caller's (n_vertices / n_triangles int32, may be NULL);
+ * *components, *vertices_out and *triangles_out are context-owned, valid until
+ * the next call of the same function or destroy, and NULL when their count is 0.
+ * Device form: device arrays (the output of dp_tsdf_mesh_device is the intended
+ * input); one cap per output buffer: the first min(cap, count) records are
+ * written and nothing beyond them (a buffer may be NULL with cap 0); the counts
+ * returned are the full counts, so a caller sees an overflow; everything is
+ * queued on `stream` (NULL = the context's) and the call waits once, for the
+ * counts and statistics.  mco NULL = the defaults; stats may be NULL.
+ * Errors (DP_E_ARG): a negative count or a count above 2^31 - 1; a NULL input
+ * with a non-zero count; min_triangles < 0; min_fraction outside 0..1 or NaN;
+ * max_components < 0; flags != 0; a NULL count (or, host form, result) pointer;
+ * a negative cap, or a cap > 0 without its buffer; an output pointer equal to an
+ * input pointer.  n_triangles = 0 or n_vertices = 0 is legal and yields empty
+ * results. */
+typedef struct dp_mesh_clean_options {
+    int64_t min_triangles;   /* 1    least triangles of a kept component (>= 0)             */
+    float   min_fraction;    /* 0    least share of the largest component's triangles (0..1) */
+    int32_t max_components;  /* 0    0 = no limit, else keep only the first so many by rank  */
+    int32_t flags;           /* none defined; non-zero is DP_E_ARG                           */
+    int32_t reserved;
+} dp_mesh_clean_options;
+typedef struct dp_mesh_component {
+    int32_t root, vertices, triangles, rank;
+} dp_mesh_component;
+typedef struct dp_mesh_clean_stats {
+    int64_t vertices_in, triangles_in, invalid_triangles, unused_vertices, components, largest_triangles,
+        components_kept, vertices_out, triangles_out;
+    double clean_ms;
+} dp_mesh_clean_stats;
+
+void dp_default_mesh_clean_options(dp_mesh_clean_options *mco);
+int dp_mesh_components(dp_ctx *ctx, const int32_t *triangles, int64_t n_triangles, int64_t n_vertices,
+                       int32_t *vertex_component, int32_t *triangle_component, const dp_mesh_component **components,
+                       int64_t *n_components, dp_mesh_clean_stats *stats);
+int dp_mesh_components_device(dp_ctx *ctx, const int32_t *d_triangles, int64_t n_triangles, int64_t n_vertices,
+                              int32_t *d_vertex_component, int32_t *d_triangle_component,
+                              dp_mesh_component *d_components, int64_t component_cap, int64_t *n_components,
+                              dp_mesh_clean_stats *stats, void *stream);
+int dp_mesh_clean(dp_ctx *ctx, const dp_mesh_clean_options *mco, const dp_mesh_vertex *vertices, int64_t n_vertices,
+                  const int32_t *triangles, int64_t n_triangles, const dp_mesh_vertex **vertices_out,
+                  int64_t *n_vertices_out, const int32_t **triangles_out, int64_t *n_triangles_out,
+                  int32_t *vertex_map, int32_t *triangle_map, dp_mesh_clean_stats *stats);
+int dp_mesh_clean_device(dp_ctx *ctx, const dp_mesh_clean_options *mco, const dp_mesh_vertex *d_vertices,
+                         int64_t n_vertices, const int32_t *d_triangles, int64_t n_triangles,
+                         dp_mesh_vertex *d_vertices_out, int64_t vertex_cap, int64_t *n_vertices_out,
+                         int32_t *d_triangles_out, int64_t triangle_cap, int64_t *n_triangles_out,
+                         int32_t *d_vertex_map, int32_t *d_triangle_map, dp_mesh_clean_stats *stats, void *stream);
+
 /* ---- seed generation: Features::Matcher::GenerateSeeds ---
  * modules/features/matcher.cpp:18-43 with the default MatcherOptions
  * (matcher.h:21-32: ORB detector, kNN matcher, no direct epipolar matching,

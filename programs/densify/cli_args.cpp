@@ -41,14 +41,20 @@ void usage()
                  "                             score_%%04d.pfm -- and before --fuse fuses them; W = odd\n"
                  "                             window side 3..11, default 7; T = least score, default 0.5)\n"
                  "               [--mesh FILE.ply [--mesh-dim N] [--mesh-voxel S] [--mesh-trunc T]\n"
-                 "                [--mesh-min-weight M]]  (after those: the depth maps of every view,\n"
+                 "                [--mesh-min-weight M] [--mesh-min-component N]\n"
+                 "                [--mesh-min-component-frac F] [--mesh-keep-largest K]]\n"
+                 "                            (after those: the depth maps of every view,\n"
                  "                             rendered -- and refined, with --refine-maps -- on the device,\n"
                  "                             integrated into one TSDF volume around the written patches\n"
                  "                             and meshed by marching tetrahedra -- dp_tsdf_integrate,\n"
                  "                             dp_tsdf_mesh; N = voxels along the patches' longest side,\n"
                  "                             2..1024, default 256; S = voxel side, default that side / N;\n"
                  "                             T = truncation, default 4 S; M = least views per voxel,\n"
-                 "                             1..64, default 2)\n"
+                 "                             1..64, default 2; with N, F or K the mesh's connected\n"
+                 "                             components are labelled on the device and the small ones\n"
+                 "                             dropped before the PLY is written -- dp_mesh_clean: those of\n"
+                 "                             fewer than N triangles, of less than the share F, 0..1, of the\n"
+                 "                             largest component's triangles, or not among the K largest)\n"
                  "       densify --synthetic V,W,H,KIND --write-scene DIR\n");
 }
 
@@ -195,6 +201,21 @@ Parse parse_args(int argc, char **argv, Args &a, std::string &error)
                 a.mesh_min_weight = (int)k;
             else
                 error = "--mesh-min-weight expects 1..64";
+        } else if (o == "--mesh-min-component") {
+            if (int_in_range(v, 0, 2147483647L, k))
+                a.mesh_min_component = k;
+            else
+                error = "--mesh-min-component expects 0..2147483647";
+        } else if (o == "--mesh-min-component-frac") {
+            if (number_in_range(v, 0.0, 1.0, t))
+                a.mesh_min_component_frac = t;
+            else
+                error = "--mesh-min-component-frac expects a number in 0..1";
+        } else if (o == "--mesh-keep-largest") {
+            if (int_in_range(v, 1, 2147483647L, k))
+                a.mesh_keep_largest = k;
+            else
+                error = "--mesh-keep-largest expects 1..2147483647";
         } else if (o == "--exchange") {
             a.exchange_mode = v;
             if (one_of(v, {"auto", "rccl", "copy"}) < 0)

@@ -33,6 +33,15 @@ struct Args {
     double mesh_voxel = 0.0;      // 0: that side / mesh_dim
     double mesh_trunc = 0.0;      // 0: 4 voxels
     int mesh_min_weight = 2;
+    // --mesh-min-component N, --mesh-min-component-frac F, --mesh-keep-largest K:
+    // dp_mesh_clean on the mesh before it is written; none given: no clean-up
+    long long mesh_min_component = -1; // < 0: not given (the library's default)
+    double mesh_min_component_frac = -1.0;
+    long long mesh_keep_largest = -1;
+    bool mesh_clean() const
+    {
+        return mesh_min_component >= 0 || mesh_min_component_frac >= 0.0 || mesh_keep_largest >= 0;
+    }
 
     Args();
 };

@@ -522,7 +522,8 @@ std::string write_fused(dp_ctx *ctx, const Args &args, int32_t V, const std::vec
 
 // --mesh: the device maps integrated into one TSDF volume around the written
 // patches (dp_tsdf_integrate_device) and meshed there (dp_tsdf_mesh_device,
-// once for the counts and once into buffers of that size); only the mesh comes
+// once for the counts and once into buffers of that size) and, with one of the
+// clean-up options, cleaned there (dp_mesh_clean_device); only the mesh comes
 // back.  The volume is the patches' bounding box padded by the truncation;
 // the voxel defaults to the box's longest side / --mesh-dim, the truncation to
 // four voxels.  Returns the report's "mesh" member.
@@ -578,6 +579,42 @@ std::string write_mesh(dp_ctx *ctx, const Args &args, int32_t V, const std::vect
           "dp_tsdf_mesh_device");
     if (nv != vcap || nt != tcap)
         throw std::runtime_error("--mesh: the counts changed between two runs");
+    // --mesh-min-component / -frac / --mesh-keep-largest: the small components
+    // dropped where the mesh lies (dp_mesh_clean_device; a clean mesh is no
+    // larger than its input, so the input's counts size the buffers)
+    std::string cleaned;
+    if (args.mesh_clean()) {
+        dp_mesh_clean_options mco;
+        dp_default_mesh_clean_options(&mco);
+        if (args.mesh_min_component >= 0)
+            mco.min_triangles = args.mesh_min_component;
+        if (args.mesh_min_component_frac >= 0.0)
+            mco.min_fraction = (float)args.mesh_min_component_frac;
+        if (args.mesh_keep_largest >= 0)
+            mco.max_components = (int32_t)args.mesh_keep_largest;
+        dp_mesh_vertex *d_cverts = (dp_mesh_vertex *)m.bytes((size_t)vcap * sizeof(dp_mesh_vertex), "--mesh");
+        int32_t *d_ctris = (int32_t *)m.bytes((size_t)tcap * 3 * sizeof(int32_t), "--mesh");
+        dp_mesh_clean_stats cs;
+        check(ctx,
+              dp_mesh_clean_device(ctx, &mco, vcap ? d_verts : nullptr, vcap, tcap ? d_tris : nullptr, tcap,
+                                   vcap ? d_cverts : nullptr, vcap, &nv, tcap ? d_ctris : nullptr, tcap, &nt, nullptr,
+                                   nullptr, &cs, nullptr),
+              "dp_mesh_clean_device");
+        if (nv > vcap || nt > tcap)
+            throw std::runtime_error("--mesh: the clean-up returned more than it was given");
+        d_verts = d_cverts;
+        d_tris = d_ctris;
+        char cbuf[480];
+        std::snprintf(cbuf, sizeof cbuf,
+                      ", \"clean\": {\"vertices_in\": %lld, \"triangles_in\": %lld, \"invalid_triangles\": %lld, "
+                      "\"unused_vertices\": %lld, \"components\": %lld, \"largest_triangles\": %lld, "
+                      "\"components_kept\": %lld, \"vertices_out\": %lld, \"triangles_out\": %lld, \"clean_ms\": %.3f}",
+                      (long long)cs.vertices_in, (long long)cs.triangles_in, (long long)cs.invalid_triangles,
+                      (long long)cs.unused_vertices, (long long)cs.components, (long long)cs.largest_triangles,
+                      (long long)cs.components_kept, (long long)cs.vertices_out, (long long)cs.triangles_out,
+                      cs.clean_ms);
+        cleaned = cbuf;
+    }
     std::vector<dp_mesh_vertex> verts((size_t)nv);
     std::vector<int32_t> tris((size_t)nt * 3);
     if ((nv > 0 && hipMemcpy(verts.data(), d_verts, verts.size() * sizeof(dp_mesh_vertex), hipMemcpyDeviceToHost) !=
@@ -595,11 +632,11 @@ std::string write_mesh(dp_ctx *ctx, const Args &args, int32_t V, const std::vect
     std::snprintf(buf, sizeof buf,
                   ", \"mesh\": {\"vertices\": %lld, \"triangles\": %lld, \"ms\": %.3f, \"dim\": [%d, %d, %d], "
                   "\"voxel\": %.9g, \"trunc\": %.9g, \"observed_voxels\": %lld, \"active_cells\": %lld, "
-                  "\"integrate_ms\": %.3f, \"mesh_ms\": %.3f}",
+                  "\"integrate_ms\": %.3f, \"mesh_ms\": %.3f",
                   (long long)nv, (long long)nt, ts.integrate_ms + ms.mesh_ms, to.dim[0], to.dim[1], to.dim[2],
                   (double)to.voxel, (double)to.trunc, (long long)ts.observed_voxels, (long long)ms.active_cells,
                   ts.integrate_ms, ms.mesh_ms);
-    return m.refined + buf;
+    return m.refined + buf + cleaned + "}";
 }
 
 using Clock = std::chrono::steady_clock;
