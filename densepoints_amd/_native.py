@@ -465,6 +465,8 @@ SIGNATURES = [
     ("dp_probe_keep_gather", _I, [_P, _P, ctypes.c_int64, _P, _P, _P]),
     ("dp_probe_akaze_plane", _I, [_P, _I, _I, _I, _P, ctypes.c_int64, _P]),
     ("dp_probe_orb_level", _I, [_P, _I, _I, _I, _D, _P, ctypes.c_int64, _P]),
+    ("dp_probe_seed_stages", _I, [_P, _I, _P, _P, _P, _I, _P, _P, _P, _P]),
+    ("dp_probe_seed_t2q", _I, [_P, _I, _P, _P]),
 ]
 
 

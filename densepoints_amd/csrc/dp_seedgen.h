@@ -63,7 +63,7 @@ struct dp_seedgen {
     std::vector<dp_keypoint> h_kp; // host copies of kp_b / kv_b (a detector's result)
     std::vector<int32_t> h_kv;
     std::vector<uint8_t> h_desc;
-    std::vector<int32_t> h_q2t;
+    std::vector<int32_t> h_q2t, h_t2q; // per (pair, query) / (pair, train): the other side's index or -1
     std::vector<double> h_xyz;
     bool have_stages = false;
 };

@@ -448,7 +448,7 @@ int triangulate(dp_ctx *c, dp_seedgen *s, const PairPlan &plan, int64_t n)
 }
 
 // the n6 points (s->obs), the n descriptors and the match tables to the host
-// (s->h_xyz, h_desc, h_q2t).  One host wait.
+// (s->h_xyz, h_desc, h_q2t, h_t2q with -1 for an empty slot).  One host wait.
 int read_back(dp_ctx *c, dp_seedgen *s, const PairPlan &plan, int64_t n, int64_t n6)
 {
     hipStream_t st = c->stream;
@@ -456,10 +456,66 @@ int read_back(dp_ctx *c, dp_seedgen *s, const PairPlan &plan, int64_t n, int64_t
     const size_t dbytes = (size_t)4 * s->desc_words;
     s->h_desc.resize(dbytes * n);
     s->h_q2t.resize(plan.q_total);
+    s->h_t2q.resize(plan.t2q_total);
     DP_HIP(c, hipMemcpyAsync(s->h_xyz.data(), s->obs.p, (size_t)n6 * 24, hipMemcpyDeviceToHost, st));
     DP_HIP(c, hipMemcpyAsync(s->h_desc.data(), s->desc.p, (size_t)n * dbytes, hipMemcpyDeviceToHost, st));
     DP_HIP(c, hipMemcpyAsync(s->h_q2t.data(), s->q2t.p, (size_t)plan.q_total * 4, hipMemcpyDeviceToHost, st));
+    DP_HIP(c, hipMemcpyAsync(s->h_t2q.data(), s->t2q.p, (size_t)plan.t2q_total * 4, hipMemcpyDeviceToHost, st));
     DP_HIP(c, hipStreamSynchronize(st));
+    for (int32_t &q : s->h_t2q)
+        if (q == dpk::kNoMatch)
+            q = -1;
+    return DP_OK;
+}
+
+// what the stages after a detector leave behind besides the host tables
+struct StageResult {
+    int np = 0;
+    int64_t ratio_matches = 0, matches = 0, points = 0;
+    Event t3, t4; // matching ends at t3, triangulation at t4
+};
+
+// Everything after a detector: n keypoints as Detected (dp_seedgen.h) states
+// them -> the points in s->h_xyz and the tables of read_back.  The one
+// sequence dp_generate_seeds and dp_probe_seed_stages both run.
+int stages_after_detect(dp_ctx *c, dp_seedgen *s, const dp_matcher_options &mo, int64_t n, StageResult &r)
+{
+    hipStream_t st = c->stream;
+    int rc = view_offsets(c, s, n);
+    if (rc != DP_OK)
+        return rc;
+
+    // ---- DefaultPairsList + MatchKeypoints + FilterMatches
+    PairPlan plan;
+    rc = plan_pairs(c, s, plan);
+    if (rc == DP_OK)
+        rc = match_pairs(c, s, mo, plan);
+    if (rc != DP_OK)
+        return rc;
+    DP_HIP(c, hipEventRecord(r.t3, st));
+
+    // ---- TriangulateMatches, the valid points compacted into s->obs
+    rc = triangulate(c, s, plan, n);
+    if (rc != DP_OK)
+        return rc;
+    struct P3 { // local to this function: its name is part of the select kernel's
+        double x, y, z;
+    };
+    unsigned long long cnt[2] = {0, 0};
+    const int64_t n6 = select_flagged(
+        c, s, reinterpret_cast<P3 *>(s->X.p), s->valid.p, reinterpret_cast<P3 *>(s->obs.p), n, [&]() {
+            hipError_t e = hipEventRecord(r.t4, st);
+            return e != hipSuccess ? e : hipMemcpyAsync(cnt, s->counters.p, sizeof(cnt), hipMemcpyDeviceToHost, st);
+        });
+    if (n6 < 0)
+        return (int)n6;
+    rc = read_back(c, s, plan, n, n6);
+    if (rc != DP_OK)
+        return rc;
+    r.np = plan.np;
+    r.ratio_matches = (int64_t)cnt[0];
+    r.matches = (int64_t)cnt[1];
+    r.points = n6;
     return DP_OK;
 }
 
@@ -540,7 +596,6 @@ static int generate_seeds(dp_ctx *c, const dp_matcher_options *mo_in, const doub
         return fail(c, DP_E_OOM, "seedgen state");
     s->have_stages = false;
     DP_HIP(c, hipSetDevice(c->device));
-    hipStream_t st = c->stream;
     const auto t_wall0 = std::chrono::steady_clock::now();
     const int V = c->V;
     std::vector<int32_t> vw(V), vh(V);
@@ -554,56 +609,117 @@ static int generate_seeds(dp_ctx *c, const dp_matcher_options *mo_in, const doub
     rc = (mo.detector_type == DP_DETECTOR_AKAZE ? akaze_detect : orb_detect)(c, s, mo, vw, vh, det, probe);
     if (rc != DP_OK || probe)
         return rc;
-    rc = view_offsets(c, s, det.n);
-    if (rc != DP_OK)
-        return rc;
-
-    // ---- DefaultPairsList + MatchKeypoints + FilterMatches
-    PairPlan plan;
-    rc = plan_pairs(c, s, plan);
-    if (rc == DP_OK)
-        rc = match_pairs(c, s, mo, plan);
-    if (rc != DP_OK)
-        return rc;
-    Event t3, t4;
-    DP_HIP(c, hipEventRecord(t3, st));
-
-    // ---- TriangulateMatches, the valid points compacted into s->obs
-    rc = triangulate(c, s, plan, det.n);
-    if (rc != DP_OK)
-        return rc;
-    struct P3 { // local to this function: its name is part of the select kernel's
-        double x, y, z;
-    };
-    unsigned long long cnt[2] = {0, 0};
-    const int64_t n6 = select_flagged(
-        c, s, reinterpret_cast<P3 *>(s->X.p), s->valid.p, reinterpret_cast<P3 *>(s->obs.p), det.n, [&]() {
-            hipError_t e = hipEventRecord(t4, st);
-            return e != hipSuccess ? e : hipMemcpyAsync(cnt, s->counters.p, sizeof(cnt), hipMemcpyDeviceToHost, st);
-        });
-    if (n6 < 0)
-        return (int)n6;
-    rc = read_back(c, s, plan, det.n, n6);
+    StageResult sr;
+    rc = stages_after_detect(c, s, mo, det.n, sr);
     if (rc != DP_OK)
         return rc;
 
     dp_seed_stats S{};
     S.keypoints_detected = det.keypoints_detected;
     S.keypoints = det.n;
-    S.pairs = plan.np;
-    S.ratio_matches = (int64_t)cnt[0];
-    S.matches = (int64_t)cnt[1];
-    S.points = n6;
+    S.pairs = sr.np;
+    S.ratio_matches = sr.ratio_matches;
+    S.matches = sr.matches;
+    S.points = sr.points;
     S.detect_ms = ev_ms(det.e0, det.e1);
     S.describe_ms = ev_ms(det.e1, det.e2);
-    S.match_ms = ev_ms(det.e2, t3);
-    S.triangulate_ms = ev_ms(t3, t4);
+    S.match_ms = ev_ms(det.e2, sr.t3);
+    S.triangulate_ms = ev_ms(sr.t3, sr.t4);
     S.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_wall0).count();
     s->have_stages = true;
     if (stats)
         *stats = S;
     *xyz_out = s->h_xyz.data();
-    *n_out = n6;
+    *n_out = sr.points;
+    return DP_OK;
+}
+
+// The caller's keypoints and descriptors stand in for a detector's result
+// (Detected, dp_seedgen.h); the stages after it are dp_generate_seeds' own.
+extern "C" int dp_probe_seed_stages(dp_ctx *c, int n_views, const int32_t *counts, const dp_keypoint *kp,
+                                    const uint8_t *desc, int descriptor_bytes, const dp_matcher_options *mo_in,
+                                    const double **xyz_out, int64_t *n_out, dp_seed_stats *stats)
+{
+    if (!c)
+        return DP_E_ARG;
+    if (!xyz_out || !n_out)
+        return fail(c, DP_E_ARG, "dp_probe_seed_stages: null output");
+    *xyz_out = nullptr;
+    *n_out = 0;
+    if (c->V < 1)
+        return fail(c, DP_E_STATE, "dp_probe_seed_stages: no views set");
+    if (n_views != c->V)
+        return fail(c, DP_E_ARG, "dp_probe_seed_stages: one keypoint count per view of the context is needed");
+    if (descriptor_bytes != 32 && descriptor_bytes != 64)
+        return fail(c, DP_E_ARG, "dp_probe_seed_stages: descriptors are 32 or 64 bytes wide");
+    if (!counts)
+        return fail(c, DP_E_ARG, "dp_probe_seed_stages: null counts");
+    const int words = descriptor_bytes / 4;
+    int64_t n = 0;
+    for (int v = 0; v < n_views; ++v) {
+        if (counts[v] < 0)
+            return fail(c, DP_E_ARG, "dp_probe_seed_stages: negative keypoint count");
+        if (counts[v] >= (1 << dpk::knn_row_bits(words)))
+            return fail(c, DP_E_ARG, "dp_probe_seed_stages: 2^22 (32-byte) / 2^21 (64-byte) or more keypoints in one view");
+        n += counts[v];
+    }
+    if (n > 0 && (!kp || !desc))
+        return fail(c, DP_E_ARG, "dp_probe_seed_stages: null keypoints or descriptors");
+    dp_matcher_options mo;
+    if (mo_in)
+        mo = *mo_in;
+    else
+        dp_default_matcher_options(&mo);
+    int rc = check_matcher_options(c, mo);
+    if (rc != DP_OK)
+        return rc;
+    dp_seedgen *s = seedgen(c);
+    if (!s)
+        return fail(c, DP_E_OOM, "seedgen state");
+    s->have_stages = false;
+    DP_HIP(c, hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    const auto t_wall0 = std::chrono::steady_clock::now();
+    DP_HIP(c, s->n_sel.reserve(1));
+
+    s->desc_words = words;
+    s->h_kp.assign(kp, kp + n);
+    s->h_kv.resize(n);
+    for (int64_t v = 0, i = 0; v < n_views; ++v)
+        for (int32_t k = 0; k < counts[v]; ++k)
+            s->h_kv[i++] = (int32_t)v;
+    DP_HIP(c, s->kp_b.reserve(n + 1));
+    DP_HIP(c, s->kv_b.reserve(n + 1));
+    DP_HIP(c, s->desc.reserve((size_t)(n + 1) * words));
+    if (n > 0) {
+        DP_HIP(c, hipMemcpyAsync(s->kp_b.p, s->h_kp.data(), (size_t)n * sizeof(dp_keypoint), hipMemcpyHostToDevice, st));
+        DP_HIP(c, hipMemcpyAsync(s->kv_b.p, s->h_kv.data(), (size_t)n * 4, hipMemcpyHostToDevice, st));
+        DP_HIP(c, hipMemcpyAsync(s->desc.p, desc, (size_t)n * descriptor_bytes, hipMemcpyHostToDevice, st));
+    }
+    Event t2;
+    DP_HIP(c, hipEventRecord(t2, st));
+    DP_HIP(c, hipStreamSynchronize(st)); // a detector leaves the stream idle; desc is the caller's
+
+    StageResult sr;
+    rc = stages_after_detect(c, s, mo, n, sr);
+    if (rc != DP_OK)
+        return rc;
+
+    dp_seed_stats S{};
+    S.keypoints_detected = n;
+    S.keypoints = n;
+    S.pairs = sr.np;
+    S.ratio_matches = sr.ratio_matches;
+    S.matches = sr.matches;
+    S.points = sr.points;
+    S.match_ms = ev_ms(t2, sr.t3);
+    S.triangulate_ms = ev_ms(sr.t3, sr.t4);
+    S.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_wall0).count();
+    s->have_stages = true;
+    if (stats)
+        *stats = S;
+    *xyz_out = s->h_xyz.data();
+    *n_out = sr.points;
     return DP_OK;
 }
 
@@ -652,5 +768,19 @@ extern "C" int dp_seed_matches(dp_ctx *c, int pair, int32_t *first, int32_t *sec
         *q2t = s->h_q2t.data() + s->h_jobs[pair].out_off;
     if (nq)
         *nq = s->h_jobs[pair].nq;
+    return DP_OK;
+}
+
+extern "C" int dp_probe_seed_t2q(dp_ctx *c, int pair, const int32_t **t2q, int64_t *nt)
+{
+    if (!c)
+        return DP_E_ARG;
+    dp_seedgen *s = c->seeds.get();
+    if (!s || !s->have_stages)
+        return fail(c, DP_E_STATE, "dp_probe_seed_t2q: no dp_generate_seeds result");
+    if (pair < 0 || pair >= (int)s->h_pairs.size() || !t2q || !nt)
+        return fail(c, DP_E_ARG, "dp_probe_seed_t2q: bad pair or null output");
+    *t2q = s->h_t2q.data() + s->h_pairs[pair].t2q_off;
+    *nt = s->h_jobs[pair].nt;
     return DP_OK;
 }

@@ -105,6 +105,40 @@ class Matcher:
             ctypes.memmove(m.ctypes.data, q.value, n.value * 4)
         return a.value, b.value, m
 
+    def t2q(self, pair: int) -> np.ndarray:
+        """train -> first (lowest) query index or -1 of one pair."""
+        t = ctypes.c_void_p()
+        n = ctypes.c_int64()
+        check(lib.dp_probe_seed_t2q(self.engine.handle, pair, ctypes.byref(t), ctypes.byref(n)), self.engine.handle)
+        m = np.zeros(n.value, dtype=np.int32)
+        if n.value:
+            ctypes.memmove(m.ctypes.data, t.value, n.value * 4)
+        return m
+
+    def probe_stages(self, counts, keypoints: np.ndarray, descriptors: np.ndarray) -> np.ndarray:
+        """dp_probe_seed_stages: the stages after the detector on planted
+        keypoints (KEYPOINT_DTYPE, view-major, counts[v] per view of the
+        engine) and their descriptors (n x 32 or n x 64 bytes).  Points, stats,
+        keypoints(), matches() and t2q() as after generate_seeds()."""
+        cnt = np.ascontiguousarray(counts, dtype=np.int32)
+        kp = np.ascontiguousarray(keypoints, dtype=KEYPOINT_DTYPE)
+        d = np.ascontiguousarray(descriptors, dtype=np.uint8)
+        if d.ndim != 2 or len(d) != len(kp) or int(cnt.sum()) != len(kp):
+            raise ValueError("probe_stages: one descriptor row per keypoint, counts summing to their number")
+        mo = self.options.to_c()
+        out = ctypes.c_void_p()
+        n = ctypes.c_int64()
+        st = N.DpSeedStats()
+        check(lib.dp_probe_seed_stages(self.engine.handle, len(cnt), ptr(cnt), ptr(kp), ptr(d), d.shape[1],
+                                       ctypes.byref(mo), ctypes.byref(out), ctypes.byref(n), ctypes.byref(st)),
+              self.engine.handle)
+        pts = np.zeros((n.value, 3), dtype=np.float64)
+        if n.value:
+            ctypes.memmove(pts.ctypes.data, out.value, n.value * 24)
+        self.points = pts
+        self.stats = {name: getattr(st, name) for name, _ in N.DpSeedStats._fields_}
+        return pts
+
 
 def knn_match(engine, query: np.ndarray, train: np.ndarray, width: int = 32):
     """BFMatcher(NORM_HAMMING).knnMatch(query, train, 2) on `width`-byte rows

@@ -48,6 +48,27 @@ int dp_probe_akaze_plane(dp_ctx *c, int view, int level, int which, float *out, 
  * level 0, then the INTER_LINEAR resizes level to level */
 int dp_probe_orb_level(dp_ctx *c, int view, int level, int n_levels, double scale_factor, uint8_t *out,
                        int64_t cap, int32_t wh[2]);
+/* The stages of seed generation after the detector, on keypoints the caller
+ * plants: per-view offsets, pair plan, matching (kNN / FLANN / direct
+ * epipolar), the match tables, triangulation and the read-back.  It uploads
+ * counts[v] keypoints per view (n_views = the context's views; kp and desc
+ * view-major, descriptor_bytes = 32 or 64 per row) as a detector's result and
+ * then runs the same code as dp_generate_seeds.  Only the projection matrices
+ * of the views are used: the pixels are never read and the coordinates need
+ * not lie inside them.  mo = NULL takes the defaults; its detector fields are
+ * ignored.  Points and stats as dp_generate_seeds (keypoints_detected =
+ * keypoints = the planted count, detect_ms = describe_ms = 0);
+ * dp_seed_keypoints, dp_seed_matches and dp_probe_seed_t2q read the rest.
+ * DP_E_ARG: a null pointer, a width other than 32 or 64, a negative count, a
+ * view with 2^22 (32-byte) / 2^21 (64-byte) or more rows, n_views != views. */
+int dp_probe_seed_stages(dp_ctx *c, int n_views, const int32_t *counts, const dp_keypoint *kp, const uint8_t *desc,
+                         int descriptor_bytes, const dp_matcher_options *mo, const double **xyz_out, int64_t *n_out,
+                         dp_seed_stats *stats);
+/* The train -> query table of one pair after dp_generate_seeds or
+ * dp_probe_seed_stages: per keypoint of the pair's second view the first
+ * (lowest) query matched to it, or -1; *nt = its length.  Valid until the
+ * next call on the context. */
+int dp_probe_seed_t2q(dp_ctx *c, int pair, const int32_t **t2q, int64_t *nt);
 /* diagnostic builds (-DDP_STAMPS) only: per-phase s_memtime cycle sums of the
  * refine kernel since the last call (0 maps, 1 texture 0, 2 other views,
  * 3 NCC finish, 6 patches, 7 whole patch); DP_E_STATE otherwise */

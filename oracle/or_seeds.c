@@ -688,19 +688,36 @@ typedef struct or_seeds {
     int32_t *pair_first, *pair_second;
     int64_t *q_off;       /* npairs + 1 */
     int32_t *q2t;
+    int64_t *t_off;       /* npairs + 1 */
+    int32_t *t2q;         /* per (pair, train): first query in list order or -1 */
     int64_t ratio_matches, matches;
     int64_t n_points;
     double *xyz;
+    int64_t *trk_off;     /* n_points + 1: the observations of each point ... */
+    int32_t *trk;         /* ... as (view, keypoint) in DLT row order, itself first */
+    int64_t trk_cap;
 } or_seeds;
 
+static void track_push(or_seeds *r, int64_t at, int view, int kp)
+{
+    if (at >= r->trk_cap) {
+        r->trk_cap = r->trk_cap ? 2 * r->trk_cap : 1024;
+        r->trk = (int32_t *)realloc(r->trk, sizeof(int32_t) * 2 * (size_t)r->trk_cap);
+    }
+    r->trk[2 * at] = view;
+    r->trk[2 * at + 1] = kp;
+}
+
 static int nearest_int_f(float v) { return (int)lrintf(v); }
+
+or_seeds *or_seeds_from_keypoints(int V, const double *P, const int64_t *kp_off, const or_keypoint *kp,
+                                  const uint8_t *desc, int dbytes, const or_matcher_options *mo);
 
 or_seeds *or_seeds_run(int V, const double *P, const int32_t *W, const int32_t *H, const uint8_t *const *bgr,
                        const or_matcher_options *mo)
 {
-    or_seeds *r = (or_seeds *)calloc(1, sizeof(or_seeds));
-    r->V = V;
-    r->kp_off = (int64_t *)calloc((size_t)V + 1, sizeof(int64_t));
+    int64_t *kp_off = (int64_t *)calloc((size_t)V + 1, sizeof(int64_t));
+    int64_t n_detected = 0;
     or_keypoint **kv = (or_keypoint **)calloc((size_t)V, sizeof(void *));
     uint8_t **dv = (uint8_t **)calloc((size_t)V, sizeof(void *));
     int *nv = (int *)calloc((size_t)V, sizeof(int));
@@ -708,7 +725,6 @@ or_seeds *or_seeds_run(int V, const double *P, const int32_t *W, const int32_t *
     or_orb_pattern(pat);
     const int akaze = mo->detector_type == 0;
     const int db = akaze ? 64 : 32;
-    r->dbytes = db;
     for (int v = 0; v < V; ++v) {
         int n;
         if (akaze) {
@@ -716,7 +732,7 @@ or_seeds *or_seeds_run(int V, const double *P, const int32_t *W, const int32_t *
             n = or_akaze_view(bgr[v], W[v], H[v], mo, &kv[v], &dv[v], &nd);
             if (n < 0)
                 return NULL;
-            r->n_detected += nd;
+            n_detected += nd;
         } else {
             Level lv[16];
             memset(lv, 0, sizeof(lv));
@@ -728,7 +744,7 @@ or_seeds *or_seeds_run(int V, const double *P, const int32_t *W, const int32_t *
                 return NULL;
             }
             n = orb_detect(lv, mo, &kv[v]);
-            r->n_detected += n;
+            n_detected += n;
             n = filter_keypoints(kv[v], n, W[v], H[v], mo);
             dv[v] = (uint8_t *)malloc((size_t)32 * (n + 1));
             describe(lv, kv[v], n, pat, dv[v]);
@@ -738,35 +754,65 @@ or_seeds *or_seeds_run(int V, const double *P, const int32_t *W, const int32_t *
             }
         }
         nv[v] = n;
-        r->kp_off[v + 1] = r->kp_off[v] + n;
+        kp_off[v + 1] = kp_off[v] + n;
     }
-    int64_t nk = r->kp_off[V];
-    r->kp = (or_keypoint *)malloc(sizeof(or_keypoint) * (size_t)(nk + 1));
-    r->desc = (uint8_t *)malloc((size_t)db * (nk + 1));
+    int64_t nk = kp_off[V];
+    or_keypoint *kp = (or_keypoint *)malloc(sizeof(or_keypoint) * (size_t)(nk + 1));
+    uint8_t *desc = (uint8_t *)malloc((size_t)db * (nk + 1));
     for (int v = 0; v < V; ++v) {
-        memcpy(r->kp + r->kp_off[v], kv[v], sizeof(or_keypoint) * (size_t)nv[v]);
-        memcpy(r->desc + db * r->kp_off[v], dv[v], (size_t)db * nv[v]);
+        memcpy(kp + kp_off[v], kv[v], sizeof(or_keypoint) * (size_t)nv[v]);
+        memcpy(desc + db * kp_off[v], dv[v], (size_t)db * nv[v]);
         free(kv[v]);
         free(dv[v]);
     }
     free(kv);
     free(dv);
     free(nv);
+    or_seeds *r = or_seeds_from_keypoints(V, P, kp_off, kp, desc, db, mo);
+    r->n_detected = n_detected;
+    free(kp_off);
+    free(kp);
+    free(desc);
+    return r;
+}
+
+/* The stages after the detectors (DefaultPairsList, MatchKeypoints /
+ * DirectEpipolarMatching, FilterMatches, TriangulateMatches) on given
+ * keypoints: view v holds kp[kp_off[v] .. kp_off[v + 1]) with descriptors of
+ * dbytes (32 or 64) bytes each.  The inputs are copied. */
+or_seeds *or_seeds_from_keypoints(int V, const double *P, const int64_t *kp_off, const or_keypoint *kp,
+                                  const uint8_t *desc, int dbytes, const or_matcher_options *mo)
+{
+    or_seeds *r = (or_seeds *)calloc(1, sizeof(or_seeds));
+    r->V = V;
+    const int db = dbytes;
+    r->dbytes = db;
+    r->kp_off = (int64_t *)calloc((size_t)V + 1, sizeof(int64_t));
+    memcpy(r->kp_off, kp_off, sizeof(int64_t) * ((size_t)V + 1));
+    int64_t nk = r->kp_off[V];
+    r->n_detected = nk;
+    r->kp = (or_keypoint *)malloc(sizeof(or_keypoint) * (size_t)(nk + 1));
+    r->desc = (uint8_t *)malloc((size_t)db * (nk + 1));
+    memcpy(r->kp, kp, sizeof(or_keypoint) * (size_t)nk);
+    memcpy(r->desc, desc, (size_t)db * nk);
     /* pairs */
     int np = V * (V - 1) / 2;
     r->npairs = np;
     r->pair_first = (int32_t *)malloc(sizeof(int32_t) * (size_t)(np + 1));
     r->pair_second = (int32_t *)malloc(sizeof(int32_t) * (size_t)(np + 1));
     r->q_off = (int64_t *)calloc((size_t)np + 1, sizeof(int64_t));
+    r->t_off = (int64_t *)calloc((size_t)np + 1, sizeof(int64_t));
     int p = 0;
     for (int i = 0; i < V; ++i)
         for (int j = i + 1; j < V; ++j) {
             r->pair_first[p] = i;
             r->pair_second[p] = j;
             r->q_off[p + 1] = r->q_off[p] + (r->kp_off[i + 1] - r->kp_off[i]);
+            r->t_off[p + 1] = r->t_off[p] + (r->kp_off[j + 1] - r->kp_off[j]);
             ++p;
         }
     r->q2t = (int32_t *)malloc(sizeof(int32_t) * (size_t)(r->q_off[np] + 1));
+    r->t2q = (int32_t *)malloc(sizeof(int32_t) * (size_t)(r->t_off[np] + 1));
     int32_t **t2q = (int32_t **)calloc((size_t)np + 1, sizeof(void *));
     for (p = 0; p < np; ++p) {
         int i = r->pair_first[p], j = r->pair_second[p];
@@ -775,7 +821,7 @@ or_seeds *or_seeds_run(int V, const double *P, const int32_t *W, const int32_t *
         double F[9];
         or_fundamental_matrix(P + 12 * i, P + 12 * j, F);
         int32_t *q2t = r->q2t + r->q_off[p];
-        t2q[p] = (int32_t *)malloc(sizeof(int32_t) * (size_t)(nt + 1));
+        t2q[p] = r->t2q + r->t_off[p];
         for (int64_t k = 0; k < nt; ++k)
             t2q[p][k] = -1;
         if (!mo->epipolar_matching) {
@@ -825,6 +871,7 @@ or_seeds *or_seeds_run(int V, const double *P, const int32_t *W, const int32_t *
     }
     /* TriangulateMatches, (view, keypoint) order */
     r->xyz = (double *)malloc(sizeof(double) * 3 * (size_t)(nk + 1));
+    r->trk_off = (int64_t *)calloc((size_t)nk + 2, sizeof(int64_t));
     for (int v = 0; v < V; ++v)
         for (int64_t k = 0; k < r->kp_off[v + 1] - r->kp_off[v]; ++k) {
             Dlt d;
@@ -832,6 +879,8 @@ or_seeds *or_seeds_run(int V, const double *P, const int32_t *W, const int32_t *
             const or_keypoint *me = r->kp + r->kp_off[v] + k;
             dlt_obs(&d, P + 12 * v, (float)nearest_int_f(me->x), (float)nearest_int_f(me->y));
             int m = 0;
+            const int64_t t0 = r->trk_off[r->n_points];
+            track_push(r, t0, v, (int)k);
             for (p = 0; p < np; ++p) {
                 int ov, ok;
                 if (r->pair_first[p] == v) {
@@ -848,14 +897,14 @@ or_seeds *or_seeds_run(int V, const double *P, const int32_t *W, const int32_t *
                 const or_keypoint *o = r->kp + r->kp_off[ov] + ok;
                 dlt_obs(&d, P + 12 * ov, (float)nearest_int_f(o->x), (float)nearest_int_f(o->y));
                 ++m;
+                track_push(r, t0 + m, ov, ok);
             }
             if (m >= 1) {
                 dlt_solve(&d, r->xyz + 3 * r->n_points);
                 r->n_points++;
+                r->trk_off[r->n_points] = t0 + m + 1;
             }
         }
-    for (p = 0; p < np; ++p)
-        free(t2q[p]);
     free(t2q);
     return r;
 }
@@ -871,7 +920,11 @@ void or_seeds_free(or_seeds *r)
     free(r->pair_second);
     free(r->q_off);
     free(r->q2t);
+    free(r->t_off);
+    free(r->t2q);
     free(r->xyz);
+    free(r->trk_off);
+    free(r->trk);
     free(r);
 }
 
@@ -908,6 +961,28 @@ int64_t or_seeds_pair(const or_seeds *r, int p, int32_t *first_second, int32_t *
     }
     if (q2t)
         memcpy(q2t, r->q2t + r->q_off[p], sizeof(int32_t) * (size_t)n);
+    return n;
+}
+
+/* train -> query table of pair p: per keypoint of the second view the first
+ * query in list order matched to it, or -1; returns its length */
+int64_t or_seeds_pair_t2q(const or_seeds *r, int p, int32_t *t2q)
+{
+    int64_t n = r->t_off[p + 1] - r->t_off[p];
+    if (t2q)
+        memcpy(t2q, r->t2q + r->t_off[p], sizeof(int32_t) * (size_t)n);
+    return n;
+}
+
+/* the observations each point was triangulated from: off (n_points + 1) and
+ * (view, keypoint) pairs in DLT row order; returns their total number */
+int64_t or_seeds_tracks(const or_seeds *r, int64_t *off, int32_t *view_kp)
+{
+    int64_t n = r->trk_off[r->n_points];
+    if (off)
+        memcpy(off, r->trk_off, sizeof(int64_t) * (size_t)(r->n_points + 1));
+    if (view_kp)
+        memcpy(view_kp, r->trk, sizeof(int32_t) * 2 * (size_t)n);
     return n;
 }
 

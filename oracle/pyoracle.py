@@ -122,6 +122,9 @@ def _load():
         "or_epipolar_distance": (ctypes.c_float, [P, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float]),
         "or_triangulate": (None, [ctypes.c_int64, P, P, P, P]),
         "or_seeds_run": (P, [ctypes.c_int, P, P, P, P, P]),
+        "or_seeds_from_keypoints": (P, [ctypes.c_int, P, P, P, P, ctypes.c_int, P]),
+        "or_seeds_pair_t2q": (ctypes.c_int64, [P, ctypes.c_int, P]),
+        "or_seeds_tracks": (ctypes.c_int64, [P, P, P]),
         "or_seeds_free": (None, [P]),
         "or_seeds_counts": (None, [P, P]),
         "or_seeds_view": (ctypes.c_int64, [P, ctypes.c_int, P, P]),
@@ -672,24 +675,14 @@ def triangulate(projections: list, observations: list) -> np.ndarray:
     return X
 
 
-def seeds_run(P: np.ndarray, images: list, mo: OrMatcherOptions | None = None) -> dict:
-    """Full GenerateSeeds on BGR8 images (H x W x 3); every stage's output."""
-    mo = mo or matcher_options()
-    V = len(images)
-    P = np.ascontiguousarray(np.asarray(P, dtype=np.float64).reshape(V, 12))
-    imgs = [np.ascontiguousarray(im, dtype=np.uint8) for im in images]
-    W = np.array([im.shape[1] for im in imgs], dtype=np.int32)
-    H = np.array([im.shape[0] for im in imgs], dtype=np.int32)
-    ptrs = (ctypes.c_void_p * V)(*[im.ctypes.data for im in imgs])
-    h = lib.or_seeds_run(V, _p(P), _p(W), _p(H), ptrs, ctypes.byref(mo))
-    if not h:
-        raise ValueError("or_seeds_run: image too small for the pyramid")
+def _seeds_result(h, V: int) -> dict:
+    """every stage's output of an or_seeds handle, which is freed"""
     try:
         c = np.zeros(7, dtype=np.int64)
         lib.or_seeds_counts(h, _p(c))
         out = {"counts": dict(zip(["views", "pairs", "detected", "keypoints", "ratio_matches", "matches", "points"],
                                   c.tolist())),
-               "keypoints": [], "descriptors": [], "pairs": [], "q2t": []}
+               "keypoints": [], "descriptors": [], "pairs": [], "q2t": [], "t2q": []}
         db = lib.or_seeds_desc_bytes(h)
         for v in range(V):
             n = lib.or_seeds_view(h, v, None, None)
@@ -705,10 +698,51 @@ def seeds_run(P: np.ndarray, images: list, mo: OrMatcherOptions | None = None) -
             lib.or_seeds_pair(h, p, _p(fs), _p(q))
             out["pairs"].append((int(fs[0]), int(fs[1])))
             out["q2t"].append(q)
+            t = np.zeros(lib.or_seeds_pair_t2q(h, p, None), dtype=np.int32)
+            lib.or_seeds_pair_t2q(h, p, _p(t))
+            out["t2q"].append(t)
         pts = np.zeros((int(c[6]), 3))
         if len(pts):
             lib.or_seeds_points(h, _p(pts))
         out["points"] = pts
+        # per point the (view, keypoint) observations it was triangulated from, in DLT row order
+        off = np.zeros(len(pts) + 1, dtype=np.int64)
+        vk = np.zeros((lib.or_seeds_tracks(h, None, None), 2), dtype=np.int32)
+        lib.or_seeds_tracks(h, _p(off), _p(vk))
+        out["tracks"] = [vk[off[i]:off[i + 1]] for i in range(len(pts))]
         return out
     finally:
         lib.or_seeds_free(h)
+
+
+def seeds_run(P: np.ndarray, images: list, mo: OrMatcherOptions | None = None) -> dict:
+    """Full GenerateSeeds on BGR8 images (H x W x 3); every stage's output."""
+    mo = mo or matcher_options()
+    V = len(images)
+    P = np.ascontiguousarray(np.asarray(P, dtype=np.float64).reshape(V, 12))
+    imgs = [np.ascontiguousarray(im, dtype=np.uint8) for im in images]
+    W = np.array([im.shape[1] for im in imgs], dtype=np.int32)
+    H = np.array([im.shape[0] for im in imgs], dtype=np.int32)
+    ptrs = (ctypes.c_void_p * V)(*[im.ctypes.data for im in imgs])
+    h = lib.or_seeds_run(V, _p(P), _p(W), _p(H), ptrs, ctypes.byref(mo))
+    if not h:
+        raise ValueError("or_seeds_run: image too small for the pyramid")
+    return _seeds_result(h, V)
+
+
+def seeds_from_keypoints(P: np.ndarray, counts, keypoints: np.ndarray, descriptors: np.ndarray,
+                         mo: OrMatcherOptions | None = None) -> dict:
+    """The stages after the detectors (or_seeds_from_keypoints) on planted
+    keypoints: counts[v] per view, KEYPOINT_DTYPE rows view-major, n x 32 or
+    n x 64 descriptor bytes.  The result of seeds_run."""
+    mo = mo or matcher_options()
+    V = len(counts)
+    P = np.ascontiguousarray(np.asarray(P, dtype=np.float64).reshape(V, 12))
+    off = np.zeros(V + 1, dtype=np.int64)
+    off[1:] = np.cumsum(np.asarray(counts, dtype=np.int64))
+    kp = np.ascontiguousarray(keypoints, dtype=KEYPOINT_DTYPE)
+    d = np.ascontiguousarray(descriptors, dtype=np.uint8)
+    if d.ndim != 2 or d.shape[1] not in (32, 64) or len(d) != len(kp) or int(off[V]) != len(kp):
+        raise ValueError("seeds_from_keypoints: one 32- or 64-byte descriptor per keypoint, counts summing to them")
+    h = lib.or_seeds_from_keypoints(V, _p(P), _p(off), _p(kp), _p(d), d.shape[1], ctypes.byref(mo))
+    return _seeds_result(h, V)

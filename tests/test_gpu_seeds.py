@@ -46,6 +46,7 @@ def compare_run(eng, r, mo_kw, V):
         fa, fb, q2t = m.matches(p)
         assert (fa, fb) == (a, b)
         assert np.array_equal(q2t, r["q2t"][p]), f"pair {p}: match tables differ"
+        assert np.array_equal(m.t2q(p), r["t2q"][p]), f"pair {p}: train-side match tables differ"
     assert np.array_equal(bits(pts), bits(r["points"]))
     return m
 
