@@ -1,13 +1,16 @@
 // dp_buf.h -- the owning resource types of the host code: device memory that
 // only grows (DevBuf), pinned host memory that only grows (HostBuf), an exact
-// device allocation (DevMem) and an event (Event).  Each frees in its
-// destructor, moves and does not copy, so a context's members need no
-// hand-written cleanup.  Depends on the HIP runtime API alone.
+// device allocation (DevMem) and an event (Event), and two things built from
+// them: a timed section (Timer) and striped statistics counters
+// (StripedCounters).  Each frees in its destructor, moves and does not copy, so
+// a context's members need no hand-written cleanup.  Depends on the HIP
+// runtime API alone.
 #pragma once
 
 #include <hip/hip_runtime_api.h>
 
 #include <cstddef>
+#include <cstdint>
 
 namespace dpk {
 
@@ -167,6 +170,52 @@ struct Event {
         if (e)
             (void)hipEventDestroy(e);
         e = nullptr;
+    }
+};
+
+// a timed section of a stream: begin and end record an event each, ms reads
+// the time between them once the stream has passed both
+struct Timer {
+    Event e0, e1;
+    hipError_t begin(hipStream_t s) { return hipEventRecord(e0, s); }
+    hipError_t end(hipStream_t s) { return hipEventRecord(e1, s); }
+    hipError_t ms(double &out)
+    {
+        float t = 0.0f;
+        const hipError_t e = hipEventElapsedTime(&t, e0, e1);
+        out = (double)t;
+        return e;
+    }
+};
+
+// `counters` statistics kept `stripes` times on the device, so that the waves'
+// adds (wave_count, dp_mapdev.h) spread over as many addresses, and their
+// pinned copy; `extra` pinned words behind the copy take the totals a stage
+// reads in the same wait
+struct StripedCounters {
+    DevBuf<unsigned long long> dev;
+    HostBuf<unsigned long long> host;
+    int stripes = 0, counters = 0;
+    size_t words() const { return (size_t)stripes * (size_t)counters; }
+    hipError_t reserve(int stripes_, int counters_, size_t extra_words = 0)
+    {
+        stripes = stripes_, counters = counters_;
+        const hipError_t e = dev.reserve(words());
+        return e != hipSuccess ? e : host.resize(words() + extra_words);
+    }
+    hipError_t zero(hipStream_t s) { return hipMemsetAsync(dev.p, 0, sizeof(unsigned long long) * words(), s); }
+    // queues the copy; the sums are valid once the stream has passed it
+    hipError_t read(hipStream_t s)
+    {
+        return hipMemcpyAsync(host.p, dev.p, sizeof(unsigned long long) * words(), hipMemcpyDeviceToHost, s);
+    }
+    unsigned long long *extra() { return host.p + words(); }
+    int64_t sum(int k) const
+    {
+        int64_t t = 0;
+        for (int st = 0; st < stripes; ++st)
+            t += (int64_t)host.p[st * counters + k];
+        return t;
     }
 };
 

@@ -3,18 +3,22 @@
 // views, pyramid, filter, batch refine/expand; dp_densify.hip: the densify
 // engine; dp_fast.hip: performance mode; dp_synth.hip: synthetic scenes and
 // probes; dp_seeds_capi.hip, dp_seeds_orb.hip, dp_seeds_akaze.hip: seed
-// generation (their own state is dp_seedgen.h); dp_render.hip: maps;
-// dp_fuse.hip: their fusion; dp_mapref.hip: their refinement; dp_tsdf.hip:
-// their volume and mesh; dp_meshclean.hip: the mesh's components).  Every member that owns a device or pinned
-// allocation or an event has an owning type (dp_buf.h), so deleting the
-// context frees them; only the views and the pyramid (free_views) and the
-// stream, which must outlive them all, are released by hand.
+// generation (their own state is dp_seedgen.h); the map stages --
+// dp_render.hip: maps; dp_fuse.hip: their fusion; dp_mapref.hip: their
+// refinement; dp_tsdf.hip: their volume and mesh; dp_meshclean.hip: the mesh's
+// components -- each with its scratch as one named member of the context and
+// the host helpers they share at the end of this file).  Every member that
+// owns a device or pinned allocation or an event has an owning type
+// (dp_buf.h), so deleting the context frees them; only the views and the
+// pyramid (free_views) and the stream, which must outlive them all, are
+// released by hand.
 #pragma once
 
 #include "dp_buf.h"
 #include "dp_internal.h"
 
 #include <chrono>
+#include <cmath>
 #include <memory>
 #include <string>
 #include <thread>
@@ -54,6 +58,89 @@ using dpk::DevMem;
 using dpk::Event;
 using dpk::HostBuf;
 using dpk::parallel_for;
+
+using dpk::StripedCounters;
+using dpk::Timer;
+
+namespace dpk {
+
+// ---- the map stages' scratch, one struct per stage (dp_ctx::render, fuse,
+// mapref, tsdf, clean); `time` is the section behind the stage's *_ms, `in`,
+// `out` and `io` stage the host forms' planes ----------------------------------
+
+// dp_render_maps: the pair list, the counters (kRenderCounters, then one per
+// chunk), the slot tables
+struct RenderScratch {
+    DevBuf<unsigned long long> count;
+    DevBuf<RenderPair> pairs;
+    DevBuf<RenderSlot> slots;
+    DevBuf<int32_t> slot_of;
+    DevBuf<unsigned char> out;
+    Timer time;
+};
+
+// dp_fuse_maps: emitted flags, per-block counts and their scan, the view table,
+// the host form's device and pinned points
+struct FuseScratch {
+    DevBuf<uint8_t> flag;
+    DevBuf<unsigned long long> bcount, boff;
+    StripedCounters count; // + the scan's total
+    DevBuf<FuseView> tab;
+    DevBuf<unsigned char> in;
+    DevBuf<dp_fused_point> pts;
+    HostBuf<dp_fused_point> res;
+    Timer time;
+};
+
+// dp_refine_maps
+struct MaprefScratch {
+    DevBuf<MaprefView> tab;
+    StripedCounters count;
+    DevBuf<unsigned char> io;
+    Timer time;
+};
+
+// dp_tsdf_integrate / dp_tsdf_mesh: the view table, the host forms' staged
+// inputs and volume; the mesh's edge flags (one byte per lattice point, in
+// 32-bit words), per-cell triangle counts, per-point first vertex numbers,
+// per-block counts and their scans, the host form's device and pinned results
+// (it times its two phases apart)
+struct TsdfScratch {
+    DevBuf<TsdfView> tab;
+    StripedCounters count; // the mesh: the active cells' stripes + the vertex and triangle totals
+    DevBuf<unsigned long long> bcount, boff;
+    DevBuf<unsigned char> in, vol;
+    DevBuf<uint32_t> flags, vbase;
+    DevBuf<uint8_t> tcount;
+    DevBuf<dp_mesh_vertex> verts;
+    DevBuf<int32_t> tris;
+    HostBuf<dp_mesh_vertex> hverts;
+    HostBuf<int32_t> htris;
+    Timer time[2];
+};
+
+// dp_mesh_components / dp_mesh_clean: the union-find parents (the labels after
+// the flatten), used flags, per-root triangle and vertex counts, component
+// numbers (at roots), kept flags (by component number), the rank sort's keys,
+// the new vertex numbers, per-block counts and their scans, Tmax; the host
+// forms' staged inputs, device results and pinned results (they time their
+// phases apart)
+struct CleanScratch {
+    DevBuf<int32_t> parent, tcnt, vcnt, cnum, vmap, tmax;
+    DevBuf<uint8_t> used, keptc;
+    DevBuf<unsigned long long> keys, keys_sorted, bcount, boff;
+    StripedCounters count; // + C, the kept vertex and triangle totals, Tmax
+    DevBuf<unsigned char> in;
+    DevBuf<int32_t> maps, tris;
+    DevBuf<dp_mesh_vertex> verts;
+    DevBuf<dp_mesh_component> comps;
+    HostBuf<int32_t> htris;
+    HostBuf<dp_mesh_vertex> hverts;
+    HostBuf<dp_mesh_component> hcomps;
+    Timer time[3];
+};
+
+} // namespace dpk
 
 struct SeedgenFree {
     void operator()(dp_seedgen *s) const { dp_seedgen_free(s); }
@@ -95,70 +182,18 @@ struct dp_ctx {
     DevBuf<uint8_t> f_alive, f_keep;
     DevBuf<double> f_rho;
     DevBuf<dp_patch> f_pat;
-    // dp_render_maps: z-buffer (8 B per pixel of the requested views), pair list,
-    // counters (dpk::kRenderCounters, then one per chunk), slot tables, the host
-    // form's output planes, timing events
-    DevBuf<unsigned long long> r_z, r_count;
-    DevBuf<dpk::RenderPair> r_pairs;
-    DevBuf<dpk::RenderSlot> r_slots;
-    DevBuf<int32_t> r_slot_of;
-    DevBuf<unsigned char> r_out;
-    Event r_e0, r_e1;
-    // dp_fuse_maps: the per-pixel masks live in r_z (8 B per pixel of the
-    // requested views, as the z-buffer; the calls never overlap); emitted flags,
-    // per-block counts and their scan, striped counters, the view table, the
-    // host form's staged planes and points, the statistics read, timing events
-    DevBuf<uint8_t> u_flag;
-    DevBuf<unsigned long long> u_bcount, u_boff, u_count;
-    DevBuf<dpk::FuseView> u_tab;
-    DevBuf<unsigned char> u_in;
-    DevBuf<dp_fused_point> u_pts;
-    HostBuf<dp_fused_point> u_res;
-    HostBuf<unsigned long long> u_hcount;
-    Event u_e0, u_e1;
-    // dp_refine_maps: the view table, striped counters and their host copy,
-    // the host form's staged input and output planes, timing events
-    DevBuf<dpk::MaprefView> m_tab;
-    DevBuf<unsigned long long> m_count;
-    HostBuf<unsigned long long> m_hcount;
-    DevBuf<unsigned char> m_io;
-    Event m_e0, m_e1;
-    // dp_tsdf_integrate / dp_tsdf_mesh: the view table, striped counters and the
-    // statistics read, the host forms' staged inputs and volume; the mesh's edge
-    // flags (one byte per lattice point, in 32-bit words), per-cell triangle
-    // counts, per-point first vertex numbers, per-block counts and their scans,
-    // the host form's device and pinned results, timing events (the host form
-    // of the mesh times its two phases apart)
-    DevBuf<dpk::TsdfView> t_tab;
-    DevBuf<unsigned long long> t_count, t_bcount, t_boff;
-    HostBuf<unsigned long long> t_hcount;
-    DevBuf<unsigned char> t_in, t_vol;
-    DevBuf<uint32_t> t_flags, t_vbase;
-    DevBuf<uint8_t> t_tcount;
-    DevBuf<dp_mesh_vertex> t_verts;
-    DevBuf<int32_t> t_tris;
-    HostBuf<dp_mesh_vertex> t_hverts;
-    HostBuf<int32_t> t_htris;
-    Event t_e0, t_e1, t_e2, t_e3;
-    // dp_mesh_components / dp_mesh_clean: the union-find parents (the labels
-    // after the flatten), used flags, per-root triangle and vertex counts,
-    // component numbers (at roots), kept flags (by component number), the rank
-    // sort's keys, the new vertex numbers, per-block counts and their scans,
-    // striped counters, Tmax, the statistics read; the host forms' staged
-    // inputs, device results and pinned results; timing events (the host forms
-    // time their phases apart)
-    DevBuf<int32_t> c_parent, c_tcnt, c_vcnt, c_cnum, c_vmap, c_tmax;
-    DevBuf<uint8_t> c_used, c_keptc;
-    DevBuf<unsigned long long> c_keys, c_keys_sorted, c_bcount, c_boff, c_count;
-    HostBuf<unsigned long long> c_hcount;
-    DevBuf<unsigned char> c_in;
-    DevBuf<int32_t> c_maps, c_tris;
-    DevBuf<dp_mesh_vertex> c_verts;
-    DevBuf<dp_mesh_component> c_comps;
-    HostBuf<int32_t> c_htris;
-    HostBuf<dp_mesh_vertex> c_hverts;
-    HostBuf<dp_mesh_component> c_hcomps;
-    Event c_e[6];
+    // Buffers shared on purpose by stages whose calls never overlap on a context:
+    //   pix64          8 B per pixel of the requested views: dp_render_maps'
+    //                  z-buffer and dp_fuse_maps' masks
+    //   f_rho          the filter's rho, which is also dp_render_maps' splat radius
+    //   f_pat, f_keep  the filter's staging of host patches and flags, which the
+    //                  host form of dp_render_maps stages its own in
+    DevBuf<unsigned long long> pix64;
+    dpk::RenderScratch render;
+    dpk::FuseScratch fuse;
+    dpk::MaprefScratch mapref;
+    dpk::TsdfScratch tsdf;
+    dpk::CleanScratch clean;
     HostBuf<dp_patch> result; // dp_densify / dp_densify_result output (pinned)
     // dp_densify_iterate: per iteration {evaluations, filter survivors} on the
     // device (read once, at the end) and the filters' timing events
@@ -267,7 +302,58 @@ static inline int fail(dp_ctx *c, int code, const std::string &msg)
     return code;
 }
 
-#define DP_HIP(c, expr)                                                                       \
+// ---- host helpers shared by the map stages' C-ABI halves ----------------------
+
+// The `views` argument of a map stage: set, 1..min(V, cap) ids, each unique and
+// < V; `who` is the entry point named in the message.  A stage without a cap
+// of its own passes DP_MAX_VIEWS.
+static inline int check_view_list(dp_ctx *c, const char *who, const int32_t *views, int n_views, int cap)
+{
+    const std::string w(who);
+    if (c->V <= 0)
+        return fail(c, DP_E_STATE, w + ": no views set");
+    if (!views || n_views < 1 || n_views > c->V || n_views > cap)
+        return fail(c, DP_E_ARG,
+                    w + (cap < DP_MAX_VIEWS ? ": n_views must be in 1..min(V, " + std::to_string(cap) + ")"
+                                            : ": n_views must be in 1..V"));
+    uint64_t seen[2] = {0, 0};
+    for (int k = 0; k < n_views; ++k) {
+        const int32_t v = views[k];
+        if (v < 0 || v >= c->V || ((seen[v >> 6] >> (v & 63)) & 1ull))
+            return fail(c, DP_E_ARG, w + ": view ids must be unique and < V");
+        seen[v >> 6] |= 1ull << (v & 63);
+    }
+    return DP_OK;
+}
+
+// P of the view with the adjugate and the determinant of its left 3x3 (the
+// spec's view table entry); false when the matrix is singular
+static inline bool view_inverse(const dpg::ViewDev &v, dpk::ViewInv &t)
+{
+    const double *P = v.P;
+    const double h[9] = {P[0], P[1], P[2], P[4], P[5], P[6], P[8], P[9], P[10]};
+    for (int j = 0; j < 12; ++j)
+        t.P[j] = P[j];
+    t.det = dpg::adjugate3(h, t.A);
+    return t.det != 0.0 && std::isfinite(t.det);
+}
+
+// pixels of view v at the current level
+static inline size_t view_pixels(const dp_ctx *c, int32_t v) { return (size_t)c->hv[v].W * (size_t)c->hv[v].H; }
+
+// the layout of a host form's planes in one staging buffer: add returns the
+// plane's offset, 256-B aligned; total is the buffer's size
+struct PlanePacker {
+    size_t total = 0;
+    size_t add(size_t bytes)
+    {
+        const size_t off = total;
+        total += (bytes + 255) & ~(size_t)255;
+        return off;
+    }
+};
+
+#define DP_HIP(c, expr)                                                                      \
     do {                                                                                      \
         hipError_t _e = (expr);                                                               \
         if (_e != hipSuccess)                                                                 \

@@ -22,6 +22,7 @@
 // the host knows: no host read between the passes.  Every decision is a
 // function of the planes and, for the suppression, of the pass-1 masks alone.
 #include "dp_ctx.h"
+#include "dp_mapdev.h"
 
 #include <hipcub/hipcub.hpp>
 
@@ -30,38 +31,11 @@
 namespace dpk {
 namespace {
 
-__device__ __forceinline__ uint32_t lanes_below(uint64_t m)
-{
-    const uint32_t lo = __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u);
-    return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), lo);
-}
-
-__device__ __forceinline__ bool is_depth(float z) { return z > 0.0f && z <= 3.402823466e+38f; }
-
-__device__ __forceinline__ void backproject(const FuseView &v, int x, int y, float z, double *X)
-{
-    const double zd = (double)z;
-    const double b0 = zd * (double)x - v.P[3];
-    const double b1 = zd * (double)y - v.P[7];
-    const double b2 = zd - v.P[11];
-    for (int j = 0; j < 3; ++j)
-        X[j] = ((v.A[3 * j] * b0 + v.A[3 * j + 1] * b1) + v.A[3 * j + 2] * b2) / v.det;
-}
-
 // steps 1-4 of observe: the matched pixel of X in view s, its index and depth
 __device__ __forceinline__ bool match(const FuseView &s, const double *X, double &d, int64_t &at, float &zs)
 {
-    d = ((s.P[8] * X[0] + s.P[9] * X[1]) + s.P[10] * X[2]) + s.P[11];
-    if (!(d > 0.0))
-        return false;
-    const double h0 = ((s.P[0] * X[0] + s.P[1] * X[1]) + s.P[2] * X[2]) + s.P[3];
-    const double h1 = ((s.P[4] * X[0] + s.P[5] * X[1]) + s.P[6] * X[2]) + s.P[7];
-    double u, v;
-    dpg::div2(h0, h1, d, u, v);
-    if (!(fabs(u) < 2.0e9) || !(fabs(v) < 2.0e9))
-        return false;
-    const int32_t xi = (int32_t)rint(u), yi = (int32_t)rint(v);
-    if (xi < 0 || xi >= s.W || yi < 0 || yi >= s.H)
+    int32_t xi, yi;
+    if (!nearest_pixel(s.inv.P, s.W, s.H, X, d, xi, yi))
         return false;
     at = (int64_t)yi * s.W + xi;
     zs = s.depth[at];
@@ -81,15 +55,6 @@ __device__ __forceinline__ bool agrees(const FuseArgs &a, const FuseView &s, dou
     return c >= 0.0 && c * c >= a.cos2 * (dpg::dot3(nr, nr) * dpg::dot3(ns, ns));
 }
 
-// one add per wave and counter, spread over kFuseStripes copies
-__device__ __forceinline__ void wave_count(const FuseArgs &a, int counter, unsigned long long v, uint32_t stripe)
-{
-    for (int o = 32; o > 0; o >>= 1)
-        v += __shfl_xor(v, o);
-    if ((threadIdx.x & 63) == 0 && v)
-        atomicAdd(&a.count[(stripe & (kFuseStripes - 1)) * kFuseCounters + counter], v);
-}
-
 __global__ __launch_bounds__(kFuseBlock) void fuse_mask_kernel(FuseArgs a)
 {
     const int k = blockIdx.y;
@@ -102,7 +67,7 @@ __global__ __launch_bounds__(kFuseBlock) void fuse_mask_kernel(FuseArgs a)
         return;
     double X[3] = {0.0, 0.0, 0.0}, nr[3] = {0.0, 0.0, 0.0};
     if (part) {
-        backproject(r, (int)(i % r.W), (int)(i / r.W), z, X);
+        backproject(r.inv, (double)(int)(i % r.W), (double)(int)(i / r.W), (double)z, X);
         if (a.has_normals)
             for (int j = 0; j < 3; ++j)
                 nr[j] = (double)r.normal[3 * i + j];
@@ -125,9 +90,9 @@ __global__ __launch_bounds__(kFuseBlock) void fuse_mask_kernel(FuseArgs a)
     if (part)
         a.mask[r.poff + i] = mask;
     const uint32_t stripe = blockIdx.x * (kFuseBlock / 64) + (threadIdx.x >> 6);
-    wave_count(a, 0, part ? 1ull : 0ull, stripe);
-    wave_count(a, 1, (unsigned long long)matched, stripe);
-    wave_count(a, 2, (unsigned long long)__popcll(mask), stripe);
+    wave_count<kFuseStripes, kFuseCounters>(a.count, 0, part ? 1ull : 0ull, stripe);
+    wave_count<kFuseStripes, kFuseCounters>(a.count, 1, (unsigned long long)matched, stripe);
+    wave_count<kFuseStripes, kFuseCounters>(a.count, 2, (unsigned long long)__popcll(mask), stripe);
 }
 
 __global__ __launch_bounds__(kFuseBlock) void fuse_count_kernel(FuseArgs a)
@@ -151,7 +116,7 @@ __global__ __launch_bounds__(kFuseBlock) void fuse_count_kernel(FuseArgs a)
     if (__any(lower != 0)) {
         double X[3] = {0.0, 0.0, 0.0};
         if (lower)
-            backproject(r, (int)(i % r.W), (int)(i / r.W), z, X);
+            backproject(r.inv, (double)(int)(i % r.W), (double)(int)(i / r.W), (double)z, X);
         for (int kp = 0; kp < k; ++kp) {
             const bool bit = (lower >> kp) & 1ull;
             if (!__any(bit))
@@ -177,7 +142,8 @@ __global__ __launch_bounds__(kFuseBlock) void fuse_count_kernel(FuseArgs a)
             t += wc[w];
         a.bcount[(int64_t)blockIdx.y * gridDim.x + blockIdx.x] = t;
     }
-    wave_count(a, 3, fusable ? 1ull : 0ull, blockIdx.x * (kFuseBlock / 64) + (threadIdx.x >> 6));
+    const uint32_t stripe = blockIdx.x * (kFuseBlock / 64) + (threadIdx.x >> 6);
+    wave_count<kFuseStripes, kFuseCounters>(a.count, 3, fusable ? 1ull : 0ull, stripe);
 }
 
 __global__ __launch_bounds__(kFuseBlock) void fuse_emit_kernel(FuseArgs a)
@@ -205,7 +171,7 @@ __global__ __launch_bounds__(kFuseBlock) void fuse_emit_kernel(FuseArgs a)
     double acc[3] = {0.0, 0.0, 0.0}, sum[3] = {0.0, 0.0, 0.0}, X[3] = {0.0, 0.0, 0.0};
     uint64_t mask = 0;
     if (writes) {
-        backproject(r, x, y, r.depth[i], X);
+        backproject(r.inv, (double)x, (double)y, (double)r.depth[i], X);
         mask = a.mask[r.poff + i];
         for (int j = 0; j < 3; ++j) {
             acc[j] = X[j];
@@ -223,7 +189,7 @@ __global__ __launch_bounds__(kFuseBlock) void fuse_emit_kernel(FuseArgs a)
         float zs;
         if (bit && match(s, X, d, at, zs)) {
             double Y[3];
-            backproject(s, (int)(at % s.W), (int)(at / s.W), zs, Y);
+            backproject(s.inv, (double)(int)(at % s.W), (double)(int)(at / s.W), (double)zs, Y);
             for (int j = 0; j < 3; ++j) {
                 acc[j] += Y[j];
                 if (a.has_normals)
@@ -302,47 +268,15 @@ static int fuse_check(dp_ctx *c, const int32_t *views, int n_views, const dp_fus
         return fail(c, DP_E_ARG, "dp_fuse_maps: min_normal_cos must be in 0..1");
     if (!n_out)
         return fail(c, DP_E_ARG, "dp_fuse_maps: n_out must be given");
-    if (c->V <= 0)
-        return fail(c, DP_E_STATE, "dp_fuse_maps: no views set");
-    if (!views || n_views < 1 || n_views > c->V || n_views > 64)
-        return fail(c, DP_E_ARG, "dp_fuse_maps: n_views must be in 1..min(V, 64)");
-    uint64_t seen[2] = {0, 0};
-    for (int k = 0; k < n_views; ++k) {
-        const int32_t v = views[k];
-        if (v < 0 || v >= c->V || ((seen[v >> 6] >> (v & 63)) & 1ull))
-            return fail(c, DP_E_ARG, "dp_fuse_maps: view ids must be unique and < V");
-        seen[v >> 6] |= 1ull << (v & 63);
-    }
+    const int rc = check_view_list(c, "dp_fuse_maps", views, n_views, 64);
+    if (rc != DP_OK)
+        return rc;
     if (!depth)
         return fail(c, DP_E_ARG, "dp_fuse_maps: depth planes must be given");
     for (int k = 0; k < n_views; ++k)
         if (!depth[k] || (normal && !normal[k]))
             return fail(c, DP_E_ARG, "dp_fuse_maps: a plane pointer is NULL");
     return DP_OK;
-}
-
-// the view table entry of the spec: adjugate and determinant of the left 3x3
-static bool fuse_view(const dpg::ViewDev &v, dpk::FuseView &t)
-{
-    const double *P = v.P;
-    const double h[9] = {P[0], P[1], P[2], P[4], P[5], P[6], P[8], P[9], P[10]};
-    for (int j = 0; j < 12; ++j)
-        t.P[j] = P[j];
-    t.A[0] = h[4] * h[8] - h[5] * h[7];
-    t.A[1] = h[2] * h[7] - h[1] * h[8];
-    t.A[2] = h[1] * h[5] - h[2] * h[4];
-    t.A[3] = h[5] * h[6] - h[3] * h[8];
-    t.A[4] = h[0] * h[8] - h[2] * h[6];
-    t.A[5] = h[2] * h[3] - h[0] * h[5];
-    t.A[6] = h[3] * h[7] - h[4] * h[6];
-    t.A[7] = h[1] * h[6] - h[0] * h[7];
-    t.A[8] = h[0] * h[4] - h[1] * h[3];
-    t.det = (h[0] * t.A[0] + h[1] * t.A[3]) + h[2] * t.A[6];
-    t.W = v.W;
-    t.H = v.H;
-    t.pitch = v.pitch;
-    t.img = v.img;
-    return t.det != 0.0 && std::isfinite(t.det);
 }
 
 extern "C" int dp_fuse_maps_device(dp_ctx *c, const int32_t *views, int n_views, const dp_fuse_options *fo,
@@ -363,8 +297,13 @@ extern "C" int dp_fuse_maps_device(dp_ctx *c, const int32_t *views, int n_views,
     int64_t pixels = 0, max_px = 0;
     for (int k = 0; k < n_views; ++k) {
         dpk::FuseView &t = tab[(size_t)k];
-        if (!fuse_view(c->hv[views[k]], t))
+        const dpg::ViewDev &v = c->hv[views[k]];
+        if (!view_inverse(v, t.inv))
             return fail(c, DP_E_ARG, "dp_fuse_maps: a requested view's left 3x3 is singular");
+        t.W = v.W;
+        t.H = v.H;
+        t.pitch = v.pitch;
+        t.img = v.img;
         t.view = views[k];
         t.depth = d_depth[k];
         t.normal = d_normal ? d_normal[k] : nullptr;
@@ -377,70 +316,61 @@ extern "C" int dp_fuse_maps_device(dp_ctx *c, const int32_t *views, int n_views,
     }
     hipSetDevice(c->device);
     hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    DP_HIP(c, c->u_e0.create());
-    DP_HIP(c, c->u_e1.create());
     const unsigned gx = (unsigned)std::max<int64_t>((max_px + dpk::kFuseBlock - 1) / dpk::kFuseBlock, 1);
     const int64_t blocks = (int64_t)gx * n_views;
     if (blocks > 0x7FFFFFFFll - 1)
         return fail(c, DP_E_ARG, "dp_fuse_maps: too many pixels");
-    const size_t ncount = (size_t)dpk::kFuseStripes * dpk::kFuseCounters;
-    DP_HIP(c, c->r_z.reserve((size_t)std::max<int64_t>(pixels, 1)));
-    DP_HIP(c, c->u_flag.reserve((size_t)std::max<int64_t>(pixels, 1)));
-    DP_HIP(c, c->u_bcount.reserve((size_t)blocks + 1));
-    DP_HIP(c, c->u_boff.reserve((size_t)blocks + 1));
-    DP_HIP(c, c->u_count.reserve(ncount));
-    DP_HIP(c, c->u_tab.reserve((size_t)n_views));
-    DP_HIP(c, c->u_hcount.resize(ncount + 1));
+    DP_HIP(c, c->pix64.reserve((size_t)std::max<int64_t>(pixels, 1)));
+    DP_HIP(c, c->fuse.flag.reserve((size_t)std::max<int64_t>(pixels, 1)));
+    DP_HIP(c, c->fuse.bcount.reserve((size_t)blocks + 1));
+    DP_HIP(c, c->fuse.boff.reserve((size_t)blocks + 1));
+    DP_HIP(c, c->fuse.count.reserve(dpk::kFuseStripes, dpk::kFuseCounters, 1));
+    DP_HIP(c, c->fuse.tab.reserve((size_t)n_views));
     size_t scan_bytes = 0;
-    DP_HIP(c, hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, c->u_bcount.p, c->u_boff.p, (int)(blocks + 1), s));
+    DP_HIP(c, hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, c->fuse.bcount.p, c->fuse.boff.p, (int)(blocks + 1),
+                                               s));
     DP_HIP(c, c->scan_tmp.reserve(scan_bytes ? scan_bytes : 1));
 
     dpk::FuseArgs a{};
-    a.tab = c->u_tab.p;
+    a.tab = c->fuse.tab.p;
     a.K = n_views;
     a.min_views = o.min_views;
     a.no_suppress = (o.flags & DP_FUSE_NO_SUPPRESS) ? 1 : 0;
     a.has_normals = d_normal ? 1 : 0;
     a.tol = (double)o.depth_tol;
     a.cos2 = (double)o.min_normal_cos * (double)o.min_normal_cos;
-    a.mask = c->r_z.p;
-    a.flag = c->u_flag.p;
-    a.bcount = c->u_bcount.p;
-    a.boff = c->u_boff.p;
-    a.count = c->u_count.p;
+    a.mask = c->pix64.p;
+    a.flag = c->fuse.flag.p;
+    a.bcount = c->fuse.bcount.p;
+    a.boff = c->fuse.boff.p;
+    a.count = c->fuse.count.dev.p;
     a.out = d_points;
     a.cap = cap;
 
     // the table is a small pageable copy: staged before the call returns
-    DP_HIP(c, hipMemcpyAsync(c->u_tab.p, tab.data(), sizeof(dpk::FuseView) * tab.size(), hipMemcpyHostToDevice, s));
-    DP_HIP(c, hipEventRecord(c->u_e0, s));
-    DP_HIP(c, hipMemsetAsync(c->u_count.p, 0, sizeof(unsigned long long) * ncount, s));
-    DP_HIP(c, hipMemsetAsync(c->u_bcount.p + blocks, 0, sizeof(unsigned long long), s));
+    DP_HIP(c, hipMemcpyAsync(c->fuse.tab.p, tab.data(), sizeof(dpk::FuseView) * tab.size(), hipMemcpyHostToDevice, s));
+    DP_HIP(c, c->fuse.time.begin(s));
+    DP_HIP(c, c->fuse.count.zero(s));
+    DP_HIP(c, hipMemsetAsync(c->fuse.bcount.p + blocks, 0, sizeof(unsigned long long), s));
     DP_HIP(c, dpk::launch_fuse_mask(a, gx, s));
     DP_HIP(c, dpk::launch_fuse_count(a, gx, s));
-    DP_HIP(c, hipcub::DeviceScan::ExclusiveSum(c->scan_tmp.p, scan_bytes, c->u_bcount.p, c->u_boff.p,
+    DP_HIP(c, hipcub::DeviceScan::ExclusiveSum(c->scan_tmp.p, scan_bytes, c->fuse.bcount.p, c->fuse.boff.p,
                                                (int)(blocks + 1), s));
     DP_HIP(c, dpk::launch_fuse_emit(a, gx, s));
-    DP_HIP(c, hipEventRecord(c->u_e1, s));
+    DP_HIP(c, c->fuse.time.end(s));
     // the one wait: the counters and the scan's total
-    unsigned long long *h = c->u_hcount.data();
-    DP_HIP(c, hipMemcpyAsync(h, c->u_count.p, sizeof(unsigned long long) * ncount, hipMemcpyDeviceToHost, s));
-    DP_HIP(c, hipMemcpyAsync(h + ncount, c->u_boff.p + blocks, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    StripedCounters &n = c->fuse.count;
+    DP_HIP(c, n.read(s));
+    DP_HIP(c, hipMemcpyAsync(n.extra(), c->fuse.boff.p + blocks, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
     DP_HIP(c, hipStreamSynchronize(s));
-    *n_out = (int64_t)h[ncount];
+    *n_out = (int64_t)n.extra()[0];
     if (stats) {
-        int64_t sum[dpk::kFuseCounters] = {0, 0, 0, 0};
-        for (int st = 0; st < dpk::kFuseStripes; ++st)
-            for (int k = 0; k < dpk::kFuseCounters; ++k)
-                sum[k] += (int64_t)h[st * dpk::kFuseCounters + k];
-        float ms = 0.0f;
-        DP_HIP(c, hipEventElapsedTime(&ms, c->u_e0, c->u_e1));
-        stats->depth_pixels = sum[0];
-        stats->matched_pairs = sum[1];
-        stats->consistent_pairs = sum[2];
-        stats->fusable = sum[3];
+        stats->depth_pixels = n.sum(0);
+        stats->matched_pairs = n.sum(1);
+        stats->consistent_pairs = n.sum(2);
+        stats->fusable = n.sum(3);
         stats->emitted = *n_out;
-        stats->fuse_ms = (double)ms;
+        DP_HIP(c, c->fuse.time.ms(stats->fuse_ms));
     }
     return DP_OK;
 }
@@ -464,53 +394,49 @@ extern "C" int dp_fuse_maps(dp_ctx *c, const int32_t *views, int n_views, const 
     // holds no depth cannot be emitted, which bounds the point buffer
     std::vector<size_t> od((size_t)n_views), on((size_t)n_views);
     std::vector<int64_t> nd((size_t)n_views, 0);
-    size_t total = 0;
+    PlanePacker pack;
     for (int k = 0; k < n_views; ++k) {
-        const size_t px = (size_t)c->hv[views[k]].W * (size_t)c->hv[views[k]].H;
-        od[(size_t)k] = total;
-        total += (4 * px + 255) & ~(size_t)255;
-        if (normal) {
-            on[(size_t)k] = total;
-            total += (12 * px + 255) & ~(size_t)255;
-        }
+        od[(size_t)k] = pack.add(4 * view_pixels(c, views[k]));
+        if (normal)
+            on[(size_t)k] = pack.add(12 * view_pixels(c, views[k]));
     }
     parallel_for(n_views, [&](int64_t k) {
-        const int64_t px = (int64_t)c->hv[views[k]].W * c->hv[views[k]].H;
+        const size_t px = view_pixels(c, views[k]);
         const float *z = depth[k];
         int64_t n = 0;
-        for (int64_t i = 0; i < px; ++i)
-            n += z[i] > 0.0f && z[i] <= 3.402823466e+38f;
+        for (size_t i = 0; i < px; ++i)
+            n += dpk::is_depth(z[i]);
         nd[(size_t)k] = n;
     });
     int64_t cap = 0;
     for (int64_t n : nd)
         cap += n;
-    DP_HIP(c, c->u_in.reserve(total ? total : 1));
-    DP_HIP(c, c->u_pts.reserve((size_t)std::max<int64_t>(cap, 1)));
+    DP_HIP(c, c->fuse.in.reserve(pack.total ? pack.total : 1));
+    DP_HIP(c, c->fuse.pts.reserve((size_t)std::max<int64_t>(cap, 1)));
     std::vector<const float *> dd((size_t)n_views), dn((size_t)n_views);
     for (int k = 0; k < n_views; ++k) {
-        const size_t px = (size_t)c->hv[views[k]].W * (size_t)c->hv[views[k]].H;
-        dd[(size_t)k] = (const float *)(c->u_in.p + od[(size_t)k]);
-        DP_HIP(c, hipMemcpyAsync(c->u_in.p + od[(size_t)k], depth[k], 4 * px, hipMemcpyHostToDevice, s));
+        const size_t px = view_pixels(c, views[k]);
+        dd[(size_t)k] = (const float *)(c->fuse.in.p + od[(size_t)k]);
+        DP_HIP(c, hipMemcpyAsync(c->fuse.in.p + od[(size_t)k], depth[k], 4 * px, hipMemcpyHostToDevice, s));
         if (normal) {
-            dn[(size_t)k] = (const float *)(c->u_in.p + on[(size_t)k]);
-            DP_HIP(c, hipMemcpyAsync(c->u_in.p + on[(size_t)k], normal[k], 12 * px, hipMemcpyHostToDevice, s));
+            dn[(size_t)k] = (const float *)(c->fuse.in.p + on[(size_t)k]);
+            DP_HIP(c, hipMemcpyAsync(c->fuse.in.p + on[(size_t)k], normal[k], 12 * px, hipMemcpyHostToDevice, s));
         }
     }
     int64_t n = 0;
-    rc = dp_fuse_maps_device(c, views, n_views, &o, dd.data(), normal ? dn.data() : nullptr, c->u_pts.p, cap, &n,
+    rc = dp_fuse_maps_device(c, views, n_views, &o, dd.data(), normal ? dn.data() : nullptr, c->fuse.pts.p, cap, &n,
                              stats, s);
     if (rc != DP_OK)
         return rc;
     if (n > cap)
         return fail(c, DP_E_HIP, "dp_fuse_maps: more points than depth pixels");
-    DP_HIP(c, c->u_res.resize((size_t)std::max<int64_t>(n, 1)));
+    DP_HIP(c, c->fuse.res.resize((size_t)std::max<int64_t>(n, 1)));
     if (n > 0) {
-        DP_HIP(c, hipMemcpyAsync(c->u_res.data(), c->u_pts.p, sizeof(dp_fused_point) * (size_t)n,
+        DP_HIP(c, hipMemcpyAsync(c->fuse.res.data(), c->fuse.pts.p, sizeof(dp_fused_point) * (size_t)n,
                                  hipMemcpyDeviceToHost, s));
         DP_HIP(c, hipStreamSynchronize(s));
     }
-    *out = n > 0 ? c->u_res.data() : nullptr;
+    *out = n > 0 ? c->fuse.res.data() : nullptr;
     *n_out = n;
     return DP_OK;
 }

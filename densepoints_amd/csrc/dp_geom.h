@@ -40,6 +40,21 @@ DP_HD void cross3(const double *a, const double *b, double *o)
     o[2] = a[0] * b[1] - a[1] * b[0];
 }
 
+// A = adj(h) of the row-major 3 x 3 h; returns det(h)
+DP_HD double adjugate3(const double *h, double *A)
+{
+    A[0] = h[4] * h[8] - h[5] * h[7];
+    A[1] = h[2] * h[7] - h[1] * h[8];
+    A[2] = h[1] * h[5] - h[2] * h[4];
+    A[3] = h[5] * h[6] - h[3] * h[8];
+    A[4] = h[0] * h[8] - h[2] * h[6];
+    A[5] = h[2] * h[3] - h[0] * h[5];
+    A[6] = h[3] * h[7] - h[4] * h[6];
+    A[7] = h[1] * h[6] - h[0] * h[7];
+    A[8] = h[0] * h[4] - h[1] * h[3];
+    return (h[0] * A[0] + h[1] * A[3]) + h[2] * A[6];
+}
+
 // a / b and sqrt(a) of the per-evaluation uniform math (NCC finish, window
 // scale, means).  These quotients feed Nelder-Mead's comparisons and the
 // stored score directly -- no later rounding absorbs a 1-ulp error -- so the

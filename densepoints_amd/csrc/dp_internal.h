@@ -247,6 +247,19 @@ hipError_t launch_filter_front(const FilterArgs &a, hipStream_t s);
 hipError_t launch_filter_visibility(const FilterArgs &a, uint8_t *keep, hipStream_t s);
 hipError_t launch_filter_neighbors(const FilterArgs &a, uint8_t *keep, hipStream_t s);
 
+// ---- the map stages: render, fuse, mapref, tsdf + mesh (the mesh clean-up
+// keeps its arguments in dp_meshclean.hip).  Their shared device helpers are
+// in dp_mapdev.h; a striped counter block (k...Stripes x k...Counters words) is
+// written by its wave_count and owned by a dpk::StripedCounters (dp_buf.h). ----
+
+// A view's projection with the adjugate and the determinant of its left 3x3
+// (filled by view_inverse, dp_ctx.h): the leading member of the fuse and
+// mapref view table rows
+struct ViewInv {
+    double P[12];
+    double A[9], det;
+};
+
 // depth / index / normal / score maps (dp_render.hip; spec in
 // include/densepoints.h, dp_render_maps)
 struct RenderSlot { // one requested view
@@ -290,8 +303,7 @@ hipError_t launch_render_resolve(const RenderArgs &a, int max_pixels, hipStream_
 
 // depth-map fusion (dp_fuse.hip; spec in include/densepoints.h, dp_fuse_maps)
 struct FuseView { // one requested view; indexed wave-uniformly (scalar loads)
-    double P[12];
-    double A[9], det;     // adjugate and determinant of the left 3x3 of P
+    ViewInv inv;
     const float *depth;   // W x H
     const float *normal;  // W x H x 3, or null
     const uint32_t *img;  // BGRA8 plane of the current level
@@ -323,8 +335,7 @@ constexpr int kMaprefMaxSources = 8;
 constexpr int kMaprefCounters = 6; // depth pixels in, candidates, source scores, kept, filled, moved
 constexpr int kMaprefStripes = 64; // each counter kept kMaprefStripes times (summed by the host)
 struct MaprefView { // one requested view; indexed wave-uniformly (scalar loads)
-    double P[12];
-    double A[9], det;       // adjugate and determinant of the left 3x3 of P
+    ViewInv inv;
     double C[3], xr[3];     // camera centre, unit x-axis
     const float *depth;     // inputs: W x H, W x H x 3
     const float *normal;

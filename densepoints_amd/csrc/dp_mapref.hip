@@ -25,6 +25,7 @@
 // offsets) are read from global memory: eight pixels per lane, against
 // thousands of gathers.
 #include "dp_fast.h"
+#include "dp_mapdev.h"
 
 #include <algorithm>
 #include <cmath>
@@ -32,23 +33,6 @@
 
 namespace dpk {
 namespace {
-
-__device__ __forceinline__ bool is_depth(float z) { return z > 0.0f && z <= 3.402823466e+38f; }
-
-__device__ __forceinline__ double row_of(const double *P, int r, const double *X)
-{
-    return ((P[4 * r] * X[0] + P[4 * r + 1] * X[1]) + P[4 * r + 2] * X[2]) + P[4 * r + 3];
-}
-
-// backproject_d: the point of pixel (x, y) at the fp64 depth zd
-__device__ __forceinline__ void backproject_d(const MaprefView &v, double x, double y, double zd, double *X)
-{
-    const double b0 = zd * x - v.P[3];
-    const double b1 = zd * y - v.P[7];
-    const double b2 = zd - v.P[11];
-    for (int j = 0; j < 3; ++j)
-        X[j] = ((v.A[3 * j] * b0 + v.A[3 * j + 1] * b1) + v.A[3 * j + 2] * b2) / v.det;
-}
 
 // the input pixel (px, py) of view r: true iff it is inside the image and has
 // a plane (z a depth, dot(n, n) > 0)
@@ -75,21 +59,13 @@ __device__ __forceinline__ uint32_t load_pair(const uint16_t *p)
     return v;
 }
 
-// one add per wave and counter, spread over kMaprefStripes copies
-__device__ __forceinline__ void wave_count(const MaprefArgs &a, int counter, unsigned long long v, uint32_t stripe)
-{
-    for (int o = 32; o > 0; o >>= 1)
-        v += __shfl_xor(v, o);
-    if ((threadIdx.x & 63) == 0 && v)
-        atomicAdd(&a.count[(stripe & (kMaprefStripes - 1)) * kMaprefCounters + counter], v);
-}
-
 template <int WIN> __global__ __launch_bounds__(256) void mapref_kernel(MaprefArgs a)
 {
     constexpr int HW = (WIN - 1) / 2, TS = 16 + 2 * HW, N = WIN * WIN;
     __shared__ uint16_t tile[TS * TS];
     const int k = blockIdx.y;
     const MaprefView &r = a.tab[k];
+    const double *rP = r.inv.P;
     const int tiles_x = (r.W + 15) >> 4;
     if ((int)blockIdx.x >= tiles_x * ((r.H + 15) >> 4))
         return;
@@ -140,13 +116,13 @@ template <int WIN> __global__ __launch_bounds__(256) void mapref_kernel(MaprefAr
         const double xd = (double)x, yd = (double)y;
         double Xo[3] = {0.0, 0.0, 0.0}, ray[3] = {0.0, 0.0, 0.0}, dx = 0.0, len = 0.0;
         if (vmask & 1u) {
-            backproject_d(r, xd, yd, (double)z, Xo);
+            backproject(r.inv, xd, yd, (double)z, Xo);
             if (a.sweep > 0) {
-                const double d0 = row_of(r.P, 2, Xo);
-                const double cu = row_of(r.P, 0, Xo) / d0, cv = row_of(r.P, 1, Xo) / d0;
+                const double d0 = row_of(rP, 2, Xo);
+                const double cu = row_of(rP, 0, Xo) / d0, cv = row_of(rP, 1, Xo) / d0;
                 const double Xq[3] = {Xo[0] + r.xr[0], Xo[1] + r.xr[1], Xo[2] + r.xr[2]};
-                const double d1 = row_of(r.P, 2, Xq);
-                const double du = row_of(r.P, 0, Xq) / d1 - cu, dv = row_of(r.P, 1, Xq) / d1 - cv;
+                const double d1 = row_of(rP, 2, Xq);
+                const double du = row_of(rP, 0, Xq) / d1 - cu, dv = row_of(rP, 1, Xq) / d1 - cv;
                 dx = sqrt(du * du + dv * dv);
                 for (int j = 0; j < 3; ++j)
                     ray[j] = Xo[j] - r.C[j];
@@ -174,7 +150,7 @@ template <int WIN> __global__ __launch_bounds__(256) void mapref_kernel(MaprefAr
                 float zz = 0.0f;
                 if (live) {
                     load_plane(r, px, py, zz, cn);
-                    backproject_d(r, (double)px, (double)py, (double)zz, X0);
+                    backproject(r.inv, (double)px, (double)py, (double)zz, X0);
                 }
             }
             if (!__any(live))
@@ -183,9 +159,9 @@ template <int WIN> __global__ __launch_bounds__(256) void mapref_kernel(MaprefAr
             const double nd[3] = {(double)cn[0], (double)cn[1], (double)cn[2]};
             double m[3];
             for (int j = 0; j < 3; ++j)
-                m[j] = (r.A[j] * nd[0] + r.A[3 + j] * nd[1]) + r.A[6 + j] * nd[2];
-            const double p4[3] = {r.P[3], r.P[7], r.P[11]};
-            const double c = r.det * dpg::dot3(nd, X0) + dpg::dot3(m, p4);
+                m[j] = (r.inv.A[j] * nd[0] + r.inv.A[3 + j] * nd[1]) + r.inv.A[6 + j] * nd[2];
+            const double p4[3] = {rP[3], rP[7], rP[11]};
+            const double c = r.inv.det * dpg::dot3(nd, X0) + dpg::dot3(m, p4);
             const double zc = c / ((m[0] * xd + m[1] * yd) + m[2]);
             const float zf = (float)zc;
             live = live && is_depth(zf);
@@ -194,9 +170,9 @@ template <int WIN> __global__ __launch_bounds__(256) void mapref_kernel(MaprefAr
             const double zi = c / ((m[0] * (xd + 1.0) + m[1] * yd) + m[2]);
             const double zj = c / ((m[0] * xd + m[1] * (yd + 1.0)) + m[2]);
             double Xc[3], Xi[3], Xj[3];
-            backproject_d(r, xd, yd, zc, Xc);
-            backproject_d(r, xd + 1.0, yd, zi, Xi);
-            backproject_d(r, xd, yd + 1.0, zj, Xj);
+            backproject(r.inv, xd, yd, zc, Xc);
+            backproject(r.inv, xd + 1.0, yd, zi, Xi);
+            backproject(r.inv, xd, yd + 1.0, zj, Xj);
 
             // the valid sources' scores, sorted descending in fixed registers
             double top[kMaprefMaxSources];
@@ -209,12 +185,12 @@ template <int WIN> __global__ __launch_bounds__(256) void mapref_kernel(MaprefAr
                 float U0 = 0.0f, V0 = 0.0f, Ui = 0.0f, Vi = 0.0f, Uj = 0.0f, Vj = 0.0f;
                 bool ok = live;
                 if (ok) {
-                    const double dc = row_of(s.P, 2, Xc), di = row_of(s.P, 2, Xi), dj = row_of(s.P, 2, Xj);
+                    const double dc = row_of(s.inv.P, 2, Xc), di = row_of(s.inv.P, 2, Xi), dj = row_of(s.inv.P, 2, Xj);
                     ok = dc > 0.0 && di > 0.0 && dj > 0.0;
                     if (ok) {
-                        const double uc = row_of(s.P, 0, Xc) / dc, vc = row_of(s.P, 1, Xc) / dc;
-                        const double ui = row_of(s.P, 0, Xi) / di, vi = row_of(s.P, 1, Xi) / di;
-                        const double uj = row_of(s.P, 0, Xj) / dj, vj = row_of(s.P, 1, Xj) / dj;
+                        const double uc = row_of(s.inv.P, 0, Xc) / dc, vc = row_of(s.inv.P, 1, Xc) / dc;
+                        const double ui = row_of(s.inv.P, 0, Xi) / di, vi = row_of(s.inv.P, 1, Xi) / di;
+                        const double uj = row_of(s.inv.P, 0, Xj) / dj, vj = row_of(s.inv.P, 1, Xj) / dj;
                         U0 = (float)(32.0 * uc);
                         V0 = (float)(32.0 * vc);
                         Ui = (float)(32.0 * (ui - uc));
@@ -331,12 +307,12 @@ template <int WIN> __global__ __launch_bounds__(256) void mapref_kernel(MaprefAr
             r.ochoice[at] = oc;
     }
     const uint32_t stripe = blockIdx.x * 4u + (threadIdx.x >> 6);
-    wave_count(a, 0, own_depth ? 1ull : 0ull, stripe);
-    wave_count(a, 1, (unsigned long long)ncand, stripe);
-    wave_count(a, 2, (unsigned long long)nscored, stripe);
-    wave_count(a, 3, kept ? 1ull : 0ull, stripe);
-    wave_count(a, 4, kept && !own_depth ? 1ull : 0ull, stripe);
-    wave_count(a, 5, kept && choice != 0 ? 1ull : 0ull, stripe);
+    wave_count<kMaprefStripes, kMaprefCounters>(a.count, 0, own_depth ? 1ull : 0ull, stripe);
+    wave_count<kMaprefStripes, kMaprefCounters>(a.count, 1, (unsigned long long)ncand, stripe);
+    wave_count<kMaprefStripes, kMaprefCounters>(a.count, 2, (unsigned long long)nscored, stripe);
+    wave_count<kMaprefStripes, kMaprefCounters>(a.count, 3, kept ? 1ull : 0ull, stripe);
+    wave_count<kMaprefStripes, kMaprefCounters>(a.count, 4, kept && !own_depth ? 1ull : 0ull, stripe);
+    wave_count<kMaprefStripes, kMaprefCounters>(a.count, 5, kept && choice != 0 ? 1ull : 0ull, stripe);
 }
 
 } // namespace
@@ -400,17 +376,12 @@ static int mapref_check(dp_ctx *c, const int32_t *views, int n_views, const dp_m
         return fail(c, DP_E_ARG, "dp_refine_maps: min_ncc must be in -1..1");
     if (o.flags & ~DP_MAPREF_KEEP_UNSCORED)
         return fail(c, DP_E_ARG, "dp_refine_maps: unknown flag bits");
-    if (c->V <= 0)
-        return fail(c, DP_E_STATE, "dp_refine_maps: no views set");
-    if (!views || n_views < 1 || n_views > c->V || n_views > 64)
-        return fail(c, DP_E_ARG, "dp_refine_maps: n_views must be in 1..min(V, 64)");
-    uint64_t seen[2] = {0, 0};
-    for (int k = 0; k < n_views; ++k) {
-        const int32_t v = views[k];
-        if (v < 0 || v >= c->V || ((seen[v >> 6] >> (v & 63)) & 1ull))
-            return fail(c, DP_E_ARG, "dp_refine_maps: view ids must be unique and < V");
-        seen[v >> 6] |= 1ull << (v & 63);
-    }
+    const int rc = check_view_list(c, "dp_refine_maps", views, n_views, 64);
+    if (rc != DP_OK)
+        return rc;
+    uint64_t seen[2] = {0, 0}; // the requested views, for the sources' rows
+    for (int k = 0; k < n_views; ++k)
+        seen[views[k] >> 6] |= 1ull << (views[k] & 63);
     if (sources)
         for (int k = 0; k < n_views; ++k) {
             uint64_t row[2] = {0, 0};
@@ -467,21 +438,7 @@ extern "C" int dp_refine_maps_device(dp_ctx *c, const int32_t *views, int n_view
     for (int k = 0; k < n_views; ++k) {
         dpk::MaprefView &t = tab[(size_t)k];
         const dpg::ViewDev &v = c->hv[views[k]];
-        const double *P = v.P;
-        const double h[9] = {P[0], P[1], P[2], P[4], P[5], P[6], P[8], P[9], P[10]};
-        for (int j = 0; j < 12; ++j)
-            t.P[j] = P[j];
-        t.A[0] = h[4] * h[8] - h[5] * h[7];
-        t.A[1] = h[2] * h[7] - h[1] * h[8];
-        t.A[2] = h[1] * h[5] - h[2] * h[4];
-        t.A[3] = h[5] * h[6] - h[3] * h[8];
-        t.A[4] = h[0] * h[8] - h[2] * h[6];
-        t.A[5] = h[2] * h[3] - h[0] * h[5];
-        t.A[6] = h[3] * h[7] - h[4] * h[6];
-        t.A[7] = h[1] * h[6] - h[0] * h[7];
-        t.A[8] = h[0] * h[4] - h[1] * h[3];
-        t.det = (h[0] * t.A[0] + h[1] * t.A[3]) + h[2] * t.A[6];
-        if (t.det == 0.0 || !std::isfinite(t.det))
+        if (!view_inverse(v, t.inv))
             return fail(c, DP_E_ARG, "dp_refine_maps: a requested view's left 3x3 is singular");
         for (int j = 0; j < 3; ++j) {
             t.C[j] = v.C[j];
@@ -532,15 +489,12 @@ extern "C" int dp_refine_maps_device(dp_ctx *c, const int32_t *views, int n_view
     }
     hipSetDevice(c->device);
     hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    const size_t ncount = (size_t)dpk::kMaprefStripes * dpk::kMaprefCounters;
-    DP_HIP(c, c->m_e0.create());
-    DP_HIP(c, c->m_e1.create());
-    DP_HIP(c, c->m_tab.reserve((size_t)n_views));
-    DP_HIP(c, c->m_count.reserve(ncount));
-    DP_HIP(c, c->m_hcount.resize(ncount));
+    StripedCounters &n = c->mapref.count;
+    DP_HIP(c, c->mapref.tab.reserve((size_t)n_views));
+    DP_HIP(c, n.reserve(dpk::kMaprefStripes, dpk::kMaprefCounters));
 
     dpk::MaprefArgs a{};
-    a.tab = c->m_tab.p;
+    a.tab = c->mapref.tab.p;
     a.K = n_views;
     a.window = o.window;
     a.sweep = o.sweep;
@@ -556,33 +510,26 @@ extern "C" int dp_refine_maps_device(dp_ctx *c, const int32_t *views, int n_view
         const double N = (double)(o.window * o.window);
         a.dmin = ((c->opt.ncc_denom_min * 256.0) * N) * N;
     }
-    a.count = c->m_count.p;
+    a.count = n.dev.p;
 
     // the table is a small pageable copy: staged before the call returns
-    DP_HIP(c, hipMemcpyAsync(c->m_tab.p, tab.data(), sizeof(dpk::MaprefView) * tab.size(), hipMemcpyHostToDevice, s));
-    DP_HIP(c, hipMemsetAsync(c->m_count.p, 0, sizeof(unsigned long long) * ncount, s));
-    DP_HIP(c, hipEventRecord(c->m_e0, s));
+    DP_HIP(c, hipMemcpyAsync(c->mapref.tab.p, tab.data(), sizeof(dpk::MaprefView) * tab.size(), hipMemcpyHostToDevice, s));
+    DP_HIP(c, n.zero(s));
+    DP_HIP(c, c->mapref.time.begin(s));
     DP_HIP(c, dpk::launch_mapref(a, (unsigned)max_tiles, s));
-    DP_HIP(c, hipEventRecord(c->m_e1, s));
+    DP_HIP(c, c->mapref.time.end(s));
     if (!stats)
         return DP_OK;
     // the one wait: the counters
-    unsigned long long *h = c->m_hcount.data();
-    DP_HIP(c, hipMemcpyAsync(h, c->m_count.p, sizeof(unsigned long long) * ncount, hipMemcpyDeviceToHost, s));
+    DP_HIP(c, n.read(s));
     DP_HIP(c, hipStreamSynchronize(s));
-    int64_t sum[dpk::kMaprefCounters] = {0, 0, 0, 0, 0, 0};
-    for (int st = 0; st < dpk::kMaprefStripes; ++st)
-        for (int k = 0; k < dpk::kMaprefCounters; ++k)
-            sum[k] += (int64_t)h[st * dpk::kMaprefCounters + k];
-    float ms = 0.0f;
-    DP_HIP(c, hipEventElapsedTime(&ms, c->m_e0, c->m_e1));
-    stats->depth_pixels_in = sum[0];
-    stats->candidates = sum[1];
-    stats->source_scores = sum[2];
-    stats->kept = sum[3];
-    stats->filled = sum[4];
-    stats->moved = sum[5];
-    stats->refine_ms = (double)ms;
+    stats->depth_pixels_in = n.sum(0);
+    stats->candidates = n.sum(1);
+    stats->source_scores = n.sum(2);
+    stats->kept = n.sum(3);
+    stats->filled = n.sum(4);
+    stats->moved = n.sum(5);
+    DP_HIP(c, c->mapref.time.ms(stats->refine_ms));
     return DP_OK;
 }
 
@@ -605,24 +552,21 @@ extern "C" int dp_refine_maps(dp_ctx *c, const int32_t *views, int n_views, cons
     // choice out
     const size_t words[6] = {1, 3, 1, 3, 1, 1};
     std::vector<size_t> off((size_t)n_views * 6);
-    size_t total = 0;
+    PlanePacker pack;
     for (int k = 0; k < n_views; ++k) {
-        const size_t px = (size_t)c->hv[views[k]].W * (size_t)c->hv[views[k]].H;
+        const size_t px = view_pixels(c, views[k]);
         const bool want[6] = {true, true, depth_out && depth_out[k], normal_out && normal_out[k],
                               score_out && score_out[k], choice_out && choice_out[k]};
-        for (int j = 0; j < 6; ++j) {
-            off[(size_t)k * 6 + j] = total;
-            if (want[j])
-                total += (4 * words[j] * px + 255) & ~(size_t)255;
-        }
+        for (int j = 0; j < 6; ++j)
+            off[(size_t)k * 6 + j] = want[j] ? pack.add(4 * words[j] * px) : 0;
     }
-    DP_HIP(c, c->m_io.reserve(total ? total : 1));
+    DP_HIP(c, c->mapref.io.reserve(pack.total ? pack.total : 1));
     std::vector<const float *> dd((size_t)n_views), dn((size_t)n_views);
     std::vector<float *> od((size_t)n_views), on((size_t)n_views), os((size_t)n_views);
     std::vector<int32_t *> oc((size_t)n_views);
     for (int k = 0; k < n_views; ++k) {
-        const size_t px = (size_t)c->hv[views[k]].W * (size_t)c->hv[views[k]].H;
-        unsigned char *b = c->m_io.p;
+        const size_t px = view_pixels(c, views[k]);
+        unsigned char *b = c->mapref.io.p;
         const size_t *f = &off[(size_t)k * 6];
         dd[(size_t)k] = (const float *)(b + f[0]);
         dn[(size_t)k] = (const float *)(b + f[1]);
@@ -638,7 +582,7 @@ extern "C" int dp_refine_maps(dp_ctx *c, const int32_t *views, int n_views, cons
     if (rc != DP_OK)
         return rc;
     for (int k = 0; k < n_views; ++k) {
-        const size_t px = (size_t)c->hv[views[k]].W * (size_t)c->hv[views[k]].H;
+        const size_t px = view_pixels(c, views[k]);
         if (od[(size_t)k])
             DP_HIP(c, hipMemcpyAsync(depth_out[k], od[(size_t)k], 4 * px, hipMemcpyDeviceToHost, s));
         if (on[(size_t)k])

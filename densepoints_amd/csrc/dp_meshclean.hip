@@ -32,6 +32,7 @@
 // used as an address: an invalid triangle reaches neither parent[] nor the
 // vertex array.
 #include "dp_ctx.h"
+#include "dp_mapdev.h"
 #include "dp_wave.h"
 
 #include <hipcub/hipcub.hpp>
@@ -123,14 +124,10 @@ __device__ __forceinline__ void unite(int32_t *parent, int32_t a, int32_t b)
     }
 }
 
-// one add per wave and counter, spread over kCleanStripes copies (every lane calls)
-__device__ __forceinline__ void wave_count(unsigned long long *count, int counter, unsigned long long v)
+// counter += the wave's sum of v, on the wave's stripe (every lane calls)
+__device__ __forceinline__ void clean_count(const CleanArgs &a, int counter, unsigned long long v)
 {
-    for (int o = 32; o > 0; o >>= 1)
-        v += __shfl_xor(v, o);
-    const uint32_t stripe = blockIdx.x * (kCleanBlock / 64) + (threadIdx.x >> 6);
-    if ((threadIdx.x & 63) == 0 && v)
-        atomicAdd(&count[(stripe & (kCleanStripes - 1)) * kCleanCounters + counter], v);
+    wave_count<kCleanStripes, kCleanCounters>(a.count, counter, v, blockIdx.x * (kCleanBlock / 64) + (threadIdx.x >> 6));
 }
 
 // cnt[key] += 1 for every lane with `on`, as one add per distinct key of the
@@ -150,39 +147,6 @@ __device__ __forceinline__ void wave_add_by_key(int32_t *cnt, int32_t key, bool 
             }
         }
     }
-}
-
-// the sum of v over the block, in every thread (every thread calls)
-__device__ __forceinline__ uint32_t block_sum(uint32_t v, uint32_t *wsum)
-{
-    for (int o = 32; o > 0; o >>= 1)
-        v += __shfl_xor(v, o);
-    if ((threadIdx.x & 63) == 0)
-        wsum[threadIdx.x >> 6] = v;
-    __syncthreads();
-    uint32_t t = 0;
-    for (int w = 0; w < kCleanBlock / 64; ++w)
-        t += wsum[w];
-    return t;
-}
-
-// the sum of v over the block's threads below this one (every thread calls)
-__device__ __forceinline__ uint32_t block_exclusive(uint32_t v, uint32_t *wsum)
-{
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    uint32_t x = v;
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t y = __shfl_up(x, o);
-        if (lane >= o)
-            x += y;
-    }
-    if (lane == 63)
-        wsum[wv] = x;
-    __syncthreads();
-    uint32_t base = 0;
-    for (int w = 0; w < wv; ++w)
-        base += wsum[w];
-    return base + x - v;
 }
 
 // the triangle's indices; false (and nothing else read) unless all three are vertices
@@ -221,7 +185,7 @@ __global__ __launch_bounds__(kCleanBlock) void clean_union_kernel(CleanArgs a)
         unite(a.parent, v[0], v[1]);
         unite(a.parent, v[0], v[2]);
     }
-    wave_count(a.count, 0, t < a.nt && !valid ? 1ull : 0ull);
+    clean_count(a, 0, t < a.nt && !valid ? 1ull : 0ull);
 }
 
 __global__ __launch_bounds__(kCleanBlock) void clean_flatten_kernel(CleanArgs a)
@@ -237,10 +201,10 @@ __global__ __launch_bounds__(kCleanBlock) void clean_flatten_kernel(CleanArgs a)
         root = used && r == (int32_t)v;
     }
     wave_add_by_key(a.vcnt, r, used);
-    const uint32_t total = block_sum(root ? 1u : 0u, wsum);
+    const uint32_t total = block_sum<kCleanBlock>(root ? 1u : 0u, wsum);
     if (threadIdx.x == 0)
         a.bcount[seg_roots(a) + blockIdx.x] = total;
-    wave_count(a.count, 1, used ? 1ull : 0ull);
+    clean_count(a, 1, used ? 1ull : 0ull);
 }
 
 __global__ __launch_bounds__(kCleanBlock) void clean_tricount_kernel(CleanArgs a)
@@ -287,7 +251,7 @@ __global__ __launch_bounds__(kCleanBlock) void clean_select_kernel(CleanArgs a)
         if (c < a.ccap)
             a.comps[c].rank = (int32_t)r;
     }
-    wave_count(a.count, 2, kept ? 1ull : 0ull);
+    clean_count(a, 2, kept ? 1ull : 0ull);
 }
 
 __global__ __launch_bounds__(kCleanBlock) void clean_vlabel_kernel(CleanArgs a)
@@ -314,7 +278,7 @@ __device__ __forceinline__ bool vertex_kept(const CleanArgs &a, int64_t v)
 __global__ __launch_bounds__(kCleanBlock) void clean_vcount_kernel(CleanArgs a)
 {
     __shared__ uint32_t wsum[kCleanBlock / 64];
-    const uint32_t total = block_sum(vertex_kept(a, item_of()) ? 1u : 0u, wsum);
+    const uint32_t total = block_sum<kCleanBlock>(vertex_kept(a, item_of()) ? 1u : 0u, wsum);
     if (threadIdx.x == 0)
         a.bcount[seg_verts(a) + blockIdx.x] = total;
 }
@@ -324,7 +288,7 @@ __global__ __launch_bounds__(kCleanBlock) void clean_tcount_kernel(CleanArgs a)
     __shared__ uint32_t wsum[kCleanBlock / 64];
     int32_t v[3];
     const bool keep = load_triangle(a, item_of(), v) && a.keptc[a.cnum[a.parent[v[0]]]] != 0;
-    const uint32_t total = block_sum(keep ? 1u : 0u, wsum);
+    const uint32_t total = block_sum<kCleanBlock>(keep ? 1u : 0u, wsum);
     if (threadIdx.x == 0)
         a.bcount[seg_tris(a) + blockIdx.x] = total;
 }
@@ -400,8 +364,6 @@ using dpk::CleanArgs;
 using dpk::kCleanCounters;
 using dpk::kCleanStripes;
 
-constexpr size_t kCleanHost = (size_t)kCleanStripes * kCleanCounters + 4; // the counters, then C, VO, TO, Tmax
-
 struct CleanRun {
     CleanArgs a{};
     size_t tmp_bytes = 0;
@@ -463,35 +425,32 @@ int clean_prepare(dp_ctx *c, const int32_t *d_tris, int64_t nt, const dp_mesh_ve
     a.min_fraction = o.min_fraction;
     a.max_components = o.max_components;
     const size_t n = (size_t)std::max<int64_t>(nv, 1), nb = (size_t)(2 * (a.nbv + 1) + a.nbt + 1);
-    for (dpk::Event &e : c->c_e)
-        DP_HIP(c, e.create());
-    DP_HIP(c, c->c_parent.reserve(n));
-    DP_HIP(c, c->c_tcnt.reserve(n));
-    DP_HIP(c, c->c_vcnt.reserve(n));
-    DP_HIP(c, c->c_cnum.reserve(n));
-    DP_HIP(c, c->c_vmap.reserve(n));
-    DP_HIP(c, c->c_tmax.reserve(1));
-    DP_HIP(c, c->c_used.reserve(n));
-    DP_HIP(c, c->c_keptc.reserve(n));
-    DP_HIP(c, c->c_keys.reserve(n));
-    DP_HIP(c, c->c_keys_sorted.reserve(n));
-    DP_HIP(c, c->c_bcount.reserve(nb));
-    DP_HIP(c, c->c_boff.reserve(nb));
-    DP_HIP(c, c->c_count.reserve((size_t)kCleanStripes * kCleanCounters));
-    DP_HIP(c, c->c_hcount.resize(kCleanHost));
-    a.parent = c->c_parent.p;
-    a.tcnt = c->c_tcnt.p;
-    a.vcnt = c->c_vcnt.p;
-    a.cnum = c->c_cnum.p;
-    a.vmap = c->c_vmap.p;
-    a.tmax = c->c_tmax.p;
-    a.used = c->c_used.p;
-    a.keptc = c->c_keptc.p;
-    a.keys = c->c_keys.p;
-    a.keys_sorted = c->c_keys_sorted.p;
-    a.bcount = c->c_bcount.p;
-    a.boff = c->c_boff.p;
-    a.count = c->c_count.p;
+    DP_HIP(c, c->clean.parent.reserve(n));
+    DP_HIP(c, c->clean.tcnt.reserve(n));
+    DP_HIP(c, c->clean.vcnt.reserve(n));
+    DP_HIP(c, c->clean.cnum.reserve(n));
+    DP_HIP(c, c->clean.vmap.reserve(n));
+    DP_HIP(c, c->clean.tmax.reserve(1));
+    DP_HIP(c, c->clean.used.reserve(n));
+    DP_HIP(c, c->clean.keptc.reserve(n));
+    DP_HIP(c, c->clean.keys.reserve(n));
+    DP_HIP(c, c->clean.keys_sorted.reserve(n));
+    DP_HIP(c, c->clean.bcount.reserve(nb));
+    DP_HIP(c, c->clean.boff.reserve(nb));
+    DP_HIP(c, c->clean.count.reserve(kCleanStripes, kCleanCounters, 4)); // + C, VO, TO, Tmax
+    a.parent = c->clean.parent.p;
+    a.tcnt = c->clean.tcnt.p;
+    a.vcnt = c->clean.vcnt.p;
+    a.cnum = c->clean.cnum.p;
+    a.vmap = c->clean.vmap.p;
+    a.tmax = c->clean.tmax.p;
+    a.used = c->clean.used.p;
+    a.keptc = c->clean.keptc.p;
+    a.keys = c->clean.keys.p;
+    a.keys_sorted = c->clean.keys_sorted.p;
+    a.bcount = c->clean.bcount.p;
+    a.boff = c->clean.boff.p;
+    a.count = c->clean.count.dev.p;
     size_t b = 0;
     const int nscan = (int)std::max(a.nbv, a.nbt) + 1;
     DP_HIP(c, hipcub::DeviceScan::ExclusiveSum(nullptr, b, a.bcount, a.boff, nscan, s));
@@ -511,7 +470,7 @@ int clean_label(dp_ctx *c, CleanRun &run, hipStream_t s)
 {
     const CleanArgs &a = run.a;
     size_t b = run.tmp_bytes;
-    DP_HIP(c, hipMemsetAsync(a.count, 0, sizeof(unsigned long long) * kCleanStripes * kCleanCounters, s));
+    DP_HIP(c, c->clean.count.zero(s));
     DP_HIP(c, hipMemsetAsync(a.tmax, 0, sizeof(int32_t), s));
     DP_HIP(c, hipMemsetAsync(a.bcount + a.nbv, 0, sizeof(unsigned long long), s));
     DP_HIP(c, dpk::launch_over(dpk::clean_init_kernel, a.nbv, a, s));
@@ -572,56 +531,52 @@ int clean_emit(dp_ctx *c, CleanRun &run, hipStream_t s)
     return DP_OK;
 }
 
-// the counters, C, Tmax and (with `kept`) the kept totals into c_hcount; waits
+// the counters and, behind them, C, (with `kept`) the kept totals and Tmax; waits
 int clean_read(dp_ctx *c, const CleanRun &run, bool kept, hipStream_t s)
 {
     const CleanArgs &a = run.a;
-    const size_t nc = (size_t)kCleanStripes * kCleanCounters;
-    unsigned long long *h = c->c_hcount.data();
-    h[nc + 1] = h[nc + 2] = h[nc + 3] = 0;
-    DP_HIP(c, hipMemcpyAsync(h, a.count, sizeof(unsigned long long) * nc, hipMemcpyDeviceToHost, s));
-    DP_HIP(c, hipMemcpyAsync(h + nc, a.boff + a.nbv, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    unsigned long long *h = c->clean.count.extra();
+    h[1] = h[2] = h[3] = 0;
+    DP_HIP(c, c->clean.count.read(s));
+    DP_HIP(c, hipMemcpyAsync(h, a.boff + a.nbv, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
     if (kept) {
-        DP_HIP(c, hipMemcpyAsync(h + nc + 1, a.boff + (a.nbv + 1) + a.nbv, sizeof(unsigned long long),
+        DP_HIP(c, hipMemcpyAsync(h + 1, a.boff + (a.nbv + 1) + a.nbv, sizeof(unsigned long long),
                                  hipMemcpyDeviceToHost, s));
-        DP_HIP(c, hipMemcpyAsync(h + nc + 2, a.boff + 2 * (a.nbv + 1) + a.nbt, sizeof(unsigned long long),
+        DP_HIP(c, hipMemcpyAsync(h + 2, a.boff + 2 * (a.nbv + 1) + a.nbt, sizeof(unsigned long long),
                                  hipMemcpyDeviceToHost, s));
     }
-    DP_HIP(c, hipMemcpyAsync(h + nc + 3, a.tmax, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    DP_HIP(c, hipMemcpyAsync(h + 3, a.tmax, sizeof(int32_t), hipMemcpyDeviceToHost, s));
     DP_HIP(c, hipStreamSynchronize(s));
     return DP_OK;
 }
 
-// c_hcount as statistics; without `kept` (dp_mesh_components) nothing was selected
+// what clean_read read as statistics; without `kept` (dp_mesh_components) nothing was selected
 dp_mesh_clean_stats clean_stats(dp_ctx *c, const CleanRun &run, bool kept, double ms)
 {
-    const unsigned long long *h = c->c_hcount.data();
-    const size_t nc = (size_t)kCleanStripes * kCleanCounters;
-    int64_t sum[kCleanCounters] = {0, 0, 0};
-    for (int st = 0; st < kCleanStripes; ++st)
-        for (int k = 0; k < kCleanCounters; ++k)
-            sum[k] += (int64_t)h[st * kCleanCounters + k];
+    const unsigned long long *h = c->clean.count.extra();
+    const int64_t sum[kCleanCounters] = {c->clean.count.sum(0), c->clean.count.sum(1), c->clean.count.sum(2)};
     dp_mesh_clean_stats r{};
     r.vertices_in = run.a.nv;
     r.triangles_in = run.a.nt;
     r.invalid_triangles = sum[0];
     r.unused_vertices = run.a.nv - sum[1];
-    r.components = (int64_t)h[nc];
-    r.largest_triangles = (int64_t)(int32_t)(uint32_t)h[nc + 3];
+    r.components = (int64_t)h[0];
+    r.largest_triangles = (int64_t)(int32_t)(uint32_t)h[3];
     r.components_kept = kept ? sum[2] : r.components;
-    r.vertices_out = kept ? (int64_t)h[nc + 1] : sum[1];
-    r.triangles_out = kept ? (int64_t)h[nc + 2] : run.a.nt - sum[0];
+    r.vertices_out = kept ? (int64_t)h[1] : sum[1];
+    r.triangles_out = kept ? (int64_t)h[2] : run.a.nt - sum[0];
     r.clean_ms = ms;
     return r;
 }
 
-int clean_elapsed(dp_ctx *c, int first, int pairs, double &ms)
+// the time of the first `sections` timed sections
+int clean_elapsed(dp_ctx *c, int sections, double &ms)
 {
     ms = 0.0;
-    for (int k = 0; k < pairs; ++k) {
-        float t = 0.0f;
-        DP_HIP(c, hipEventElapsedTime(&t, c->c_e[first + 2 * k], c->c_e[first + 2 * k + 1]));
-        ms += (double)t;
+    for (int k = 0; k < sections; ++k) {
+        double t = 0.0;
+        DP_HIP(c, c->clean.time[k].ms(t));
+        ms += t;
     }
     return DP_OK;
 }
@@ -656,16 +611,16 @@ extern "C" int dp_mesh_components_device(dp_ctx *c, const int32_t *d_triangles, 
     run.a.ccap = component_cap;
     run.a.vcomp = d_vertex_component;
     run.a.tcomp = d_triangle_component;
-    DP_HIP(c, hipEventRecord(c->c_e[0], s));
+    DP_HIP(c, c->clean.time[0].begin(s));
     if ((rc = clean_label(c, run, s)) != DP_OK || (rc = clean_select(c, run, s)) != DP_OK ||
         (rc = clean_labels_out(c, run, s)) != DP_OK)
         return rc;
-    DP_HIP(c, hipEventRecord(c->c_e[1], s));
+    DP_HIP(c, c->clean.time[0].end(s));
     // the one wait: the counts and statistics
     if ((rc = clean_read(c, run, false, s)) != DP_OK)
         return rc;
     double ms = 0.0;
-    if ((rc = clean_elapsed(c, 0, 1, ms)) != DP_OK)
+    if ((rc = clean_elapsed(c, 1, ms)) != DP_OK)
         return rc;
     const dp_mesh_clean_stats st = clean_stats(c, run, false, ms);
     *n_components = st.components;
@@ -692,36 +647,36 @@ extern "C" int dp_mesh_components(dp_ctx *c, const int32_t *triangles, int64_t n
     hipSetDevice(c->device);
     hipStream_t s = c->stream;
     const int64_t nt = n_triangles, nv = n_vertices;
-    DP_HIP(c, c->c_in.reserve((size_t)std::max<int64_t>(12 * nt, 1)));
-    DP_HIP(c, c->c_maps.reserve((size_t)std::max<int64_t>(nv + nt, 1)));
+    DP_HIP(c, c->clean.in.reserve((size_t)std::max<int64_t>(12 * nt, 1)));
+    DP_HIP(c, c->clean.maps.reserve((size_t)std::max<int64_t>(nv + nt, 1)));
     if (nt > 0)
-        DP_HIP(c, hipMemcpyAsync(c->c_in.p, triangles, 12 * (size_t)nt, hipMemcpyHostToDevice, s));
+        DP_HIP(c, hipMemcpyAsync(c->clean.in.p, triangles, 12 * (size_t)nt, hipMemcpyHostToDevice, s));
     dp_mesh_clean_options o;
     dp_default_mesh_clean_options(&o);
     CleanRun run;
-    if ((rc = clean_prepare(c, (const int32_t *)c->c_in.p, nt, nullptr, nv, o, s, run)) != DP_OK)
+    if ((rc = clean_prepare(c, (const int32_t *)c->clean.in.p, nt, nullptr, nv, o, s, run)) != DP_OK)
         return rc;
-    DP_HIP(c, hipEventRecord(c->c_e[0], s));
+    DP_HIP(c, c->clean.time[0].begin(s));
     if ((rc = clean_label(c, run, s)) != DP_OK)
         return rc;
-    DP_HIP(c, hipEventRecord(c->c_e[1], s));
+    DP_HIP(c, c->clean.time[0].end(s));
     // the number of components sizes the table and the sort
     if ((rc = clean_read(c, run, false, s)) != DP_OK)
         return rc;
-    const int64_t C = (int64_t)c->c_hcount.data()[(size_t)kCleanStripes * kCleanCounters];
-    DP_HIP(c, c->c_comps.reserve((size_t)std::max<int64_t>(C, 1)));
-    DP_HIP(c, c->c_hcomps.resize((size_t)std::max<int64_t>(C, 1)));
-    run.a.comps = c->c_comps.p;
+    const int64_t C = (int64_t)c->clean.count.extra()[0];
+    DP_HIP(c, c->clean.comps.reserve((size_t)std::max<int64_t>(C, 1)));
+    DP_HIP(c, c->clean.hcomps.resize((size_t)std::max<int64_t>(C, 1)));
+    run.a.comps = c->clean.comps.p;
     run.a.ccap = C;
     run.a.nsort = C;
-    run.a.vcomp = vertex_component ? c->c_maps.p : nullptr;
-    run.a.tcomp = triangle_component ? c->c_maps.p + nv : nullptr;
-    DP_HIP(c, hipEventRecord(c->c_e[2], s));
+    run.a.vcomp = vertex_component ? c->clean.maps.p : nullptr;
+    run.a.tcomp = triangle_component ? c->clean.maps.p + nv : nullptr;
+    DP_HIP(c, c->clean.time[1].begin(s));
     if ((rc = clean_select(c, run, s)) != DP_OK || (rc = clean_labels_out(c, run, s)) != DP_OK)
         return rc;
-    DP_HIP(c, hipEventRecord(c->c_e[3], s));
+    DP_HIP(c, c->clean.time[1].end(s));
     if (C > 0)
-        DP_HIP(c, hipMemcpyAsync(c->c_hcomps.data(), c->c_comps.p, sizeof(dp_mesh_component) * (size_t)C,
+        DP_HIP(c, hipMemcpyAsync(c->clean.hcomps.data(), c->clean.comps.p, sizeof(dp_mesh_component) * (size_t)C,
                                  hipMemcpyDeviceToHost, s));
     if (vertex_component && nv > 0)
         DP_HIP(c, hipMemcpyAsync(vertex_component, run.a.vcomp, 4 * (size_t)nv, hipMemcpyDeviceToHost, s));
@@ -729,10 +684,10 @@ extern "C" int dp_mesh_components(dp_ctx *c, const int32_t *triangles, int64_t n
         DP_HIP(c, hipMemcpyAsync(triangle_component, run.a.tcomp, 4 * (size_t)nt, hipMemcpyDeviceToHost, s));
     DP_HIP(c, hipStreamSynchronize(s));
     double ms = 0.0;
-    if ((rc = clean_elapsed(c, 0, 2, ms)) != DP_OK)
+    if ((rc = clean_elapsed(c, 2, ms)) != DP_OK)
         return rc;
     const dp_mesh_clean_stats st = clean_stats(c, run, false, ms);
-    *components = C > 0 ? c->c_hcomps.data() : nullptr;
+    *components = C > 0 ? c->clean.hcomps.data() : nullptr;
     *n_components = C;
     if (stats)
         *stats = st;
@@ -780,16 +735,16 @@ extern "C" int dp_mesh_clean_device(dp_ctx *c, const dp_mesh_clean_options *mco,
     run.a.tcap = triangle_cap;
     run.a.vmap_out = d_vertex_map;
     run.a.tmap_out = d_triangle_map;
-    DP_HIP(c, hipEventRecord(c->c_e[0], s));
+    DP_HIP(c, c->clean.time[0].begin(s));
     if ((rc = clean_label(c, run, s)) != DP_OK || (rc = clean_select(c, run, s)) != DP_OK ||
         (rc = clean_count_kept(c, run, s)) != DP_OK || (rc = clean_emit(c, run, s)) != DP_OK)
         return rc;
-    DP_HIP(c, hipEventRecord(c->c_e[1], s));
+    DP_HIP(c, c->clean.time[0].end(s));
     // the one wait: the counts and statistics
     if ((rc = clean_read(c, run, true, s)) != DP_OK)
         return rc;
     double ms = 0.0;
-    if ((rc = clean_elapsed(c, 0, 1, ms)) != DP_OK)
+    if ((rc = clean_elapsed(c, 1, ms)) != DP_OK)
         return rc;
     const dp_mesh_clean_stats st = clean_stats(c, run, true, ms);
     *n_vertices_out = st.vertices_out;
@@ -828,63 +783,63 @@ extern "C" int dp_mesh_clean(dp_ctx *c, const dp_mesh_clean_options *mco, const 
     const int64_t nt = n_triangles, nv = n_vertices;
     // staged inputs: the vertices (16 B each), then the triangles
     const size_t vbytes = sizeof(dp_mesh_vertex) * (size_t)nv;
-    DP_HIP(c, c->c_in.reserve(std::max<size_t>(vbytes + 12 * (size_t)nt, 1)));
-    DP_HIP(c, c->c_maps.reserve((size_t)std::max<int64_t>(nv + nt, 1)));
+    DP_HIP(c, c->clean.in.reserve(std::max<size_t>(vbytes + 12 * (size_t)nt, 1)));
+    DP_HIP(c, c->clean.maps.reserve((size_t)std::max<int64_t>(nv + nt, 1)));
     if (nv > 0)
-        DP_HIP(c, hipMemcpyAsync(c->c_in.p, vertices, vbytes, hipMemcpyHostToDevice, s));
+        DP_HIP(c, hipMemcpyAsync(c->clean.in.p, vertices, vbytes, hipMemcpyHostToDevice, s));
     if (nt > 0)
-        DP_HIP(c, hipMemcpyAsync(c->c_in.p + vbytes, triangles, 12 * (size_t)nt, hipMemcpyHostToDevice, s));
+        DP_HIP(c, hipMemcpyAsync(c->clean.in.p + vbytes, triangles, 12 * (size_t)nt, hipMemcpyHostToDevice, s));
     CleanRun run;
-    if ((rc = clean_prepare(c, (const int32_t *)(c->c_in.p + vbytes), nt, (const dp_mesh_vertex *)c->c_in.p, nv, o, s,
-                            run)) != DP_OK)
+    if ((rc = clean_prepare(c, (const int32_t *)(c->clean.in.p + vbytes), nt, (const dp_mesh_vertex *)c->clean.in.p, nv, o,
+                            s, run)) != DP_OK)
         return rc;
-    DP_HIP(c, hipEventRecord(c->c_e[0], s));
+    DP_HIP(c, c->clean.time[0].begin(s));
     if ((rc = clean_label(c, run, s)) != DP_OK)
         return rc;
-    DP_HIP(c, hipEventRecord(c->c_e[1], s));
+    DP_HIP(c, c->clean.time[0].end(s));
     // the number of components sizes the sort
     if ((rc = clean_read(c, run, false, s)) != DP_OK)
         return rc;
-    run.a.nsort = (int64_t)c->c_hcount.data()[(size_t)kCleanStripes * kCleanCounters];
-    DP_HIP(c, hipEventRecord(c->c_e[2], s));
+    run.a.nsort = (int64_t)c->clean.count.extra()[0];
+    DP_HIP(c, c->clean.time[1].begin(s));
     if ((rc = clean_select(c, run, s)) != DP_OK || (rc = clean_count_kept(c, run, s)) != DP_OK)
         return rc;
-    DP_HIP(c, hipEventRecord(c->c_e[3], s));
+    DP_HIP(c, c->clean.time[1].end(s));
     // the kept totals size the results
     if ((rc = clean_read(c, run, true, s)) != DP_OK)
         return rc;
-    const unsigned long long *h = c->c_hcount.data() + (size_t)kCleanStripes * kCleanCounters;
+    const unsigned long long *h = c->clean.count.extra();
     const int64_t vo = (int64_t)h[1], to = (int64_t)h[2];
-    DP_HIP(c, c->c_verts.reserve((size_t)std::max<int64_t>(vo, 1)));
-    DP_HIP(c, c->c_tris.reserve((size_t)std::max<int64_t>(3 * to, 1)));
-    DP_HIP(c, c->c_hverts.resize((size_t)std::max<int64_t>(vo, 1)));
-    DP_HIP(c, c->c_htris.resize((size_t)std::max<int64_t>(3 * to, 1)));
-    run.a.vout = c->c_verts.p;
+    DP_HIP(c, c->clean.verts.reserve((size_t)std::max<int64_t>(vo, 1)));
+    DP_HIP(c, c->clean.tris.reserve((size_t)std::max<int64_t>(3 * to, 1)));
+    DP_HIP(c, c->clean.hverts.resize((size_t)std::max<int64_t>(vo, 1)));
+    DP_HIP(c, c->clean.htris.resize((size_t)std::max<int64_t>(3 * to, 1)));
+    run.a.vout = c->clean.verts.p;
     run.a.vcap = vo;
-    run.a.tout = c->c_tris.p;
+    run.a.tout = c->clean.tris.p;
     run.a.tcap = to;
-    run.a.vmap_out = vertex_map ? c->c_maps.p : nullptr;
-    run.a.tmap_out = triangle_map ? c->c_maps.p + nv : nullptr;
-    DP_HIP(c, hipEventRecord(c->c_e[4], s));
+    run.a.vmap_out = vertex_map ? c->clean.maps.p : nullptr;
+    run.a.tmap_out = triangle_map ? c->clean.maps.p + nv : nullptr;
+    DP_HIP(c, c->clean.time[2].begin(s));
     if ((rc = clean_emit(c, run, s)) != DP_OK)
         return rc;
-    DP_HIP(c, hipEventRecord(c->c_e[5], s));
+    DP_HIP(c, c->clean.time[2].end(s));
     if (vo > 0)
-        DP_HIP(c, hipMemcpyAsync(c->c_hverts.data(), c->c_verts.p, sizeof(dp_mesh_vertex) * (size_t)vo,
+        DP_HIP(c, hipMemcpyAsync(c->clean.hverts.data(), c->clean.verts.p, sizeof(dp_mesh_vertex) * (size_t)vo,
                                  hipMemcpyDeviceToHost, s));
     if (to > 0)
-        DP_HIP(c, hipMemcpyAsync(c->c_htris.data(), c->c_tris.p, 12 * (size_t)to, hipMemcpyDeviceToHost, s));
+        DP_HIP(c, hipMemcpyAsync(c->clean.htris.data(), c->clean.tris.p, 12 * (size_t)to, hipMemcpyDeviceToHost, s));
     if (vertex_map && nv > 0)
         DP_HIP(c, hipMemcpyAsync(vertex_map, run.a.vmap_out, 4 * (size_t)nv, hipMemcpyDeviceToHost, s));
     if (triangle_map && nt > 0)
         DP_HIP(c, hipMemcpyAsync(triangle_map, run.a.tmap_out, 4 * (size_t)nt, hipMemcpyDeviceToHost, s));
     DP_HIP(c, hipStreamSynchronize(s));
     double ms = 0.0;
-    if ((rc = clean_elapsed(c, 0, 3, ms)) != DP_OK)
+    if ((rc = clean_elapsed(c, 3, ms)) != DP_OK)
         return rc;
     const dp_mesh_clean_stats st = clean_stats(c, run, true, ms);
-    *vertices_out = vo > 0 ? c->c_hverts.data() : nullptr;
-    *triangles_out = to > 0 ? c->c_htris.data() : nullptr;
+    *vertices_out = vo > 0 ? c->clean.hverts.data() : nullptr;
+    *triangles_out = to > 0 ? c->clean.htris.data() : nullptr;
     *n_vertices_out = vo;
     *n_triangles_out = to;
     if (stats)

@@ -17,23 +17,13 @@
 // The result is a per-pixel minimum of values that depend on one (patch, view,
 // pixel) alone: independent of the pair order and of the launch geometry.
 #include "dp_ctx.h"
+#include "dp_mapdev.h"
 
 #include <cmath>
 #include <cstdlib>
 
 namespace dpk {
 namespace {
-
-__device__ __forceinline__ uint32_t lanes_below(uint64_t m)
-{
-    const uint32_t lo = __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u);
-    return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), lo);
-}
-
-__device__ __forceinline__ double row_of(const double *P, int r, double x, double y, double z)
-{
-    return ((P[4 * r] * x + P[4 * r + 1] * y) + P[4 * r + 2] * z) + P[4 * r + 3];
-}
 
 __device__ __forceinline__ bool finite3(const float *f) { return isfinite(f[0]) && isfinite(f[1]) && isfinite(f[2]); }
 
@@ -46,7 +36,7 @@ __device__ bool make_pair(const dpg::ViewDev &v, const double *X, const double *
         if (!(dpg::dot3(n, d) > 0.0))
             return false;
     }
-    const double d0 = row_of(v.P, 2, X[0], X[1], X[2]);
+    const double d0 = row_of(v.P, 2, X);
     if (!(d0 > 0.0))
         return false;
     const double t = dpg::dot3(v.xr, n);
@@ -79,18 +69,9 @@ __device__ bool make_pair(const dpg::ViewDev &v, const double *X, const double *
         const double *Pr = v.P + 4 * r;
         h[3 * r] = (Pr[0] * e1[0] + Pr[1] * e1[1]) + Pr[2] * e1[2];
         h[3 * r + 1] = (Pr[0] * e2[0] + Pr[1] * e2[1]) + Pr[2] * e2[2];
-        h[3 * r + 2] = row_of(v.P, r, X[0], X[1], X[2]);
+        h[3 * r + 2] = row_of(v.P, r, X);
     }
-    pr.A[0] = h[4] * h[8] - h[5] * h[7];
-    pr.A[1] = h[2] * h[7] - h[1] * h[8];
-    pr.A[2] = h[1] * h[5] - h[2] * h[4];
-    pr.A[3] = h[5] * h[6] - h[3] * h[8];
-    pr.A[4] = h[0] * h[8] - h[2] * h[6];
-    pr.A[5] = h[2] * h[3] - h[0] * h[5];
-    pr.A[6] = h[3] * h[7] - h[4] * h[6];
-    pr.A[7] = h[1] * h[6] - h[0] * h[7];
-    pr.A[8] = h[0] * h[4] - h[1] * h[3];
-    pr.D = (h[0] * pr.A[0] + h[1] * pr.A[3]) + h[2] * pr.A[6];
+    pr.D = dpg::adjugate3(h, pr.A);
     pr.s = s;
     pr.RR = R * R;
     return true;
@@ -300,18 +281,7 @@ static int render_check(dp_ctx *c, int64_t n, const void *patches, const int32_t
         return fail(c, DP_E_ARG, "dp_render_maps: splat_scale must be > 0");
     if (o.max_radius_px < 1 || o.max_radius_px > 255)
         return fail(c, DP_E_ARG, "dp_render_maps: max_radius_px must be in 1..255");
-    if (c->V <= 0)
-        return fail(c, DP_E_STATE, "dp_render_maps: no views set");
-    if (!views || n_views < 1 || n_views > c->V)
-        return fail(c, DP_E_ARG, "dp_render_maps: n_views must be in 1..V");
-    uint64_t seen[2] = {0, 0};
-    for (int k = 0; k < n_views; ++k) {
-        const int32_t v = views[k];
-        if (v < 0 || v >= c->V || ((seen[v >> 6] >> (v & 63)) & 1ull))
-            return fail(c, DP_E_ARG, "dp_render_maps: view ids must be unique and < V");
-        seen[v >> 6] |= 1ull << (v & 63);
-    }
-    return DP_OK;
+    return check_view_list(c, "dp_render_maps", views, n_views, DP_MAX_VIEWS);
 }
 
 extern "C" int dp_render_maps_device(dp_ctx *c, const dp_patch *d_patches, int64_t n, const uint8_t *d_keep,
@@ -328,8 +298,6 @@ extern "C" int dp_render_maps_device(dp_ctx *c, const dp_patch *d_patches, int64
         return rc;
     hipSetDevice(c->device);
     hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    DP_HIP(c, c->r_e0.create());
-    DP_HIP(c, c->r_e1.create());
 
     // slot tables and the z-buffer layout
     std::vector<dpk::RenderSlot> slots((size_t)n_views);
@@ -366,11 +334,11 @@ extern "C" int dp_render_maps_device(dp_ctx *c, const dp_patch *d_patches, int64
     const int64_t chunks = n > 0 ? (n + per_chunk - 1) / per_chunk : 0;
     const size_t ncount = (size_t)dpk::kRenderCounters + (size_t)chunks;
 
-    DP_HIP(c, c->r_z.reserve((size_t)zwords));
-    DP_HIP(c, c->r_pairs.reserve((size_t)pair_cap));
-    DP_HIP(c, c->r_count.reserve(ncount));
-    DP_HIP(c, c->r_slots.reserve((size_t)n_views));
-    DP_HIP(c, c->r_slot_of.reserve((size_t)DP_MAX_VIEWS));
+    DP_HIP(c, c->pix64.reserve((size_t)zwords));
+    DP_HIP(c, c->render.pairs.reserve((size_t)pair_cap));
+    DP_HIP(c, c->render.count.reserve(ncount));
+    DP_HIP(c, c->render.slots.reserve((size_t)n_views));
+    DP_HIP(c, c->render.slot_of.reserve((size_t)DP_MAX_VIEWS));
     if (n > 0)
         DP_HIP(c, c->f_rho.reserve((size_t)n));
 
@@ -381,24 +349,24 @@ extern "C" int dp_render_maps_device(dp_ctx *c, const dp_patch *d_patches, int64
     a.keep = d_keep;
     a.rho = c->f_rho.p;
     a.n = n;
-    a.slots = c->r_slots.p;
-    a.slot_of = c->r_slot_of.p;
+    a.slots = c->render.slots.p;
+    a.slot_of = c->render.slot_of.p;
     a.splat_scale = (double)o.splat_scale;
     a.max_radius = (double)o.max_radius_px;
     a.all_facing = (o.flags & DP_RENDER_ALL_FACING) ? 1 : 0;
-    a.pairs = c->r_pairs.p;
+    a.pairs = c->render.pairs.p;
     a.pair_cap = pair_cap;
-    a.zbuf = c->r_z.p;
-    a.count = c->r_count.p;
+    a.zbuf = c->pix64.p;
+    a.count = c->render.count.p;
 
     // the tables are small pageable copies: staged before the call returns
-    DP_HIP(c, hipMemcpyAsync(c->r_slots.p, slots.data(), sizeof(dpk::RenderSlot) * slots.size(),
+    DP_HIP(c, hipMemcpyAsync(c->render.slots.p, slots.data(), sizeof(dpk::RenderSlot) * slots.size(),
                              hipMemcpyHostToDevice, s));
-    DP_HIP(c, hipMemcpyAsync(c->r_slot_of.p, slot_of.data(), sizeof(int32_t) * slot_of.size(),
+    DP_HIP(c, hipMemcpyAsync(c->render.slot_of.p, slot_of.data(), sizeof(int32_t) * slot_of.size(),
                              hipMemcpyHostToDevice, s));
-    DP_HIP(c, hipEventRecord(c->r_e0, s));
-    DP_HIP(c, hipMemsetAsync(c->r_count.p, 0, sizeof(unsigned long long) * ncount, s));
-    DP_HIP(c, hipMemsetAsync(c->r_z.p, 0xFF, sizeof(unsigned long long) * (size_t)zwords, s));
+    DP_HIP(c, c->render.time.begin(s));
+    DP_HIP(c, hipMemsetAsync(c->render.count.p, 0, sizeof(unsigned long long) * ncount, s));
+    DP_HIP(c, hipMemsetAsync(c->pix64.p, 0xFF, sizeof(unsigned long long) * (size_t)zwords, s));
     if (n > 0) {
         dpk::FilterArgs fa{};
         fa.views = c->d_views;
@@ -415,18 +383,16 @@ extern "C" int dp_render_maps_device(dp_ctx *c, const dp_patch *d_patches, int64
         DP_HIP(c, dpk::launch_render_raster(a, (int)k, s));
     }
     DP_HIP(c, dpk::launch_render_resolve(a, max_pixels, s));
-    DP_HIP(c, hipEventRecord(c->r_e1, s));
+    DP_HIP(c, c->render.time.end(s));
     if (stats) {
         unsigned long long h[dpk::kRenderCounters];
-        DP_HIP(c, hipMemcpyAsync(h, c->r_count.p, sizeof(h), hipMemcpyDeviceToHost, s));
+        DP_HIP(c, hipMemcpyAsync(h, c->render.count.p, sizeof(h), hipMemcpyDeviceToHost, s));
         DP_HIP(c, hipStreamSynchronize(s));
-        float ms = 0.0f;
-        DP_HIP(c, hipEventElapsedTime(&ms, c->r_e0, c->r_e1));
         stats->patches = (int64_t)h[0];
         stats->pairs = (int64_t)h[1];
         stats->pixel_tests = (int64_t)h[2];
         stats->covered_pixels = (int64_t)h[3];
-        stats->render_ms = (double)ms;
+        DP_HIP(c, c->render.time.ms(stats->render_ms));
     }
     return DP_OK;
 }
@@ -451,29 +417,26 @@ extern "C" int dp_render_maps(dp_ctx *c, const dp_patch *patches, int64_t n, con
         size_t off, bytes;
     };
     std::vector<Plane> planes;
-    std::vector<float *> dd(n_views, nullptr), dn(n_views, nullptr), ds(n_views, nullptr);
-    std::vector<int32_t *> di(n_views, nullptr);
-    size_t total = 0;
-    auto want = [&](void *host, size_t bytes) {
-        planes.push_back({host, total, bytes});
-        total += (bytes + 255) & ~(size_t)255;
-        return planes.back().off;
-    };
-    std::vector<size_t> od(n_views), oi(n_views), on(n_views), os(n_views);
+    PlanePacker pack;
     for (int k = 0; k < n_views; ++k) {
-        const size_t px = (size_t)c->hv[views[k]].W * (size_t)c->hv[views[k]].H;
-        od[k] = depth && depth[k] ? want(depth[k], 4 * px) : (size_t)-1;
-        oi[k] = index && index[k] ? want(index[k], 4 * px) : (size_t)-1;
-        on[k] = normal && normal[k] ? want(normal[k], 12 * px) : (size_t)-1;
-        os[k] = score && score[k] ? want(score[k], 4 * px) : (size_t)-1;
+        const size_t px = view_pixels(c, views[k]);
+        void *const host[4] = {depth ? depth[k] : nullptr, index ? index[k] : nullptr, normal ? normal[k] : nullptr,
+                               score ? score[k] : nullptr};
+        for (int j = 0; j < 4; ++j) {
+            const size_t bytes = (j == 2 ? 12 : 4) * px;
+            planes.push_back({host[j], host[j] ? pack.add(bytes) : 0, bytes});
+        }
     }
-    DP_HIP(c, c->r_out.reserve(total ? total : 1));
+    DP_HIP(c, c->render.out.reserve(pack.total ? pack.total : 1));
+    // the device form's plane tables: entry 4 k + j of planes, null where not wanted
+    std::vector<float *> dd(n_views), dn(n_views), ds(n_views);
+    std::vector<int32_t *> di(n_views);
     for (int k = 0; k < n_views; ++k) {
-        unsigned char *b = c->r_out.p;
-        dd[k] = od[k] != (size_t)-1 ? (float *)(b + od[k]) : nullptr;
-        di[k] = oi[k] != (size_t)-1 ? (int32_t *)(b + oi[k]) : nullptr;
-        dn[k] = on[k] != (size_t)-1 ? (float *)(b + on[k]) : nullptr;
-        ds[k] = os[k] != (size_t)-1 ? (float *)(b + os[k]) : nullptr;
+        auto at = [&](int j) { return planes[4 * k + j].host ? c->render.out.p + planes[4 * k + j].off : nullptr; };
+        dd[k] = (float *)at(0);
+        di[k] = (int32_t *)at(1);
+        dn[k] = (float *)at(2);
+        ds[k] = (float *)at(3);
     }
     if (n > 0) {
         DP_HIP(c, c->f_pat.reserve((size_t)n));
@@ -488,7 +451,8 @@ extern "C" int dp_render_maps(dp_ctx *c, const dp_patch *patches, int64_t n, con
     if (rc != DP_OK)
         return rc;
     for (const Plane &p : planes)
-        DP_HIP(c, hipMemcpyAsync(p.host, c->r_out.p + p.off, p.bytes, hipMemcpyDeviceToHost, s));
+        if (p.host)
+            DP_HIP(c, hipMemcpyAsync(p.host, c->render.out.p + p.off, p.bytes, hipMemcpyDeviceToHost, s));
     DP_HIP(c, hipStreamSynchronize(s));
     return DP_OK;
 }

@@ -30,6 +30,7 @@
 // tetrahedron, triangle) order.  Nothing depends on the order in which lanes
 // or blocks run.
 #include "dp_ctx.h"
+#include "dp_mapdev.h"
 
 #include <hipcub/hipcub.hpp>
 
@@ -55,17 +56,6 @@ __device__ const int8_t kTri[16][2][3] = {
     {{2, 5, 4}, {0, 0, 0}}, {{0, 1, 5}, {0, 5, 4}}, {{0, 5, 3}, {0, 2, 5}}, {{1, 5, 3}, {0, 0, 0}},
     {{1, 3, 4}, {1, 4, 2}}, {{0, 3, 4}, {0, 0, 0}}, {{0, 2, 1}, {0, 0, 0}}, {{0, 0, 0}, {0, 0, 0}}};
 
-__device__ __forceinline__ bool is_depth(float z) { return z > 0.0f && z <= 3.402823466e+38f; }
-
-// one add per wave and counter, spread over kTsdfStripes copies
-__device__ __forceinline__ void wave_count(unsigned long long *count, int counter, unsigned long long v, uint32_t stripe)
-{
-    for (int o = 32; o > 0; o >>= 1)
-        v += __shfl_xor(v, o);
-    if ((threadIdx.x & 63) == 0 && v)
-        atomicAdd(&count[(stripe & (kTsdfStripes - 1)) * kTsdfCounters + counter], v);
-}
-
 __global__ __launch_bounds__(64 * kTsdfRows) void tsdf_integrate_kernel(TsdfArgs a)
 {
     const TsdfVolume &g = a.vol;
@@ -82,17 +72,9 @@ __global__ __launch_bounds__(64 * kTsdfRows) void tsdf_integrate_kernel(TsdfArgs
     uint32_t sr = 0, sg = 0, sb = 0; // at most 64 x 255 each
     for (int kv = 0; kv < a.K; ++kv) {
         const TsdfView &s = a.tab[kv];
-        const double d = ((s.P[8] * X[0] + s.P[9] * X[1]) + s.P[10] * X[2]) + s.P[11];
-        if (!in || !(d > 0.0))
-            continue;
-        const double h0 = ((s.P[0] * X[0] + s.P[1] * X[1]) + s.P[2] * X[2]) + s.P[3];
-        const double h1 = ((s.P[4] * X[0] + s.P[5] * X[1]) + s.P[6] * X[2]) + s.P[7];
-        double u, v;
-        dpg::div2(h0, h1, d, u, v);
-        if (!(fabs(u) < 2.0e9) || !(fabs(v) < 2.0e9))
-            continue;
-        const int32_t xi = (int32_t)rint(u), yi = (int32_t)rint(v);
-        if (xi < 0 || xi >= s.W || yi < 0 || yi >= s.H)
+        double d;
+        int32_t xi, yi;
+        if (!in || !nearest_pixel(s.P, s.W, s.H, X, d, xi, yi))
             continue;
         const float z = s.depth[(int64_t)yi * s.W + xi];
         if (!is_depth(z))
@@ -125,10 +107,10 @@ __global__ __launch_bounds__(64 * kTsdfRows) void tsdf_integrate_kernel(TsdfArgs
             a.rgb[at] = rgb;
     }
     const uint32_t stripe = ((blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) * kTsdfRows + threadIdx.y;
-    wave_count(a.count, 0, in ? 1ull : 0ull, stripe);
-    wave_count(a.count, 1, (unsigned long long)w, stripe);
-    wave_count(a.count, 2, w > 0 ? 1ull : 0ull, stripe);
-    wave_count(a.count, 3, w > 0 && fabsf(tsdf) < 1.0f ? 1ull : 0ull, stripe);
+    wave_count<kTsdfStripes, kTsdfCounters>(a.count, 0, in ? 1ull : 0ull, stripe);
+    wave_count<kTsdfStripes, kTsdfCounters>(a.count, 1, (unsigned long long)w, stripe);
+    wave_count<kTsdfStripes, kTsdfCounters>(a.count, 2, w > 0 ? 1ull : 0ull, stripe);
+    wave_count<kTsdfStripes, kTsdfCounters>(a.count, 3, w > 0 && fabsf(tsdf) < 1.0f ? 1ull : 0ull, stripe);
 }
 
 // ---- mesh ---------------------------------------------------------------------
@@ -179,39 +161,6 @@ __device__ __forceinline__ uint32_t tet_mask(uint32_t in8, int t)
            ((in8 >> kTetQ[t][3]) & 1u) << 3;
 }
 
-// the sum of v over the block, in thread 0 (every thread calls)
-__device__ __forceinline__ uint32_t block_sum(uint32_t v, uint32_t *wsum)
-{
-    for (int o = 32; o > 0; o >>= 1)
-        v += __shfl_xor(v, o);
-    if ((threadIdx.x & 63) == 0)
-        wsum[threadIdx.x >> 6] = v;
-    __syncthreads();
-    uint32_t t = 0;
-    for (int w = 0; w < kMeshBlock / 64; ++w)
-        t += wsum[w];
-    return t;
-}
-
-// the sum of v over the block's threads below this one (every thread calls)
-__device__ __forceinline__ uint32_t block_exclusive(uint32_t v, uint32_t *wsum)
-{
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    uint32_t x = v;
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t y = __shfl_up(x, o);
-        if (lane >= o)
-            x += y;
-    }
-    if (lane == 63)
-        wsum[wv] = x;
-    __syncthreads();
-    uint32_t base = 0;
-    for (int w = 0; w < wv; ++w)
-        base += wsum[w];
-    return base + x - v;
-}
-
 __global__ __launch_bounds__(kMeshBlock) void mesh_count_kernel(MeshArgs a)
 {
     __shared__ uint32_t wsum[kMeshBlock / 64];
@@ -248,21 +197,17 @@ __global__ __launch_bounds__(kMeshBlock) void mesh_count_kernel(MeshArgs a)
     }
     if (p.point)
         a.tcount[p.L] = (uint8_t)nt;
-    const uint32_t total = block_sum(nt, wsum);
+    const uint32_t total = block_sum<kMeshBlock>(nt, wsum);
     if (threadIdx.x == 0)
         a.bcount[a.blocks + 1 + blockIdx.x] = total;
-    unsigned long long n = active ? 1ull : 0ull;
-    for (int o = 32; o > 0; o >>= 1)
-        n += __shfl_xor(n, o);
-    if ((threadIdx.x & 63) == 0 && n)
-        atomicAdd(&a.active[(blockIdx.x * (kMeshBlock / 64) + (threadIdx.x >> 6)) & (kTsdfStripes - 1)], n);
+    wave_count<kTsdfStripes, 1>(a.active, 0, active ? 1ull : 0ull, blockIdx.x * (kMeshBlock / 64) + (threadIdx.x >> 6));
 }
 
 __global__ __launch_bounds__(kMeshBlock) void mesh_vcount_kernel(MeshArgs a)
 {
     __shared__ uint32_t wsum[kMeshBlock / 64];
     const Lattice p = lattice_of(a);
-    const uint32_t total = block_sum(p.point ? (uint32_t)__popc(flag_byte(a, p.L)) : 0u, wsum);
+    const uint32_t total = block_sum<kMeshBlock>(p.point ? (uint32_t)__popc(flag_byte(a, p.L)) : 0u, wsum);
     if (threadIdx.x == 0)
         a.bcount[blockIdx.x] = total;
 }
@@ -435,17 +380,9 @@ static int64_t tsdf_points(const dp_tsdf_options &o) { return (int64_t)o.dim[0] 
 // the integration's argument checks (they need no device)
 static int tsdf_check_views(dp_ctx *c, const int32_t *views, int n_views, const float *const *depth)
 {
-    if (c->V <= 0)
-        return fail(c, DP_E_STATE, "dp_tsdf_integrate: no views set");
-    if (!views || n_views < 1 || n_views > c->V || n_views > 64)
-        return fail(c, DP_E_ARG, "dp_tsdf_integrate: n_views must be in 1..min(V, 64)");
-    uint64_t seen[2] = {0, 0};
-    for (int k = 0; k < n_views; ++k) {
-        const int32_t v = views[k];
-        if (v < 0 || v >= c->V || ((seen[v >> 6] >> (v & 63)) & 1ull))
-            return fail(c, DP_E_ARG, "dp_tsdf_integrate: view ids must be unique and < V");
-        seen[v >> 6] |= 1ull << (v & 63);
-    }
+    const int rc = check_view_list(c, "dp_tsdf_integrate", views, n_views, 64);
+    if (rc != DP_OK)
+        return rc;
     if (!depth)
         return fail(c, DP_E_ARG, "dp_tsdf_integrate: depth planes must be given");
     for (int k = 0; k < n_views; ++k)
@@ -483,45 +420,35 @@ extern "C" int dp_tsdf_integrate_device(dp_ctx *c, const int32_t *views, int n_v
     }
     hipSetDevice(c->device);
     hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    const size_t ncount = (size_t)dpk::kTsdfStripes * dpk::kTsdfCounters;
-    DP_HIP(c, c->t_e0.create());
-    DP_HIP(c, c->t_e1.create());
-    DP_HIP(c, c->t_tab.reserve((size_t)n_views));
-    DP_HIP(c, c->t_count.reserve(ncount));
-    DP_HIP(c, c->t_hcount.resize(ncount + 2));
+    StripedCounters &n = c->tsdf.count;
+    DP_HIP(c, c->tsdf.tab.reserve((size_t)n_views));
+    DP_HIP(c, n.reserve(dpk::kTsdfStripes, dpk::kTsdfCounters));
 
     dpk::TsdfArgs a{};
-    a.tab = c->t_tab.p;
+    a.tab = c->tsdf.tab.p;
     a.K = n_views;
     a.vol = tsdf_volume(*opts);
     a.trunc = (double)opts->trunc;
     a.tsdf = d_tsdf;
     a.weight = d_weight;
     a.rgb = d_rgb;
-    a.count = c->t_count.p;
+    a.count = n.dev.p;
 
     // the table is a small pageable copy: staged before the call returns
-    DP_HIP(c, hipMemcpyAsync(c->t_tab.p, tab.data(), sizeof(dpk::TsdfView) * tab.size(), hipMemcpyHostToDevice, s));
-    DP_HIP(c, hipMemsetAsync(c->t_count.p, 0, sizeof(unsigned long long) * ncount, s));
-    DP_HIP(c, hipEventRecord(c->t_e0, s));
+    DP_HIP(c, hipMemcpyAsync(c->tsdf.tab.p, tab.data(), sizeof(dpk::TsdfView) * tab.size(), hipMemcpyHostToDevice, s));
+    DP_HIP(c, n.zero(s));
+    DP_HIP(c, c->tsdf.time[0].begin(s));
     DP_HIP(c, dpk::launch_tsdf_integrate(a, s));
-    DP_HIP(c, hipEventRecord(c->t_e1, s));
+    DP_HIP(c, c->tsdf.time[0].end(s));
     if (!stats)
         return DP_OK;
-    unsigned long long *h = c->t_hcount.data();
-    DP_HIP(c, hipMemcpyAsync(h, c->t_count.p, sizeof(unsigned long long) * ncount, hipMemcpyDeviceToHost, s));
+    DP_HIP(c, n.read(s));
     DP_HIP(c, hipStreamSynchronize(s));
-    int64_t sum[dpk::kTsdfCounters] = {0, 0, 0, 0};
-    for (int st = 0; st < dpk::kTsdfStripes; ++st)
-        for (int k = 0; k < dpk::kTsdfCounters; ++k)
-            sum[k] += (int64_t)h[st * dpk::kTsdfCounters + k];
-    float ms = 0.0f;
-    DP_HIP(c, hipEventElapsedTime(&ms, c->t_e0, c->t_e1));
-    stats->voxels = sum[0];
-    stats->observations = sum[1];
-    stats->observed_voxels = sum[2];
-    stats->near_voxels = sum[3];
-    stats->integrate_ms = (double)ms;
+    stats->voxels = n.sum(0);
+    stats->observations = n.sum(1);
+    stats->observed_voxels = n.sum(2);
+    stats->near_voxels = n.sum(3);
+    DP_HIP(c, c->tsdf.time[0].ms(stats->integrate_ms));
     return DP_OK;
 }
 
@@ -540,21 +467,19 @@ extern "C" int dp_tsdf_integrate(dp_ctx *c, const int32_t *views, int n_views, c
     // device copies of the planes, 256-B aligned, in one buffer; the three
     // output volumes in another
     std::vector<size_t> od((size_t)n_views);
-    size_t total = 0;
-    for (int k = 0; k < n_views; ++k) {
-        od[(size_t)k] = total;
-        total += (4 * (size_t)c->hv[views[k]].W * (size_t)c->hv[views[k]].H + 255) & ~(size_t)255;
-    }
+    PlanePacker pack;
+    for (int k = 0; k < n_views; ++k)
+        od[(size_t)k] = pack.add(4 * view_pixels(c, views[k]));
     const size_t vol = 4 * (size_t)tsdf_points(*opts);
-    DP_HIP(c, c->t_in.reserve(total ? total : 1));
-    DP_HIP(c, c->t_vol.reserve(3 * vol));
+    DP_HIP(c, c->tsdf.in.reserve(pack.total ? pack.total : 1));
+    DP_HIP(c, c->tsdf.vol.reserve(3 * vol));
     std::vector<const float *> dd((size_t)n_views);
     for (int k = 0; k < n_views; ++k) {
-        const size_t px = (size_t)c->hv[views[k]].W * (size_t)c->hv[views[k]].H;
-        dd[(size_t)k] = (const float *)(c->t_in.p + od[(size_t)k]);
-        DP_HIP(c, hipMemcpyAsync(c->t_in.p + od[(size_t)k], depth[k], 4 * px, hipMemcpyHostToDevice, s));
+        dd[(size_t)k] = (const float *)(c->tsdf.in.p + od[(size_t)k]);
+        DP_HIP(c, hipMemcpyAsync(c->tsdf.in.p + od[(size_t)k], depth[k], 4 * view_pixels(c, views[k]),
+                                 hipMemcpyHostToDevice, s));
     }
-    unsigned char *o = c->t_vol.p;
+    unsigned char *o = c->tsdf.vol.p;
     rc = dp_tsdf_integrate_device(c, views, n_views, opts, dd.data(), tsdf ? (float *)o : nullptr,
                                   weight ? (int32_t *)(o + vol) : nullptr, rgb ? (uint32_t *)(o + 2 * vol) : nullptr,
                                   stats, s);
@@ -589,59 +514,54 @@ int mesh_prepare(dp_ctx *c, const dp_tsdf_options &o, const float *d_tsdf, const
     a.points = tsdf_points(o);
     a.blocks = (a.points + dpk::kMeshBlock - 1) / dpk::kMeshBlock;
     const size_t words = (size_t)(a.points / 4 + 1), nb = (size_t)a.blocks + 1;
-    DP_HIP(c, c->t_e0.create());
-    DP_HIP(c, c->t_e1.create());
-    DP_HIP(c, c->t_e2.create());
-    DP_HIP(c, c->t_e3.create());
-    DP_HIP(c, c->t_flags.reserve(words));
-    DP_HIP(c, c->t_tcount.reserve((size_t)a.points));
-    DP_HIP(c, c->t_vbase.reserve((size_t)a.points));
-    DP_HIP(c, c->t_bcount.reserve(2 * nb));
-    DP_HIP(c, c->t_boff.reserve(2 * nb));
-    DP_HIP(c, c->t_count.reserve((size_t)dpk::kTsdfStripes * dpk::kTsdfCounters));
-    DP_HIP(c, c->t_hcount.resize((size_t)dpk::kTsdfStripes * dpk::kTsdfCounters + 2));
-    DP_HIP(c, hipcub::DeviceScan::ExclusiveSum(nullptr, run.scan_bytes, c->t_bcount.p, c->t_boff.p, (int)nb, s));
+    DP_HIP(c, c->tsdf.flags.reserve(words));
+    DP_HIP(c, c->tsdf.tcount.reserve((size_t)a.points));
+    DP_HIP(c, c->tsdf.vbase.reserve((size_t)a.points));
+    DP_HIP(c, c->tsdf.bcount.reserve(2 * nb));
+    DP_HIP(c, c->tsdf.boff.reserve(2 * nb));
+    DP_HIP(c, c->tsdf.count.reserve(dpk::kTsdfStripes, 1, 2));
+    DP_HIP(c, hipcub::DeviceScan::ExclusiveSum(nullptr, run.scan_bytes, c->tsdf.bcount.p, c->tsdf.boff.p, (int)nb, s));
     DP_HIP(c, c->scan_tmp.reserve(run.scan_bytes ? run.scan_bytes : 1));
     a.tsdf = d_tsdf;
     a.weight = d_weight;
     a.rgb = d_rgb;
-    a.flags = c->t_flags.p;
-    a.tcount = c->t_tcount.p;
-    a.vbase = c->t_vbase.p;
-    a.bcount = c->t_bcount.p;
-    a.boff = c->t_boff.p;
-    a.active = c->t_count.p;
+    a.flags = c->tsdf.flags.p;
+    a.tcount = c->tsdf.tcount.p;
+    a.vbase = c->tsdf.vbase.p;
+    a.bcount = c->tsdf.bcount.p;
+    a.boff = c->tsdf.boff.p;
+    a.active = c->tsdf.count.dev.p;
     return DP_OK;
 }
 
-// phase 1, and the copy of the totals into t_hcount: [stripes] the active cells'
-// stripes, then the vertex and the triangle total
+// phase 1
 int mesh_count(dp_ctx *c, MeshRun &run, hipStream_t s)
 {
     const dpk::MeshArgs &a = run.a;
     const size_t nb = (size_t)a.blocks + 1;
-    DP_HIP(c, hipMemsetAsync(c->t_flags.p, 0, sizeof(uint32_t) * (size_t)(a.points / 4 + 1), s));
-    DP_HIP(c, hipMemsetAsync(c->t_count.p, 0, sizeof(unsigned long long) * dpk::kTsdfStripes, s));
-    DP_HIP(c, hipMemsetAsync(c->t_bcount.p + a.blocks, 0, sizeof(unsigned long long), s));
-    DP_HIP(c, hipMemsetAsync(c->t_bcount.p + nb + a.blocks, 0, sizeof(unsigned long long), s));
+    DP_HIP(c, hipMemsetAsync(c->tsdf.flags.p, 0, sizeof(uint32_t) * (size_t)(a.points / 4 + 1), s));
+    DP_HIP(c, c->tsdf.count.zero(s));
+    DP_HIP(c, hipMemsetAsync(c->tsdf.bcount.p + a.blocks, 0, sizeof(unsigned long long), s));
+    DP_HIP(c, hipMemsetAsync(c->tsdf.bcount.p + nb + a.blocks, 0, sizeof(unsigned long long), s));
     DP_HIP(c, dpk::launch_mesh_count(a, s));
     DP_HIP(c, dpk::launch_mesh_vcount(a, s));
-    DP_HIP(c, hipcub::DeviceScan::ExclusiveSum(c->scan_tmp.p, run.scan_bytes, c->t_bcount.p, c->t_boff.p, (int)nb, s));
-    DP_HIP(c, hipcub::DeviceScan::ExclusiveSum(c->scan_tmp.p, run.scan_bytes, c->t_bcount.p + nb, c->t_boff.p + nb,
+    DP_HIP(c, hipcub::DeviceScan::ExclusiveSum(c->scan_tmp.p, run.scan_bytes, c->tsdf.bcount.p, c->tsdf.boff.p, (int)nb,
+                                               s));
+    DP_HIP(c, hipcub::DeviceScan::ExclusiveSum(c->scan_tmp.p, run.scan_bytes, c->tsdf.bcount.p + nb, c->tsdf.boff.p + nb,
                                                (int)nb, s));
     return DP_OK;
 }
 
+// the active cells' stripes and, behind them, the vertex and the triangle total; waits
 int mesh_read_totals(dp_ctx *c, const MeshRun &run, hipStream_t s)
 {
     const dpk::MeshArgs &a = run.a;
     const size_t nb = (size_t)a.blocks + 1;
-    unsigned long long *h = c->t_hcount.data();
-    DP_HIP(c, hipMemcpyAsync(h, c->t_count.p, sizeof(unsigned long long) * dpk::kTsdfStripes, hipMemcpyDeviceToHost, s));
-    DP_HIP(c, hipMemcpyAsync(h + dpk::kTsdfStripes, c->t_boff.p + a.blocks, sizeof(unsigned long long),
-                             hipMemcpyDeviceToHost, s));
-    DP_HIP(c, hipMemcpyAsync(h + dpk::kTsdfStripes + 1, c->t_boff.p + nb + a.blocks, sizeof(unsigned long long),
-                             hipMemcpyDeviceToHost, s));
+    unsigned long long *h = c->tsdf.count.extra();
+    DP_HIP(c, c->tsdf.count.read(s));
+    DP_HIP(c, hipMemcpyAsync(h, c->tsdf.boff.p + a.blocks, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    DP_HIP(c, hipMemcpyAsync(h + 1, c->tsdf.boff.p + nb + a.blocks, sizeof(unsigned long long), hipMemcpyDeviceToHost,
+                             s));
     DP_HIP(c, hipStreamSynchronize(s));
     return DP_OK;
 }
@@ -659,17 +579,13 @@ int mesh_emit(dp_ctx *c, MeshRun &run, dp_mesh_vertex *d_vertices, int64_t vcap,
     return DP_OK;
 }
 
-// the totals of t_hcount into the caller's counts and statistics
+// the totals read into the caller's counts and statistics
 int mesh_finish(dp_ctx *c, double ms, int64_t *n_vertices, int64_t *n_triangles, dp_mesh_stats *stats)
 {
-    const unsigned long long *h = c->t_hcount.data();
-    int64_t active = 0;
-    for (int st = 0; st < dpk::kTsdfStripes; ++st)
-        active += (int64_t)h[st];
-    *n_vertices = (int64_t)h[dpk::kTsdfStripes];
-    *n_triangles = (int64_t)h[dpk::kTsdfStripes + 1];
+    *n_vertices = (int64_t)c->tsdf.count.extra()[0];
+    *n_triangles = (int64_t)c->tsdf.count.extra()[1];
     if (stats) {
-        stats->active_cells = active;
+        stats->active_cells = c->tsdf.count.sum(0);
         stats->vertices = *n_vertices;
         stats->triangles = *n_triangles;
         stats->mesh_ms = ms;
@@ -709,18 +625,18 @@ extern "C" int dp_tsdf_mesh_device(dp_ctx *c, const dp_tsdf_options *opts, const
     MeshRun run;
     if ((rc = mesh_prepare(c, *opts, d_tsdf, d_weight, d_rgb, s, run)) != DP_OK)
         return rc;
-    DP_HIP(c, hipEventRecord(c->t_e0, s));
+    DP_HIP(c, c->tsdf.time[0].begin(s));
     if ((rc = mesh_count(c, run, s)) != DP_OK)
         return rc;
     if ((rc = mesh_emit(c, run, d_vertices, vertex_cap, d_triangles, triangle_cap, s)) != DP_OK)
         return rc;
-    DP_HIP(c, hipEventRecord(c->t_e1, s));
+    DP_HIP(c, c->tsdf.time[0].end(s));
     // the one wait: the totals
     if ((rc = mesh_read_totals(c, run, s)) != DP_OK)
         return rc;
-    float ms = 0.0f;
-    DP_HIP(c, hipEventElapsedTime(&ms, c->t_e0, c->t_e1));
-    return mesh_finish(c, (double)ms, n_vertices, n_triangles, stats);
+    double ms = 0.0;
+    DP_HIP(c, c->tsdf.time[0].ms(ms));
+    return mesh_finish(c, ms, n_vertices, n_triangles, stats);
 }
 
 extern "C" int dp_tsdf_mesh(dp_ctx *c, const dp_tsdf_options *opts, const float *tsdf, const int32_t *weight,
@@ -735,8 +651,8 @@ extern "C" int dp_tsdf_mesh(dp_ctx *c, const dp_tsdf_options *opts, const float 
     hipSetDevice(c->device);
     hipStream_t s = c->stream;
     const size_t vol = 4 * (size_t)tsdf_points(*opts);
-    DP_HIP(c, c->t_in.reserve(3 * vol));
-    unsigned char *in = c->t_in.p;
+    DP_HIP(c, c->tsdf.in.reserve(3 * vol));
+    unsigned char *in = c->tsdf.in.p;
     DP_HIP(c, hipMemcpyAsync(in, tsdf, vol, hipMemcpyHostToDevice, s));
     DP_HIP(c, hipMemcpyAsync(in + vol, weight, vol, hipMemcpyHostToDevice, s));
     if (rgb)
@@ -745,34 +661,34 @@ extern "C" int dp_tsdf_mesh(dp_ctx *c, const dp_tsdf_options *opts, const float 
     if ((rc = mesh_prepare(c, *opts, (const float *)in, (const int32_t *)(in + vol),
                            rgb ? (const uint32_t *)(in + 2 * vol) : nullptr, s, run)) != DP_OK)
         return rc;
-    DP_HIP(c, hipEventRecord(c->t_e0, s));
+    DP_HIP(c, c->tsdf.time[0].begin(s));
     if ((rc = mesh_count(c, run, s)) != DP_OK)
         return rc;
-    DP_HIP(c, hipEventRecord(c->t_e1, s));
+    DP_HIP(c, c->tsdf.time[0].end(s));
     if ((rc = mesh_read_totals(c, run, s)) != DP_OK)
         return rc;
-    float ms0 = 0.0f, ms1 = 0.0f;
-    DP_HIP(c, hipEventElapsedTime(&ms0, c->t_e0, c->t_e1));
+    double ms0 = 0.0, ms1 = 0.0;
+    DP_HIP(c, c->tsdf.time[0].ms(ms0));
     int64_t nv = 0, nt = 0;
     if ((rc = mesh_finish(c, 0.0, &nv, &nt, nullptr)) != DP_OK)
         return rc;
-    DP_HIP(c, c->t_verts.reserve((size_t)std::max<int64_t>(nv, 1)));
-    DP_HIP(c, c->t_tris.reserve((size_t)std::max<int64_t>(3 * nt, 1)));
-    DP_HIP(c, c->t_hverts.resize((size_t)std::max<int64_t>(nv, 1)));
-    DP_HIP(c, c->t_htris.resize((size_t)std::max<int64_t>(3 * nt, 1)));
-    DP_HIP(c, hipEventRecord(c->t_e2, s));
-    if ((rc = mesh_emit(c, run, c->t_verts.p, nv, c->t_tris.p, nt, s)) != DP_OK)
+    DP_HIP(c, c->tsdf.verts.reserve((size_t)std::max<int64_t>(nv, 1)));
+    DP_HIP(c, c->tsdf.tris.reserve((size_t)std::max<int64_t>(3 * nt, 1)));
+    DP_HIP(c, c->tsdf.hverts.resize((size_t)std::max<int64_t>(nv, 1)));
+    DP_HIP(c, c->tsdf.htris.resize((size_t)std::max<int64_t>(3 * nt, 1)));
+    DP_HIP(c, c->tsdf.time[1].begin(s));
+    if ((rc = mesh_emit(c, run, c->tsdf.verts.p, nv, c->tsdf.tris.p, nt, s)) != DP_OK)
         return rc;
-    DP_HIP(c, hipEventRecord(c->t_e3, s));
+    DP_HIP(c, c->tsdf.time[1].end(s));
     if (nv > 0)
-        DP_HIP(c, hipMemcpyAsync(c->t_hverts.data(), c->t_verts.p, sizeof(dp_mesh_vertex) * (size_t)nv,
+        DP_HIP(c, hipMemcpyAsync(c->tsdf.hverts.data(), c->tsdf.verts.p, sizeof(dp_mesh_vertex) * (size_t)nv,
                                  hipMemcpyDeviceToHost, s));
     if (nt > 0)
-        DP_HIP(c, hipMemcpyAsync(c->t_htris.data(), c->t_tris.p, sizeof(int32_t) * 3 * (size_t)nt,
+        DP_HIP(c, hipMemcpyAsync(c->tsdf.htris.data(), c->tsdf.tris.p, sizeof(int32_t) * 3 * (size_t)nt,
                                  hipMemcpyDeviceToHost, s));
     DP_HIP(c, hipStreamSynchronize(s));
-    DP_HIP(c, hipEventElapsedTime(&ms1, c->t_e2, c->t_e3));
-    *vertices = nv > 0 ? c->t_hverts.data() : nullptr;
-    *triangles = nt > 0 ? c->t_htris.data() : nullptr;
-    return mesh_finish(c, (double)ms0 + (double)ms1, n_vertices, n_triangles, stats);
+    DP_HIP(c, c->tsdf.time[1].ms(ms1));
+    *vertices = nv > 0 ? c->tsdf.hverts.data() : nullptr;
+    *triangles = nt > 0 ? c->tsdf.htris.data() : nullptr;
+    return mesh_finish(c, ms0 + ms1, n_vertices, n_triangles, stats);
 }

@@ -966,6 +966,19 @@ def _mesh_triangles(who: str, triangles) -> np.ndarray:
     return np.ascontiguousarray(tris, dtype=np.int32)
 
 
+def _check_view_ids(who: str, V: int, views, cap=64):
+    """The `views` argument of a map stage (None = all V): 1..cap ids (cap None:
+    at least one), unique and < V, raised as ValueError; returns them as int64."""
+    vid = np.arange(V, dtype=np.int64) if views is None else np.asarray(list(views), dtype=np.int64)
+    if cap is None and (vid.ndim != 1 or len(vid) == 0):
+        raise ValueError("%s: no views" % who)
+    if cap is not None and (vid.ndim != 1 or not 1 <= len(vid) <= cap):
+        raise ValueError("%s: 1..%d views" % (who, cap))
+    if (vid < 0).any() or (vid >= V).any() or len(set(vid.tolist())) != len(vid):
+        raise ValueError("%s: view ids must be unique and < %d" % (who, V))
+    return vid
+
+
 def check_mesh_clean_args(min_triangles=1, min_fraction=0.0, max_components=0):
     """Argument validation of Engine.mesh_clean[_device] (the limits of
     dp_mesh_clean_options, raised as ValueError before any device call); returns
@@ -1015,11 +1028,7 @@ def check_tsdf_args(V: int, views, origin, voxel, dim, trunc, min_weight: int = 
         raise ValueError("tsdf: at most 2^30 voxels")
     if not (number(min_weight) and int(min_weight) == min_weight and 1 <= int(min_weight) <= 64):
         raise ValueError("tsdf: min_weight must be in 1..64")
-    vid = np.arange(V, dtype=np.int64) if views is None else np.asarray(list(views), dtype=np.int64)
-    if vid.ndim != 1 or not 1 <= len(vid) <= 64:
-        raise ValueError("tsdf: 1..64 views")
-    if (vid < 0).any() or (vid >= V).any() or len(set(vid.tolist())) != len(vid):
-        raise ValueError("tsdf: view ids must be unique and < %d" % V)
+    vid = _check_view_ids("tsdf", V, views)
     to = N.DpTsdfOptions((ctypes.c_float * 3)(*[float(c) for c in origin]), float(voxel),
                          (ctypes.c_int32 * 3)(*[int(d) for d in dim]), float(trunc), int(min_weight), 0)
     return to, np.ascontiguousarray(vid, dtype=np.int32)
@@ -1085,11 +1094,7 @@ def check_mapref_args(V: int, views=None, sources=None, **options):
         raise ValueError("refine_maps: top_k must be in 1..max_sources")
     if not (number(o["min_ncc"]) and -1 <= o["min_ncc"] <= 1):
         raise ValueError("refine_maps: min_ncc must be in -1..1")
-    vid = np.arange(V, dtype=np.int64) if views is None else np.asarray(list(views), dtype=np.int64)
-    if vid.ndim != 1 or not 1 <= len(vid) <= 64:
-        raise ValueError("refine_maps: 1..64 views")
-    if (vid < 0).any() or (vid >= V).any() or len(set(vid.tolist())) != len(vid):
-        raise ValueError("refine_maps: view ids must be unique and < %d" % V)
+    vid = _check_view_ids("refine_maps", V, views)
     src = None
     if sources is not None:
         ms = int(o["max_sources"])
@@ -1138,11 +1143,7 @@ def check_fuse_args(V: int, views, depth_tol: float, min_views: int, min_normal_
         raise ValueError("fuse_maps: min_views must be in 0..63")
     if not (number(min_normal_cos) and 0 <= min_normal_cos <= 1):
         raise ValueError("fuse_maps: min_normal_cos must be in 0..1")
-    vid = np.arange(V, dtype=np.int64) if views is None else np.asarray(list(views), dtype=np.int64)
-    if vid.ndim != 1 or not 1 <= len(vid) <= 64:
-        raise ValueError("fuse_maps: 1..64 views")
-    if (vid < 0).any() or (vid >= V).any() or len(set(vid.tolist())) != len(vid):
-        raise ValueError("fuse_maps: view ids must be unique and < %d" % V)
+    vid = _check_view_ids("fuse_maps", V, views)
     fo = N.DpFuseOptions(float(depth_tol), int(min_views), float(min_normal_cos), 0 if suppress else N.FUSE_NO_SUPPRESS)
     return fo, np.ascontiguousarray(vid, dtype=np.int32)
 
@@ -1157,11 +1158,7 @@ def check_render_args(n: int, V: int, views, keep, splat_scale: float, max_radiu
         raise ValueError("render_maps: splat_scale must be > 0")
     if int(max_radius_px) != max_radius_px or not 1 <= int(max_radius_px) <= 255:
         raise ValueError("render_maps: max_radius_px must be in 1..255")
-    vid = np.arange(V, dtype=np.int32) if views is None else np.asarray(list(views), dtype=np.int64)
-    if vid.ndim != 1 or len(vid) == 0:
-        raise ValueError("render_maps: no views")
-    if (vid < 0).any() or (vid >= V).any() or len(set(vid.tolist())) != len(vid):
-        raise ValueError("render_maps: view ids must be unique and < %d" % V)
+    vid = _check_view_ids("render_maps", V, views, cap=None)
     if keep is not None:
         keep = np.ascontiguousarray(keep, dtype=np.uint8)
         if keep.shape != (n,):
