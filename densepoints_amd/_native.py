@@ -288,6 +288,45 @@ MESH_COMPONENT_DTYPE = np.dtype([("root", "<i4"), ("vertices", "<i4"), ("triangl
 assert MESH_COMPONENT_DTYPE.itemsize == 16 and ctypes.sizeof(DpMeshCleanOptions) == 24
 
 
+DP_VERTEX_BOUNDARY = 1
+DP_VERTEX_NONMANIFOLD = 2
+DP_SMOOTH_FREE_BOUNDARY = 1
+
+
+class DpMeshSmoothOptions(ctypes.Structure):
+    """dp_mesh_smooth_options: the steps of dp_mesh_smooth (include/densepoints.h).
+    `lambda` is a Python keyword: read it with getattr."""
+    _fields_ = [
+        ("iterations", ctypes.c_int32),
+        ("lambda", ctypes.c_float),
+        ("mu", ctypes.c_float),
+        ("flags", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
+    ]
+
+
+_ADJACENCY_COUNTS = ["vertices_in", "triangles_in", "invalid_triangles", "degenerate_triangles", "isolated_vertices",
+                     "edges", "boundary_edges", "nonmanifold_edges", "boundary_vertices", "max_valence"]
+
+
+class DpMeshAdjacencyStats(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int64) for n in _ADJACENCY_COUNTS] + [("adjacency_ms", ctypes.c_double)]
+
+
+class DpMeshSmoothStats(ctypes.Structure):
+    _fields_ = ([(n, ctypes.c_int64) for n in _ADJACENCY_COUNTS + ["movable_vertices", "pinned_vertices", "steps"]]
+                + [("adjacency_ms", ctypes.c_double), ("smooth_ms", ctypes.c_double)])
+
+
+class DpMeshNormalsStats(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int64) for n in ("vertices_in", "triangles_in", "invalid_triangles",
+                                              "degenerate_triangles", "zero_normals")] + [("normals_ms", ctypes.c_double)]
+
+
+assert ctypes.sizeof(DpMeshSmoothOptions) == 20 and ctypes.sizeof(DpMeshAdjacencyStats) == 88
+assert ctypes.sizeof(DpMeshSmoothStats) == 120 and ctypes.sizeof(DpMeshNormalsStats) == 48
+
+
 class DpSynthConfig(ctypes.Structure):
     _fields_ = [
         ("n_views", ctypes.c_int32),
@@ -428,6 +467,14 @@ SIGNATURES = [
     ("dp_mesh_clean", _I, [_P, _P, _P, ctypes.c_int64, _P, ctypes.c_int64, _P, _P, _P, _P, _P, _P, _P]),
     ("dp_mesh_clean_device", _I, [_P, _P, _P, ctypes.c_int64, _P, ctypes.c_int64, _P, ctypes.c_int64, _P, _P,
                                   ctypes.c_int64, _P, _P, _P, _P, _P]),
+    ("dp_default_mesh_smooth_options", None, [_P]),
+    ("dp_mesh_adjacency", _I, [_P, _P, ctypes.c_int64, ctypes.c_int64, _P, _P, _P, _P, _P, _P]),
+    ("dp_mesh_adjacency_device", _I, [_P, _P, ctypes.c_int64, ctypes.c_int64, _P, _P, _P, ctypes.c_int64, _P, _P, _P,
+                                      _P]),
+    ("dp_mesh_smooth", _I, [_P, _P, _P, ctypes.c_int64, _P, ctypes.c_int64, _P, _P]),
+    ("dp_mesh_smooth_device", _I, [_P, _P, _P, ctypes.c_int64, _P, ctypes.c_int64, _P, _P, _P]),
+    ("dp_mesh_normals", _I, [_P, _P, ctypes.c_int64, _P, ctypes.c_int64, _P, _P]),
+    ("dp_mesh_normals_device", _I, [_P, _P, ctypes.c_int64, _P, ctypes.c_int64, _P, _P, _P]),
     ("dp_last_kernel_ms", _I, [_P, _P]),
     ("dp_default_matcher_options", None, [_P]),
     ("dp_orb_pattern", _I, [_P]),

@@ -6,7 +6,8 @@
 // generation (their own state is dp_seedgen.h); the map stages --
 // dp_render.hip: maps; dp_fuse.hip: their fusion; dp_mapref.hip: their
 // refinement; dp_tsdf.hip: their volume and mesh; dp_meshclean.hip: the mesh's
-// components -- each with its scratch as one named member of the context and
+// components; dp_meshsmooth.hip: its adjacency, smoothing and normals -- each
+// with its scratch as one named member of the context and
 // the host helpers they share at the end of this file).  Every member that
 // owns a device or pinned allocation or an event has an owning type
 // (dp_buf.h), so deleting the context frees them; only the views and the
@@ -140,6 +141,33 @@ struct CleanScratch {
     Timer time[3];
 };
 
+// dp_mesh_adjacency / dp_mesh_smooth / dp_mesh_normals.  The adjacency: the
+// 6T edge keys and their sorted copy (the unsorted keys' memory holds the rows'
+// neighbours and counts after the sort), every sorted key's entry number, the
+// offsets and flags (the outputs may be NULL or capped; the smoothing reads
+// these), per-block head counts and their scan, the largest valence.  The
+// smoothing: two compact position arrays (3 floats per vertex).  The normals:
+// the 3T (vertex, triangle) pairs and their sorted copies.  The host forms'
+// staged inputs, device results and pinned results.
+struct MeshSmoothScratch {
+    DevBuf<unsigned long long> keys, keys_sorted, bcount, boff;
+    DevBuf<int32_t> hpos, off, maxval;
+    DevBuf<uint8_t> vflags;
+    StripedCounters count; // + the entry total, the largest valence
+    DevBuf<float> pos[2];
+    DevBuf<uint32_t> ikeys, ikeys_sorted;
+    DevBuf<int32_t> itris, itris_sorted;
+    DevBuf<unsigned char> in;
+    DevBuf<int32_t> csr;
+    DevBuf<dp_mesh_vertex> verts;
+    DevBuf<float> normals;
+    HostBuf<int32_t> hcsr;
+    HostBuf<uint8_t> hflags;
+    HostBuf<dp_mesh_vertex> hverts;
+    HostBuf<float> hnormals;
+    Timer time[2]; // the adjacency; the steps or the normals
+};
+
 } // namespace dpk
 
 struct SeedgenFree {
@@ -194,6 +222,7 @@ struct dp_ctx {
     dpk::MaprefScratch mapref;
     dpk::TsdfScratch tsdf;
     dpk::CleanScratch clean;
+    dpk::MeshSmoothScratch smooth;
     HostBuf<dp_patch> result; // dp_densify / dp_densify_result output (pinned)
     // dp_densify_iterate: per iteration {evaluations, filter survivors} on the
     // device (read once, at the end) and the filters' timing events

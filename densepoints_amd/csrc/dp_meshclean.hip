@@ -31,20 +31,18 @@
 // Every index read from a triangle is compared with n_vertices before it is
 // used as an address: an invalid triangle reaches neither parent[] nor the
 // vertex array.
-#include "dp_ctx.h"
-#include "dp_mapdev.h"
+#include "dp_meshdev.h"
 #include "dp_wave.h"
 
 #include <hipcub/hipcub.hpp>
 
 #include <algorithm>
 #include <cmath>
-#include <initializer_list>
 
 namespace dpk {
 namespace {
 
-constexpr int kCleanBlock = 256;
+constexpr int kCleanBlock = kMeshLanes;
 constexpr int kCleanStripes = 64;  // each counter kept kCleanStripes times (summed by the host)
 constexpr int kCleanCounters = 3;  // invalid triangles, used vertices, kept components
 constexpr unsigned long long kPadKey = ~0ull;
@@ -79,7 +77,7 @@ __device__ __forceinline__ int64_t seg_roots(const CleanArgs &) { return 0; }
 __device__ __forceinline__ int64_t seg_verts(const CleanArgs &a) { return a.nbv + 1; }
 __device__ __forceinline__ int64_t seg_tris(const CleanArgs &a) { return 2 * (a.nbv + 1); }
 
-__device__ __forceinline__ int64_t item_of() { return (int64_t)blockIdx.x * kCleanBlock + threadIdx.x; }
+__device__ __forceinline__ int64_t item_of() { return mesh_item(); }
 
 // parent[] is read and linked by many lanes at once: the loads are atomic, so a
 // lane never acts on a cached copy that another lane's link has replaced
@@ -152,13 +150,7 @@ __device__ __forceinline__ void wave_add_by_key(int32_t *cnt, int32_t key, bool 
 // the triangle's indices; false (and nothing else read) unless all three are vertices
 __device__ __forceinline__ bool load_triangle(const CleanArgs &a, int64_t t, int32_t v[3])
 {
-    if (t >= a.nt)
-        return false;
-    v[0] = a.tris[3 * t];
-    v[1] = a.tris[3 * t + 1];
-    v[2] = a.tris[3 * t + 2];
-    const uint64_t nv = (uint64_t)a.nv;
-    return (uint64_t)(uint32_t)v[0] < nv && (uint64_t)(uint32_t)v[1] < nv && (uint64_t)(uint32_t)v[2] < nv;
+    return load_valid_triangle(a.tris, a.nt, a.nv, t, v);
 }
 
 __global__ __launch_bounds__(kCleanBlock) void clean_init_kernel(CleanArgs a)
@@ -335,14 +327,6 @@ __global__ __launch_bounds__(kCleanBlock) void clean_temit_kernel(CleanArgs a)
     }
 }
 
-template <typename K> hipError_t launch_over(K kernel, int64_t blocks, const CleanArgs &a, hipStream_t s)
-{
-    if (blocks <= 0)
-        return hipSuccess;
-    hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(kCleanBlock), 0, s, a);
-    return hipGetLastError();
-}
-
 } // namespace
 } // namespace dpk
 
@@ -369,15 +353,6 @@ struct CleanRun {
     size_t tmp_bytes = 0;
 };
 
-int clean_check_counts(dp_ctx *c, const std::string &w, const void *tris, int64_t nt, int64_t nv)
-{
-    if (nt < 0 || nv < 0 || nt > 0x7FFFFFFFll || nv > 0x7FFFFFFFll)
-        return fail(c, DP_E_ARG, w + ": the counts must be in 0..2^31 - 1");
-    if (nt > 0 && !tris)
-        return fail(c, DP_E_ARG, w + ": triangles must be given");
-    return DP_OK;
-}
-
 int clean_check_options(dp_ctx *c, const std::string &w, const dp_mesh_clean_options &o)
 {
     if (o.min_triangles < 0)
@@ -388,24 +363,6 @@ int clean_check_options(dp_ctx *c, const std::string &w, const dp_mesh_clean_opt
         return fail(c, DP_E_ARG, w + ": max_components must be >= 0");
     if (o.flags != 0)
         return fail(c, DP_E_ARG, w + ": unknown flag bits");
-    return DP_OK;
-}
-
-int clean_check_cap(dp_ctx *c, const std::string &w, const void *buf, int64_t cap)
-{
-    if (cap < 0 || (cap > 0 && !buf))
-        return fail(c, DP_E_ARG, w + ": a cap must be >= 0, with its buffer given when > 0");
-    return DP_OK;
-}
-
-// an output may not be an input
-int clean_check_alias(dp_ctx *c, const std::string &w, std::initializer_list<const void *> outs,
-                      std::initializer_list<const void *> ins)
-{
-    for (const void *o : outs)
-        for (const void *i : ins)
-            if (o && o == i)
-                return fail(c, DP_E_ARG, w + ": an output pointer equals an input pointer");
     return DP_OK;
 }
 
@@ -591,13 +548,13 @@ extern "C" int dp_mesh_components_device(dp_ctx *c, const int32_t *d_triangles, 
     if (!c)
         return DP_E_ARG;
     const std::string w = "dp_mesh_components_device";
-    int rc = clean_check_counts(c, w, d_triangles, n_triangles, n_vertices);
+    int rc = mesh_check_counts(c, w, d_triangles, n_triangles, n_vertices);
     if (rc == DP_OK && !n_components)
         rc = fail(c, DP_E_ARG, w + ": n_components must be given");
     if (rc == DP_OK)
-        rc = clean_check_cap(c, w, d_components, component_cap);
+        rc = mesh_check_cap(c, w, d_components, component_cap);
     if (rc == DP_OK)
-        rc = clean_check_alias(c, w, {d_vertex_component, d_triangle_component, d_components}, {d_triangles});
+        rc = mesh_check_alias(c, w, {d_vertex_component, d_triangle_component, d_components}, {d_triangles});
     if (rc != DP_OK)
         return rc;
     hipSetDevice(c->device);
@@ -637,11 +594,11 @@ extern "C" int dp_mesh_components(dp_ctx *c, const int32_t *triangles, int64_t n
     if (!c)
         return DP_E_ARG;
     const std::string w = "dp_mesh_components";
-    int rc = clean_check_counts(c, w, triangles, n_triangles, n_vertices);
+    int rc = mesh_check_counts(c, w, triangles, n_triangles, n_vertices);
     if (rc == DP_OK && (!n_components || !components))
         rc = fail(c, DP_E_ARG, w + ": components and n_components must be given");
     if (rc == DP_OK)
-        rc = clean_check_alias(c, w, {vertex_component, triangle_component}, {triangles});
+        rc = mesh_check_alias(c, w, {vertex_component, triangle_component}, {triangles});
     if (rc != DP_OK)
         return rc;
     hipSetDevice(c->device);
@@ -708,7 +665,7 @@ extern "C" int dp_mesh_clean_device(dp_ctx *c, const dp_mesh_clean_options *mco,
     dp_default_mesh_clean_options(&o);
     if (mco)
         o = *mco;
-    int rc = clean_check_counts(c, w, d_triangles, n_triangles, n_vertices);
+    int rc = mesh_check_counts(c, w, d_triangles, n_triangles, n_vertices);
     if (rc == DP_OK && n_vertices > 0 && !d_vertices)
         rc = fail(c, DP_E_ARG, w + ": vertices must be given");
     if (rc == DP_OK)
@@ -716,11 +673,11 @@ extern "C" int dp_mesh_clean_device(dp_ctx *c, const dp_mesh_clean_options *mco,
     if (rc == DP_OK && (!n_vertices_out || !n_triangles_out))
         rc = fail(c, DP_E_ARG, w + ": n_vertices_out and n_triangles_out must be given");
     if (rc == DP_OK)
-        rc = clean_check_cap(c, w, d_vertices_out, vertex_cap);
+        rc = mesh_check_cap(c, w, d_vertices_out, vertex_cap);
     if (rc == DP_OK)
-        rc = clean_check_cap(c, w, d_triangles_out, triangle_cap);
+        rc = mesh_check_cap(c, w, d_triangles_out, triangle_cap);
     if (rc == DP_OK)
-        rc = clean_check_alias(c, w, {d_vertices_out, d_triangles_out, d_vertex_map, d_triangle_map},
+        rc = mesh_check_alias(c, w, {d_vertices_out, d_triangles_out, d_vertex_map, d_triangle_map},
                                {d_vertices, d_triangles});
     if (rc != DP_OK)
         return rc;
@@ -767,7 +724,7 @@ extern "C" int dp_mesh_clean(dp_ctx *c, const dp_mesh_clean_options *mco, const 
     dp_default_mesh_clean_options(&o);
     if (mco)
         o = *mco;
-    int rc = clean_check_counts(c, w, triangles, n_triangles, n_vertices);
+    int rc = mesh_check_counts(c, w, triangles, n_triangles, n_vertices);
     if (rc == DP_OK && n_vertices > 0 && !vertices)
         rc = fail(c, DP_E_ARG, w + ": vertices must be given");
     if (rc == DP_OK)
@@ -775,7 +732,7 @@ extern "C" int dp_mesh_clean(dp_ctx *c, const dp_mesh_clean_options *mco, const 
     if (rc == DP_OK && (!n_vertices_out || !n_triangles_out || !vertices_out || !triangles_out))
         rc = fail(c, DP_E_ARG, w + ": the result and count pointers must be given");
     if (rc == DP_OK)
-        rc = clean_check_alias(c, w, {vertex_map, triangle_map}, {vertices, triangles});
+        rc = mesh_check_alias(c, w, {vertex_map, triangle_map}, {vertices, triangles});
     if (rc != DP_OK)
         return rc;
     hipSetDevice(c->device);

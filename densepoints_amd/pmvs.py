@@ -39,6 +39,7 @@ __all__ = [
     "check_mapref_args",
     "check_tsdf_args",
     "check_mesh_clean_args",
+    "check_mesh_smooth_args",
     "mesh_volume",
     "write_mesh_ply",
     "read_pfm",
@@ -935,6 +936,149 @@ class Engine:
                                              _addr(stream)))
         return int(no.value), int(to.value), _mesh_clean_stats(st)
 
+    # ---- adjacency, smoothing, normals (include/densepoints.h dp_mesh_adjacency / _smooth / _normals) ----
+    def mesh_adjacency(self, triangles, n_vertices: int) -> dict:
+        """dp_mesh_adjacency: the vertex adjacency of `triangles` (n x 3 int32)
+        over n_vertices vertices as sorted CSR rows.  Returns {"offsets" int32
+        (n_vertices + 1), "neighbours" int32, "edge_triangles" int32 (the
+        triangles on each entry's edge), "vertex_flags" uint8 (bit 0: on a
+        boundary edge, bit 1: on a nonmanifold edge), "stats"}."""
+        tris = _mesh_triangles("mesh_adjacency", triangles)
+        nv = _mesh_count("mesh_adjacency", n_vertices)
+        _mesh_entries("mesh_adjacency", len(tris))
+        po, pn, pe, pf = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
+        ne, st = ctypes.c_int64(), N.DpMeshAdjacencyStats()
+        self._check(lib.dp_mesh_adjacency(self._ctx, ptr(tris) if len(tris) else None, len(tris), nv, ctypes.byref(po),
+                                          ctypes.byref(pn), ctypes.byref(pe), ctypes.byref(pf), ctypes.byref(ne),
+                                          ctypes.byref(st)))
+        E = int(ne.value)
+        off, nbr, cnt = np.zeros(nv + 1, np.int32), np.zeros(E, np.int32), np.zeros(E, np.int32)
+        flags = np.zeros(nv, np.uint8)
+        ctypes.memmove(off.ctypes.data, po.value, off.nbytes)
+        if E:
+            ctypes.memmove(nbr.ctypes.data, pn.value, nbr.nbytes)
+            ctypes.memmove(cnt.ctypes.data, pe.value, cnt.nbytes)
+        if nv:
+            ctypes.memmove(flags.ctypes.data, pf.value, flags.nbytes)
+        return dict(offsets=off, neighbours=nbr, edge_triangles=cnt, vertex_flags=flags, stats=_stats_dict(st))
+
+    def mesh_adjacency_device(self, d_triangles, n_triangles: int, n_vertices: int, d_offsets=None, d_neighbours=None,
+                              d_edge_triangles=None, entry_cap: int = 0, d_vertex_flags=None,
+                              stream: int | None = None):
+        """dp_mesh_adjacency_device: device triangles (an address) into the
+        device arrays given (addresses, None = not wanted); d_neighbours and
+        d_edge_triangles get at most entry_cap entries.  Queued on `stream`; one
+        wait.  Returns (the full entry count -- above the cap: an overflow --,
+        stats)."""
+        nt, nv = _mesh_count("mesh_adjacency_device", n_triangles), _mesh_count("mesh_adjacency_device", n_vertices)
+        _mesh_entries("mesh_adjacency_device", nt)
+        if isinstance(entry_cap, bool) or not isinstance(entry_cap, (int, np.integer)) or entry_cap < 0:
+            raise ValueError("mesh_adjacency_device: a cap must be >= 0")
+        if nt and not d_triangles:
+            raise ValueError("mesh_adjacency_device: the triangles must be given")
+        ne, st = ctypes.c_int64(), N.DpMeshAdjacencyStats()
+        self._check(lib.dp_mesh_adjacency_device(self._ctx, _addr(d_triangles), nt, nv, _addr(d_offsets),
+                                                 _addr(d_neighbours), _addr(d_edge_triangles), int(entry_cap),
+                                                 _addr(d_vertex_flags), ctypes.byref(ne), ctypes.byref(st),
+                                                 _addr(stream)))
+        return int(ne.value), _stats_dict(st)
+
+    def mesh_smooth(self, vertices, triangles, iterations: int = 10, lam: float = 0.5, mu: float = -0.53,
+                    free_boundary: bool = False):
+        """dp_mesh_smooth: `iterations` Taubin iterations (a step of factor lam,
+        then one of factor mu; mu = 0: plain Laplacian steps) of the vertex
+        positions towards their neighbours' mean; boundary vertices stay where
+        they are unless free_boundary.  Returns (vertices with pos replaced,
+        stats); the triangles are untouched."""
+        mso = check_mesh_smooth_args(iterations, lam, mu, free_boundary)
+        verts = np.ascontiguousarray(vertices, dtype=N.MESH_VERTEX_DTYPE).reshape(-1)
+        tris = _mesh_triangles("mesh_smooth", triangles)
+        nv, nt = len(verts), len(tris)
+        _mesh_entries("mesh_smooth", nt)
+        pv, st = ctypes.c_void_p(), N.DpMeshSmoothStats()
+        self._check(lib.dp_mesh_smooth(self._ctx, ctypes.byref(mso), ptr(verts) if nv else None, nv,
+                                       ptr(tris) if nt else None, nt, ctypes.byref(pv), ctypes.byref(st)))
+        out = np.zeros(nv, dtype=N.MESH_VERTEX_DTYPE)
+        if nv:
+            ctypes.memmove(out.ctypes.data, pv.value, out.nbytes)
+        return out, _stats_dict(st)
+
+    def mesh_smooth_device(self, d_vertices, n_vertices: int, d_triangles, n_triangles: int, d_vertices_out,
+                           iterations: int = 10, lam: float = 0.5, mu: float = -0.53, free_boundary: bool = False,
+                           stats: bool = True, stream: int | None = None):
+        """dp_mesh_smooth_device: a device mesh (addresses) smoothed into the
+        n_vertices records at d_vertices_out (not d_vertices).  Every step is
+        queued on `stream`; with stats=False the call does not wait and returns
+        None, else it waits once and returns the stats."""
+        mso = check_mesh_smooth_args(iterations, lam, mu, free_boundary)
+        nv, nt = _mesh_count("mesh_smooth_device", n_vertices), _mesh_count("mesh_smooth_device", n_triangles)
+        _mesh_entries("mesh_smooth_device", nt)
+        if (nv and not (d_vertices and d_vertices_out)) or (nt and not d_triangles):
+            raise ValueError("mesh_smooth_device: the vertices, the triangles and the output must be given")
+        if nv and d_vertices == d_vertices_out:
+            raise ValueError("mesh_smooth_device: the output must differ from the input")
+        st = N.DpMeshSmoothStats()
+        self._check(lib.dp_mesh_smooth_device(self._ctx, ctypes.byref(mso), _addr(d_vertices), nv, _addr(d_triangles),
+                                              nt, _addr(d_vertices_out), ctypes.byref(st) if stats else None,
+                                              _addr(stream)))
+        return _stats_dict(st) if stats else None
+
+    def mesh_normals(self, vertices, triangles):
+        """dp_mesh_normals: the area-weighted unit normal of every vertex (the
+        zero vector where no proper triangle names it or the sum vanishes).
+        Returns (normals as n x 3 float32, stats)."""
+        verts = np.ascontiguousarray(vertices, dtype=N.MESH_VERTEX_DTYPE).reshape(-1)
+        tris = _mesh_triangles("mesh_normals", triangles)
+        nv, nt = len(verts), len(tris)
+        pn, st = ctypes.c_void_p(), N.DpMeshNormalsStats()
+        self._check(lib.dp_mesh_normals(self._ctx, ptr(verts) if nv else None, nv, ptr(tris) if nt else None, nt,
+                                        ctypes.byref(pn), ctypes.byref(st)))
+        out = np.zeros((nv, 3), np.float32)
+        if nv:
+            ctypes.memmove(out.ctypes.data, pn.value, out.nbytes)
+        return out, _stats_dict(st)
+
+    def mesh_normals_device(self, d_vertices, n_vertices: int, d_triangles, n_triangles: int, d_normals,
+                            stats: bool = True, stream: int | None = None):
+        """dp_mesh_normals_device: the normals of a device mesh (addresses) into
+        the 3 * n_vertices floats at d_normals.  Queued on `stream`; with
+        stats=False the call does not wait and returns None."""
+        nv, nt = _mesh_count("mesh_normals_device", n_vertices), _mesh_count("mesh_normals_device", n_triangles)
+        if (nv and not (d_vertices and d_normals)) or (nt and not d_triangles):
+            raise ValueError("mesh_normals_device: the vertices, the triangles and the output must be given")
+        st = N.DpMeshNormalsStats()
+        self._check(lib.dp_mesh_normals_device(self._ctx, _addr(d_vertices), nv, _addr(d_triangles), nt,
+                                               _addr(d_normals), ctypes.byref(st) if stats else None, _addr(stream)))
+        return _stats_dict(st) if stats else None
+
+
+def _stats_dict(st) -> dict:
+    return {name: getattr(st, name) for name, _ in st._fields_}
+
+
+def _mesh_entries(who: str, nt: int) -> None:
+    if 6 * nt > 2**31 - 1:
+        raise ValueError("%s: 6 * n_triangles must be <= 2^31 - 1" % who)
+
+
+def check_mesh_smooth_args(iterations=10, lam=0.5, mu=-0.53, free_boundary=False):
+    """Argument validation of Engine.mesh_smooth[_device] (the limits of
+    dp_mesh_smooth_options, raised as ValueError before any device call); returns
+    the dp_mesh_smooth_options.  lam is the struct's lambda."""
+    def real(x):
+        return not isinstance(x, bool) and isinstance(x, (int, float, np.integer, np.floating))
+
+    if isinstance(iterations, bool) or not isinstance(iterations, (int, np.integer)) or not 0 <= int(iterations) <= 1000:
+        raise ValueError("mesh_smooth: iterations must be a whole number in 0..1000")
+    if not real(lam) or not 0.0 < float(np.float32(lam)) <= 1.0:
+        raise ValueError("mesh_smooth: lam must be in (0, 1]")
+    if not real(mu) or not float(np.float32(mu)) <= 0.0 or np.isinf(np.float32(mu)):
+        raise ValueError("mesh_smooth: mu must be finite and <= 0")
+    if not isinstance(free_boundary, (bool, np.bool_)):
+        raise ValueError("mesh_smooth: free_boundary must be a bool")
+    return N.DpMeshSmoothOptions(int(iterations), float(lam), float(mu),
+                                 N.DP_SMOOTH_FREE_BOUNDARY if free_boundary else 0, 0)
+
 
 def _addr(a):
     return ctypes.c_void_p(a) if a else None
@@ -1362,7 +1506,8 @@ class PMVS:
         self.stats["render"], self.stats["fused"] = rst, fst
         return out
 
-    def mesh(self, refine: int = 0, voxel=None, dim: int = 256, trunc=None, min_weight: int = 2, clean=None, **kw):
+    def mesh(self, refine: int = 0, voxel=None, dim: int = 256, trunc=None, min_weight: int = 2, clean=None,
+             smooth=None, normals: bool = False, **kw):
         """The last run()'s result as a triangle mesh: (vertices as a
         MESH_VERTEX_DTYPE array, triangles as n x 3 int32).  The depth maps of
         depth_maps(refine, **kw) -- kw: its render and refinement options --
@@ -1372,13 +1517,20 @@ class PMVS:
         surface is extracted (Engine.tsdf_mesh) over the voxels that at least
         min_weight views observed.  clean: a dict of Engine.mesh_clean's options
         (min_triangles, min_fraction, max_components) drops the mesh's small
-        components; None (the default) leaves the mesh as extracted.  The volume
-        and the statistics of the calls are left in self.stats["mesh"] (the
-        clean-up's under "clean")."""
+        components; None (the default) leaves the mesh as extracted.  smooth: a
+        dict of Engine.mesh_smooth's options (iterations, lam, mu,
+        free_boundary) relaxes the vertex positions after the clean-up; None
+        leaves them.  normals=True returns (vertices, triangles, normals), the
+        normals (Engine.mesh_normals, n x 3 float32) of the mesh as returned.
+        The volume and the statistics of the calls are left in
+        self.stats["mesh"] (the later stages' under "clean", "smooth" and
+        "normals")."""
         if not self._ran:
             raise ValueError("mesh: call run() first")
         if clean is not None:
             check_mesh_clean_args(**dict(clean))
+        if smooth is not None:
+            check_mesh_smooth_args(**dict(smooth))
         refine, mkw, kw = split_refine_args("mesh", refine, kw)
         vol = mesh_volume(self.patches["pos"], voxel, dim, trunc)
         check_tsdf_args(max(len(self.views), 1), kw.get("views"), min_weight=min_weight, **vol)
@@ -1392,9 +1544,18 @@ class PMVS:
             verts, tris, mst = eng.tsdf_mesh(volume, min_weight)
             if clean is not None:
                 verts, tris, cst = eng.mesh_clean(verts, tris, **dict(clean))
+            if smooth is not None:
+                verts, sst = eng.mesh_smooth(verts, tris, **dict(smooth))
+            if normals:
+                nrm, nst = eng.mesh_normals(verts, tris)
         self.stats["mesh"] = dict(vol, min_weight=int(min_weight), integrate=volume["stats"], mesh=mst)
         if clean is not None:
             self.stats["mesh"]["clean"] = cst
+        if smooth is not None:
+            self.stats["mesh"]["smooth"] = sst
+        if normals:
+            self.stats["mesh"]["normals"] = nst
+            return verts, tris, nrm
         return verts, tris
 
 
@@ -1445,11 +1606,17 @@ def write_ply(path: str, patches: np.ndarray) -> None:
             f.write(f"{x:g} {y:g} {z:g} {r} {g} {b} {nx:g} {ny:g} {nz:g}\n")
 
 
-def write_mesh_ply(path: str, vertices: np.ndarray, triangles: np.ndarray) -> None:
+def write_mesh_ply(path: str, vertices: np.ndarray, triangles: np.ndarray, normals=None) -> None:
     """A triangle mesh (Engine.tsdf_mesh's vertices and triangles) as an ASCII
     PLY: vertex x y z (float, %.9g: an f32 round-trips) red green blue (uchar),
-    face vertex_indices (list uchar int)."""
+    face vertex_indices (list uchar int).  With normals (Engine.mesh_normals's,
+    one row per vertex) every vertex also carries nx ny nz (float, %.9g) after
+    its colour."""
     triangles = np.asarray(triangles).reshape(-1, 3)
+    if normals is not None:
+        normals = np.asarray(normals, dtype=np.float32).reshape(-1, 3)
+        if len(normals) != len(vertices):
+            raise ValueError("write_mesh_ply: one normal per vertex")
     with open(path, "w") as f:
         f.write("ply\nformat ascii 1.0\n")
         f.write(f"element vertex {len(vertices)}\n")
@@ -1457,12 +1624,19 @@ def write_mesh_ply(path: str, vertices: np.ndarray, triangles: np.ndarray) -> No
             f.write(f"property float {n}\n")
         for n in ("red", "green", "blue"):
             f.write(f"property uchar {n}\n")
+        if normals is not None:
+            for n in ("nx", "ny", "nz"):
+                f.write(f"property float {n}\n")
         f.write(f"element face {len(triangles)}\n")
         f.write("property list uchar int vertex_indices\n")
         f.write("end_header\n")
-        for v in vertices:
+        for k, v in enumerate(vertices):
             x, y, z = (float(c) for c in v["pos"])
             r, g, b = (int(c) for c in v["rgb"])
-            f.write(f"{x:.9g} {y:.9g} {z:.9g} {r} {g} {b}\n")
+            if normals is None:
+                f.write(f"{x:.9g} {y:.9g} {z:.9g} {r} {g} {b}\n")
+            else:
+                nx, ny, nz = (float(c) for c in normals[k])
+                f.write(f"{x:.9g} {y:.9g} {z:.9g} {r} {g} {b} {nx:.9g} {ny:.9g} {nz:.9g}\n")
         for t in triangles:
             f.write(f"3 {int(t[0])} {int(t[1])} {int(t[2])}\n")

@@ -943,6 +943,136 @@ int dp_mesh_clean_device(dp_ctx *ctx, const dp_mesh_clean_options *mco, const dp
                          int32_t *d_triangles_out, int64_t triangle_cap, int64_t *n_triangles_out,
                          int32_t *d_vertex_map, int32_t *d_triangle_map, dp_mesh_clean_stats *stats, void *stream);
 
+/* ---- mesh adjacency, Taubin smoothing and vertex normals -----------------------
+ * No reference counterpart.  The mesh of dp_tsdf_mesh is terraced (every vertex
+ * sits on a lattice edge), carries the depth maps' noise and has no normals;
+ * these three calls build the adjacency of a triangle mesh, relax its vertex
+ * positions and give every vertex an area-weighted normal.  None reads a view.
+ * Every result is independent of the order in which lanes or blocks run: the
+ * integer part is counts and sorted sets, every float sum runs over a sorted
+ * row in a fixed order, and there is no floating-point atomic.  Every fp64
+ * expression below is one IEEE rounding per operation (no contraction), dvdiv
+ * and dvsqrt are the IEEE-correct fp64 quotient and square root, (float) and
+ * (double) are the IEEE conversions (round to nearest even).
+ *
+ * Definitions.  A triangle is VALID as in the clean-up section (three indices in
+ * [0, n_vertices)), DEGENERATE iff it is valid and two of its indices are equal,
+ * PROPER iff it is valid and not degenerate.  Only proper triangles take part in
+ * anything below; invalid and degenerate triangles are counted
+ * (invalid_triangles, degenerate_triangles) and their indices are never used as
+ * an address before the range check.  A proper triangle (a, b, c) puts b and c
+ * into N(a), a and c into N(b), a and b into N(c); N(v) is a set.  count(u, v) is
+ * the number of proper triangles that name both u and v.  Edge {u, v} is a
+ * BOUNDARY edge iff count = 1 and NONMANIFOLD iff count > 2.  Vertex flag byte:
+ * bit 0 (DP_VERTEX_BOUNDARY) set iff some incident edge is a boundary edge, bit 1
+ * (DP_VERTEX_NONMANIFOLD) set iff some incident edge is nonmanifold.
+ *
+ * dp_mesh_adjacency.  offsets: int32, n_vertices + 1 entries, offsets[0] = 0;
+ * row v is [offsets[v], offsets[v + 1]).  neighbours: int32, row v holds N(v) in
+ * ascending order.  edge_triangles: int32, parallel to neighbours, entry e of row
+ * v holds count(v, neighbours[e]).  vertex_flags: uint8, n_vertices entries.  The
+ * entry count E = offsets[n_vertices] is returned in *n_entries.  Statistics:
+ * vertices_in, triangles_in, invalid_triangles, degenerate_triangles,
+ * isolated_vertices (empty rows), edges = E / 2, boundary_edges,
+ * nonmanifold_edges, boundary_vertices (bit 0 set), max_valence (the longest
+ * row), adjacency_ms = device time of the call's kernels.
+ * Host form: any of the four result pointers may be NULL (not wanted); the
+ * arrays are context-owned, valid until the next dp_mesh_adjacency or destroy.
+ * Device form: any of the four buffers may be NULL; d_offsets and
+ * d_vertex_flags are written whole, d_neighbours / d_edge_triangles get the
+ * first min(entry_cap, E) entries and nothing beyond them; *n_entries is the
+ * full E, so a caller sees an overflow; everything is queued on `stream` (NULL =
+ * the context's) and the call waits once, for the counts.
+ *
+ * dp_mesh_smooth (dp_mesh_smooth_options; defaults are Taubin's lambda | mu
+ * pair, a design choice that nobody has tuned for this pipeline).  One STEP with
+ * factor f (the option widened to fp64) reads the previous step's positions only
+ * (Jacobi).  Vertex v is MOVABLE iff its row is non-empty and it is not pinned;
+ * pinned means bit 0 is set and DP_SMOOTH_FREE_BOUNDARY is not given.  For a
+ * movable v with n = |N(v)| and each coordinate c:
+ *   S = 0.0;  for j in row v, ascending:  S = S + (double)pos_j[c]
+ *   m = dvdiv(S, (double)n);  x = (double)pos_v[c];  new = (float)(x + f * (m - x))
+ * Other vertices keep their bits.  One iteration is a lambda step, then a mu
+ * step if mu != 0; positions are fp32 between steps.  The output is the input's
+ * 16-byte records with pos replaced, rgb and pad copied byte for byte; triangles
+ * are untouched, so the adjacency is built once per call.  iterations = 0
+ * copies.  Positions are expected to be finite.  Statistics: the adjacency's
+ * integer counts, movable_vertices, pinned_vertices, steps (launched),
+ * adjacency_ms, smooth_ms.
+ * Host form: *vertices_out is context-owned (valid until the next dp_mesh_smooth
+ * or destroy, NULL when n_vertices = 0).  Device form: d_vertices_out holds
+ * n_vertices records and must differ from d_vertices; all steps are queued
+ * behind one another on `stream` with no host wait between them; one wait at
+ * the end for the statistics, none when stats is NULL.
+ *
+ * dp_mesh_normals.  normal[v] (3 floats): walk the proper triangles that name v
+ * in ascending triangle index; for each such triangle (i0, i1, i2) with
+ * positions p0, p1, p2 (whichever of them v is):
+ *   e1 = (double)p1 - (double)p0,  e2 = (double)p2 - (double)p0   (componentwise)
+ *   g = (e1y*e2z - e1z*e2y,  e1z*e2x - e1x*e2z,  e1x*e2y - e1y*e2x)
+ *   s = s + g   (componentwise, s starts at 0.0)
+ * then l2 = (s.x*s.x + s.y*s.y) + s.z*s.z; if !(l2 > 0) or l2 is not finite the
+ * normal is (0, 0, 0) and counts in zero_normals, else normal_c =
+ * (float)dvdiv(s_c, dvsqrt(l2)).  With dp_tsdf_mesh's winding the normals point
+ * from inside (tsdf < 0) to outside.  The sum follows the triangle order, so the
+ * same mesh with its triangles reordered may give normals that differ in the
+ * last bits.  Statistics: vertices_in, triangles_in, invalid_triangles,
+ * degenerate_triangles, zero_normals, normals_ms.  Host form: *normals is
+ * context-owned (until the next dp_mesh_normals or destroy, NULL when n_vertices
+ * = 0).  Device form: d_normals holds 3 * n_vertices floats; one wait for the
+ * statistics, none when stats is NULL.
+ *
+ * Errors (DP_E_ARG), counts before pointers: the clean-up section's list (counts,
+ * NULL inputs, an output pointer equal to an input pointer, a negative cap), and
+ * for dp_mesh_adjacency and dp_mesh_smooth 6 * n_triangles > 2^31 - 1 (offsets
+ * are int32) and for dp_mesh_normals 3 * n_triangles > 2^31 - 1 (its pairs are
+ * counted in int32); iterations outside 0..1000; lambda outside (0, 1] or NaN; mu > 0 or
+ * NaN or infinite; unknown flag bits; a NULL n_entries or (host form) result
+ * pointer of dp_mesh_smooth / dp_mesh_normals; (device form) a NULL output of
+ * dp_mesh_smooth / dp_mesh_normals with n_vertices > 0. */
+#define DP_VERTEX_BOUNDARY 1
+#define DP_VERTEX_NONMANIFOLD 2
+#define DP_SMOOTH_FREE_BOUNDARY 1
+typedef struct dp_mesh_smooth_options {
+    int32_t iterations;  /* 10     lambda (| mu) iterations, 0..1000                     */
+    float   lambda;      /* 0.5    the shrinking step's factor, in (0, 1]                */
+    float   mu;          /* -0.53  the inflating step's factor, <= 0; 0 = plain Laplacian */
+    int32_t flags;       /* DP_SMOOTH_FREE_BOUNDARY: boundary vertices move too          */
+    int32_t reserved;
+} dp_mesh_smooth_options;
+typedef struct dp_mesh_adjacency_stats {
+    int64_t vertices_in, triangles_in, invalid_triangles, degenerate_triangles, isolated_vertices, edges,
+        boundary_edges, nonmanifold_edges, boundary_vertices, max_valence;
+    double adjacency_ms;
+} dp_mesh_adjacency_stats;
+typedef struct dp_mesh_smooth_stats {
+    int64_t vertices_in, triangles_in, invalid_triangles, degenerate_triangles, isolated_vertices, edges,
+        boundary_edges, nonmanifold_edges, boundary_vertices, max_valence, movable_vertices, pinned_vertices, steps;
+    double adjacency_ms, smooth_ms;
+} dp_mesh_smooth_stats;
+typedef struct dp_mesh_normals_stats {
+    int64_t vertices_in, triangles_in, invalid_triangles, degenerate_triangles, zero_normals;
+    double normals_ms;
+} dp_mesh_normals_stats;
+
+void dp_default_mesh_smooth_options(dp_mesh_smooth_options *mso);
+int dp_mesh_adjacency(dp_ctx *ctx, const int32_t *triangles, int64_t n_triangles, int64_t n_vertices,
+                      const int32_t **offsets, const int32_t **neighbours, const int32_t **edge_triangles,
+                      const uint8_t **vertex_flags, int64_t *n_entries, dp_mesh_adjacency_stats *stats);
+int dp_mesh_adjacency_device(dp_ctx *ctx, const int32_t *d_triangles, int64_t n_triangles, int64_t n_vertices,
+                             int32_t *d_offsets, int32_t *d_neighbours, int32_t *d_edge_triangles, int64_t entry_cap,
+                             uint8_t *d_vertex_flags, int64_t *n_entries, dp_mesh_adjacency_stats *stats, void *stream);
+int dp_mesh_smooth(dp_ctx *ctx, const dp_mesh_smooth_options *mso, const dp_mesh_vertex *vertices, int64_t n_vertices,
+                   const int32_t *triangles, int64_t n_triangles, const dp_mesh_vertex **vertices_out,
+                   dp_mesh_smooth_stats *stats);
+int dp_mesh_smooth_device(dp_ctx *ctx, const dp_mesh_smooth_options *mso, const dp_mesh_vertex *d_vertices,
+                          int64_t n_vertices, const int32_t *d_triangles, int64_t n_triangles,
+                          dp_mesh_vertex *d_vertices_out, dp_mesh_smooth_stats *stats, void *stream);
+int dp_mesh_normals(dp_ctx *ctx, const dp_mesh_vertex *vertices, int64_t n_vertices, const int32_t *triangles,
+                    int64_t n_triangles, const float **normals, dp_mesh_normals_stats *stats);
+int dp_mesh_normals_device(dp_ctx *ctx, const dp_mesh_vertex *d_vertices, int64_t n_vertices, const int32_t *d_triangles,
+                           int64_t n_triangles, float *d_normals, dp_mesh_normals_stats *stats, void *stream);
+
 /* ---- seed generation: Features::Matcher::GenerateSeeds ---
  * modules/features/matcher.cpp:18-43 with the default MatcherOptions
  * (matcher.h:21-32: ORB detector, kNN matcher, no direct epipolar matching,

@@ -55,6 +55,14 @@ void usage()
                  "                             dropped before the PLY is written -- dp_mesh_clean: those of\n"
                  "                             fewer than N triangles, of less than the share F, 0..1, of the\n"
                  "                             largest component's triangles, or not among the K largest)\n"
+                 "               [--mesh-smooth N [--mesh-smooth-lambda L] [--mesh-smooth-mu M]\n"
+                 "                [--mesh-smooth-free-boundary]] [--mesh-normals]\n"
+                 "                            (only with --mesh, after the clean-up, on the device: N =\n"
+                 "                             0..1000 Taubin iterations of the vertex positions --\n"
+                 "                             dp_mesh_smooth; L = the shrinking factor in (0, 1], default\n"
+                 "                             0.5; M = the inflating factor <= 0, default -0.53, 0 = plain\n"
+                 "                             Laplacian; boundary vertices stay unless freed;\n"
+                 "                             --mesh-normals: nx ny nz per vertex -- dp_mesh_normals)\n"
                  "       densify --synthetic V,W,H,KIND --write-scene DIR\n");
 }
 
@@ -104,6 +112,8 @@ bool set_flag(const std::string &o, Args &a)
     else if (o == "--filter") a.do_filter = true;
     else if (o == "--check-only") a.check_only = true;
     else if (o == "--depth-normals") a.depth_normals = true;
+    else if (o == "--mesh-smooth-free-boundary") a.mesh_smooth_free_boundary = true;
+    else if (o == "--mesh-normals") a.mesh_normals = true;
     else if (o == "--epipolar-matching") a.matcher.epipolar_matching = 1;
     else return false;
     return true;
@@ -216,6 +226,21 @@ Parse parse_args(int argc, char **argv, Args &a, std::string &error)
                 a.mesh_keep_largest = k;
             else
                 error = "--mesh-keep-largest expects 1..2147483647";
+        } else if (o == "--mesh-smooth") {
+            if (int_in_range(v, 0, 1000, k))
+                a.mesh_smooth = (int)k;
+            else
+                error = "--mesh-smooth expects 0..1000";
+        } else if (o == "--mesh-smooth-lambda") {
+            if (number_in_range(v, 0.0, 1.0, t) && (float)t > 0.0f)
+                a.mesh_smooth_lambda = t;
+            else
+                error = "--mesh-smooth-lambda expects a number in (0, 1]";
+        } else if (o == "--mesh-smooth-mu") {
+            if (number_in_range(v, -3.0e38, 0.0, t))
+                a.mesh_smooth_mu = t;
+            else
+                error = "--mesh-smooth-mu expects a finite number <= 0";
         } else if (o == "--exchange") {
             a.exchange_mode = v;
             if (one_of(v, {"auto", "rccl", "copy"}) < 0)
@@ -241,6 +266,15 @@ Parse parse_args(int argc, char **argv, Args &a, std::string &error)
     }
     if (a.synth.empty() && a.input.empty())
         return Parse::UsageError;
+    const bool smooth_detail = a.mesh_smooth_lambda != 0.0 || a.mesh_smooth_mu <= 0.0 || a.mesh_smooth_free_boundary;
+    if (a.mesh_path.empty() && (a.mesh_smooth >= 0 || smooth_detail || a.mesh_normals)) {
+        error = "--mesh-smooth, its options and --mesh-normals need --mesh";
+        return Parse::UsageError;
+    }
+    if (smooth_detail && a.mesh_smooth < 0) {
+        error = "--mesh-smooth-lambda, -mu and -free-boundary need --mesh-smooth";
+        return Parse::UsageError;
+    }
     if (a.iterations > 1)
         a.do_filter = true; // the filter is what tells the rounds apart
     if (a.replicate_below < 0)

@@ -42,6 +42,14 @@ struct Args {
     {
         return mesh_min_component >= 0 || mesh_min_component_frac >= 0.0 || mesh_keep_largest >= 0;
     }
+    // --mesh-smooth N [--mesh-smooth-lambda L] [--mesh-smooth-mu M]
+    // [--mesh-smooth-free-boundary]: dp_mesh_smooth on the (cleaned) mesh;
+    // --mesh-normals: dp_mesh_normals of the mesh as written.  Only with --mesh.
+    int mesh_smooth = -1;              // < 0: not given, no smoothing
+    double mesh_smooth_lambda = 0.0;   // 0: the library's default
+    double mesh_smooth_mu = 1.0;       // > 0: the library's default
+    bool mesh_smooth_free_boundary = false;
+    bool mesh_normals = false;
 
     Args();
 };

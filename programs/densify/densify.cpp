@@ -615,6 +615,53 @@ std::string write_mesh(dp_ctx *ctx, const Args &args, int32_t V, const std::vect
                       cs.clean_ms);
         cleaned = cbuf;
     }
+    // --mesh-smooth: the vertex positions relaxed where the mesh lies
+    // (dp_mesh_smooth_device; the triangles stay); --mesh-normals: the normals
+    // of the mesh as it will be written (dp_mesh_normals_device)
+    if (args.mesh_smooth >= 0) {
+        dp_mesh_smooth_options mso;
+        dp_default_mesh_smooth_options(&mso);
+        mso.iterations = args.mesh_smooth;
+        if (args.mesh_smooth_lambda != 0.0)
+            mso.lambda = (float)args.mesh_smooth_lambda;
+        if (args.mesh_smooth_mu <= 0.0)
+            mso.mu = (float)args.mesh_smooth_mu;
+        if (args.mesh_smooth_free_boundary)
+            mso.flags |= DP_SMOOTH_FREE_BOUNDARY;
+        dp_mesh_vertex *d_sverts = (dp_mesh_vertex *)m.bytes((size_t)vcap * sizeof(dp_mesh_vertex), "--mesh");
+        dp_mesh_smooth_stats ss;
+        check(ctx,
+              dp_mesh_smooth_device(ctx, &mso, nv ? d_verts : nullptr, nv, nt ? d_tris : nullptr, nt,
+                                    nv ? d_sverts : nullptr, &ss, nullptr),
+              "dp_mesh_smooth_device");
+        d_verts = d_sverts;
+        char sbuf[480];
+        std::snprintf(sbuf, sizeof sbuf,
+                      ", \"smooth\": {\"steps\": %lld, \"movable_vertices\": %lld, \"pinned_vertices\": %lld, "
+                      "\"isolated_vertices\": %lld, \"edges\": %lld, \"boundary_edges\": %lld, "
+                      "\"nonmanifold_edges\": %lld, \"max_valence\": %lld, \"adjacency_ms\": %.3f, \"smooth_ms\": %.3f}",
+                      (long long)ss.steps, (long long)ss.movable_vertices, (long long)ss.pinned_vertices,
+                      (long long)ss.isolated_vertices, (long long)ss.edges, (long long)ss.boundary_edges,
+                      (long long)ss.nonmanifold_edges, (long long)ss.max_valence, ss.adjacency_ms, ss.smooth_ms);
+        cleaned += sbuf;
+    }
+    std::vector<float> normals;
+    if (args.mesh_normals) {
+        float *d_normals = (float *)m.bytes((size_t)vcap * 3 * sizeof(float), "--mesh");
+        dp_mesh_normals_stats ns;
+        check(ctx,
+              dp_mesh_normals_device(ctx, nv ? d_verts : nullptr, nv, nt ? d_tris : nullptr, nt, nv ? d_normals : nullptr,
+                                     &ns, nullptr),
+              "dp_mesh_normals_device");
+        normals.resize((size_t)nv * 3);
+        if (nv > 0 && hipMemcpy(normals.data(), d_normals, normals.size() * sizeof(float), hipMemcpyDeviceToHost) !=
+                          hipSuccess)
+            throw std::runtime_error("--mesh: copy of the normals failed");
+        char nbuf[160];
+        std::snprintf(nbuf, sizeof nbuf, ", \"normals\": {\"zero_normals\": %lld, \"normals_ms\": %.3f}",
+                      (long long)ns.zero_normals, ns.normals_ms);
+        cleaned += nbuf;
+    }
     std::vector<dp_mesh_vertex> verts((size_t)nv);
     std::vector<int32_t> tris((size_t)nt * 3);
     if ((nv > 0 && hipMemcpy(verts.data(), d_verts, verts.size() * sizeof(dp_mesh_vertex), hipMemcpyDeviceToHost) !=
@@ -627,7 +674,7 @@ std::string write_mesh(dp_ctx *ctx, const Args &args, int32_t V, const std::vect
             out[i].pos[k] = verts[i].pos[k];
             out[i].rgb[k] = verts[i].rgb[k];
         }
-    dpio::write_mesh_ply(args.mesh_path, out, tris);
+    dpio::write_mesh_ply(args.mesh_path, out, tris, args.mesh_normals ? &normals : nullptr);
     char buf[400];
     std::snprintf(buf, sizeof buf,
                   ", \"mesh\": {\"vertices\": %lld, \"triangles\": %lld, \"ms\": %.3f, \"dim\": [%d, %d, %d], "

@@ -373,18 +373,29 @@ void write_ply(const std::string &path, const std::vector<CloudPoint> &pts)
         throw std::runtime_error("write failed: " + path);
 }
 
-void write_mesh_ply(const std::string &path, const std::vector<MeshPoint> &verts, const std::vector<int32_t> &tris)
+void write_mesh_ply(const std::string &path, const std::vector<MeshPoint> &verts, const std::vector<int32_t> &tris,
+                    const std::vector<float> *normals)
 {
+    if (normals && normals->size() != 3 * verts.size())
+        throw std::runtime_error("write_mesh_ply: three floats of normal per vertex");
     FILE *f = std::fopen(path.c_str(), "wb");
     if (!f)
         throw std::runtime_error("cannot write " + path);
     std::fprintf(f, "ply\nformat ascii 1.0\nelement vertex %zu\n", verts.size());
     std::fprintf(f, "property float x\nproperty float y\nproperty float z\n");
     std::fprintf(f, "property uchar red\nproperty uchar green\nproperty uchar blue\n");
+    if (normals)
+        std::fprintf(f, "property float nx\nproperty float ny\nproperty float nz\n");
     std::fprintf(f, "element face %zu\nproperty list uchar int vertex_indices\nend_header\n", tris.size() / 3);
-    for (const MeshPoint &p : verts)
-        std::fprintf(f, "%.9g %.9g %.9g %u %u %u\n", (double)p.pos[0], (double)p.pos[1], (double)p.pos[2],
+    for (size_t i = 0; i < verts.size(); ++i) {
+        const MeshPoint &p = verts[i];
+        std::fprintf(f, "%.9g %.9g %.9g %u %u %u", (double)p.pos[0], (double)p.pos[1], (double)p.pos[2],
                      (unsigned)p.rgb[0], (unsigned)p.rgb[1], (unsigned)p.rgb[2]);
+        if (normals)
+            std::fprintf(f, " %.9g %.9g %.9g", (double)(*normals)[3 * i], (double)(*normals)[3 * i + 1],
+                         (double)(*normals)[3 * i + 2]);
+        std::fprintf(f, "\n");
+    }
     for (size_t t = 0; t + 2 < tris.size(); t += 3)
         std::fprintf(f, "3 %d %d %d\n", (int)tris[t], (int)tris[t + 1], (int)tris[t + 2]);
     if (std::fclose(f) != 0)

@@ -81,8 +81,10 @@ struct MeshPoint {
 };
 
 // a triangle mesh as an ASCII PLY: vertex x y z (%.9g) red green blue, face
-// vertex_indices (list uchar int); tris holds three vertex numbers per triangle
-void write_mesh_ply(const std::string &path, const std::vector<MeshPoint> &verts, const std::vector<int32_t> &tris);
+// vertex_indices (list uchar int); tris holds three vertex numbers per triangle;
+// with normals (three floats per vertex) also nx ny nz (%.9g) after the colour
+void write_mesh_ply(const std::string &path, const std::vector<MeshPoint> &verts, const std::vector<int32_t> &tris,
+                    const std::vector<float> *normals = nullptr);
 
 // ---- image writers ----------------------------------------------------------
 // binary PPM (P6, RGB) of a BGR8 image
