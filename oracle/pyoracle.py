@@ -453,10 +453,15 @@ class GenerationEngine:
                 split |= sk == sk[c]
         tiles = int(np.count_nonzero(np.diff(sk))) + 1 if n else 0
         self._pstats = {"items": n, "world": world, "tiles": tiles, "split_items": int(split.sum())}
+        self._pkeys = key
         return own, False
 
     def densify_partition_stats(self):
         return dict(self._pstats)
+
+    def densify_partition_keys(self):
+        """the last partition's dense key per item (uint64)"""
+        return self._pkeys.copy()
 
     def densify_refine_items(self, g, items):
         items = np.asarray(items, dtype=np.int64)
