@@ -327,6 +327,30 @@ assert ctypes.sizeof(DpMeshSmoothOptions) == 20 and ctypes.sizeof(DpMeshAdjacenc
 assert ctypes.sizeof(DpMeshSmoothStats) == 120 and ctypes.sizeof(DpMeshNormalsStats) == 48
 
 
+DP_DECIMATE_MEAN, DP_DECIMATE_QUADRIC = 0, 1
+
+
+class DpMeshDecimateOptions(ctypes.Structure):
+    """dp_mesh_decimate_options: the cluster lattice and the placement of dp_mesh_decimate (include/densepoints.h)."""
+    _fields_ = [
+        ("origin", ctypes.c_float * 3),
+        ("cell", ctypes.c_float),
+        ("mode", ctypes.c_int32),
+        ("flags", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
+    ]
+
+
+class DpMeshDecimateStats(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int64) for n in (
+        "vertices_in", "triangles_in", "invalid_triangles", "degenerate_triangles", "unused_vertices", "clamped_vertices",
+        "clusters", "orphan_clusters", "max_cluster", "collapsed_triangles", "duplicate_triangles", "quadric_vertices",
+        "mean_vertices", "vertices_out", "triangles_out")] + [("decimate_ms", ctypes.c_double)]
+
+
+assert ctypes.sizeof(DpMeshDecimateOptions) == 28 and ctypes.sizeof(DpMeshDecimateStats) == 128
+
+
 class DpSynthConfig(ctypes.Structure):
     _fields_ = [
         ("n_views", ctypes.c_int32),
@@ -475,6 +499,10 @@ SIGNATURES = [
     ("dp_mesh_smooth_device", _I, [_P, _P, _P, ctypes.c_int64, _P, ctypes.c_int64, _P, _P, _P]),
     ("dp_mesh_normals", _I, [_P, _P, ctypes.c_int64, _P, ctypes.c_int64, _P, _P]),
     ("dp_mesh_normals_device", _I, [_P, _P, ctypes.c_int64, _P, ctypes.c_int64, _P, _P, _P]),
+    ("dp_default_mesh_decimate_options", None, [_P]),
+    ("dp_mesh_decimate", _I, [_P, _P, _P, ctypes.c_int64, _P, ctypes.c_int64, _P, _P, _P, _P, _P, _P, _P]),
+    ("dp_mesh_decimate_device", _I, [_P, _P, _P, ctypes.c_int64, _P, ctypes.c_int64, _P, ctypes.c_int64, _P, _P,
+                                     ctypes.c_int64, _P, _P, _P, _P, _P]),
     ("dp_last_kernel_ms", _I, [_P, _P]),
     ("dp_default_matcher_options", None, [_P]),
     ("dp_orb_pattern", _I, [_P]),

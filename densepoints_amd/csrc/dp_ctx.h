@@ -6,7 +6,8 @@
 // generation (their own state is dp_seedgen.h); the map stages --
 // dp_render.hip: maps; dp_fuse.hip: their fusion; dp_mapref.hip: their
 // refinement; dp_tsdf.hip: their volume and mesh; dp_meshclean.hip: the mesh's
-// components; dp_meshsmooth.hip: its adjacency, smoothing and normals -- each
+// components; dp_meshsmooth.hip: its adjacency, smoothing and normals;
+// dp_meshdecimate.hip: its simplification -- each
 // with its scratch as one named member of the context and
 // the host helpers they share at the end of this file).  Every member that
 // owns a device or pinned allocation or an event has an owning type
@@ -168,6 +169,30 @@ struct MeshSmoothScratch {
     Timer time[2]; // the adjacency; the steps or the normals
 };
 
+// dp_mesh_decimate.  The vertices: used flags, the cell keys with the vertex
+// numbers and their sorted copies (a cluster is a run of equal keys, its
+// members ascending), the cluster of every vertex, the first sorted position of
+// every cluster (K + 1 entries).  The triangles: the canonical-triple keys with
+// the triangle numbers, their sorted copies and the kept flags.  The clusters:
+// survivor flags and output numbers.  QUADRIC: the 3T (cluster, triangle) pairs
+// and their sorted copies.  Per-block counts and their scans (cluster heads,
+// survivors, kept triangles), the largest cluster; the host form's staged
+// inputs, device results and pinned results.
+struct MeshDecimateScratch {
+    DevBuf<uint8_t> used, tkeep, surv;
+    DevBuf<unsigned long long> vkeys, vkeys_sorted, tkeys, tkeys_sorted, bcount, boff;
+    DevBuf<int32_t> vidx, vidx_sorted, cid, cstart, tval[2], cout, maxval;
+    DevBuf<uint32_t> pkeys, pkeys_sorted;
+    DevBuf<int32_t> ptris, ptris_sorted;
+    StripedCounters count; // + K, the output vertex and triangle totals, the largest cluster
+    DevBuf<unsigned char> in;
+    DevBuf<int32_t> maps, tris;
+    DevBuf<dp_mesh_vertex> verts;
+    HostBuf<int32_t> htris;
+    HostBuf<dp_mesh_vertex> hverts;
+    Timer time;
+};
+
 } // namespace dpk
 
 struct SeedgenFree {
@@ -223,6 +248,7 @@ struct dp_ctx {
     dpk::TsdfScratch tsdf;
     dpk::CleanScratch clean;
     dpk::MeshSmoothScratch smooth;
+    dpk::MeshDecimateScratch decimate;
     HostBuf<dp_patch> result; // dp_densify / dp_densify_result output (pinned)
     // dp_densify_iterate: per iteration {evaluations, filter survivors} on the
     // device (read once, at the end) and the filters' timing events

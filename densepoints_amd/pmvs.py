@@ -39,6 +39,7 @@ __all__ = [
     "check_mapref_args",
     "check_tsdf_args",
     "check_mesh_clean_args",
+    "check_mesh_decimate_args",
     "check_mesh_smooth_args",
     "mesh_volume",
     "write_mesh_ply",
@@ -1051,6 +1052,61 @@ class Engine:
                                                _addr(d_normals), ctypes.byref(st) if stats else None, _addr(stream)))
         return _stats_dict(st) if stats else None
 
+    # ---- simplification (include/densepoints.h dp_mesh_decimate) ----
+    def mesh_decimate(self, vertices, triangles, cell, origin=(0.0, 0.0, 0.0), quadric: bool = False,
+                      maps: bool = False):
+        """dp_mesh_decimate: the mesh with the vertices of every cell (side
+        `cell`, the lattice anchored at `origin`) merged into one, at their mean
+        or (quadric=True) where the planes of the cell's triangles meet, without
+        the triangles that collapse or repeat.  Returns (vertices, triangles,
+        stats), and with maps=True also (vertex_map, triangle_map): the new index
+        of every input vertex and triangle, or -1."""
+        mdo = check_mesh_decimate_args(cell, origin, quadric)
+        verts = np.ascontiguousarray(vertices, dtype=N.MESH_VERTEX_DTYPE).reshape(-1)
+        tris = _mesh_triangles("mesh_decimate", triangles)
+        nv, nt = len(verts), len(tris)
+        _mesh_pairs("mesh_decimate", nt)
+        vm = np.full(nv, -1, np.int32) if maps else None
+        tm = np.full(nt, -1, np.int32) if maps else None
+        pv, pt, no, to, st = (ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_int64(), ctypes.c_int64(),
+                              N.DpMeshDecimateStats())
+        self._check(lib.dp_mesh_decimate(self._ctx, ctypes.byref(mdo), ptr(verts) if nv else None, nv,
+                                         ptr(tris) if nt else None, nt, ctypes.byref(pv), ctypes.byref(no),
+                                         ctypes.byref(pt), ctypes.byref(to), ptr(vm) if maps and nv else None,
+                                         ptr(tm) if maps and nt else None, ctypes.byref(st)))
+        vout = np.zeros(no.value, dtype=N.MESH_VERTEX_DTYPE)
+        tout = np.zeros((to.value, 3), dtype=np.int32)
+        if no.value:
+            ctypes.memmove(vout.ctypes.data, pv.value, vout.nbytes)
+        if to.value:
+            ctypes.memmove(tout.ctypes.data, pt.value, tout.nbytes)
+        out = (vout, tout, _stats_dict(st))
+        return out + (vm, tm) if maps else out
+
+    def mesh_decimate_device(self, d_vertices, n_vertices: int, d_triangles, n_triangles: int, d_vertices_out,
+                             vertex_cap: int, d_triangles_out, triangle_cap: int, cell, origin=(0.0, 0.0, 0.0),
+                             quadric: bool = False, d_vertex_map=None, d_triangle_map=None, stats: bool = True,
+                             stream: int | None = None):
+        """dp_mesh_decimate_device: a device mesh (addresses) into at most
+        vertex_cap records at d_vertices_out and triangle_cap triples at
+        d_triangles_out, and the maps (None = not wanted).  Queued on `stream`;
+        one wait.  Returns (the full vertex count, the full triangle count --
+        above a cap: an overflow --, stats, or None with stats=False)."""
+        mdo = check_mesh_decimate_args(cell, origin, quadric)
+        nv, nt = _mesh_count("mesh_decimate_device", n_vertices), _mesh_count("mesh_decimate_device", n_triangles)
+        _mesh_pairs("mesh_decimate_device", nt)
+        _mesh_cap("mesh_decimate_device", vertex_cap, d_vertices_out)
+        _mesh_cap("mesh_decimate_device", triangle_cap, d_triangles_out)
+        if (nv and not d_vertices) or (nt and not d_triangles):
+            raise ValueError("mesh_decimate_device: the vertices and triangles must be given")
+        no, to, st = ctypes.c_int64(), ctypes.c_int64(), N.DpMeshDecimateStats()
+        self._check(lib.dp_mesh_decimate_device(self._ctx, ctypes.byref(mdo), _addr(d_vertices), nv, _addr(d_triangles),
+                                                nt, _addr(d_vertices_out), int(vertex_cap), ctypes.byref(no),
+                                                _addr(d_triangles_out), int(triangle_cap), ctypes.byref(to),
+                                                _addr(d_vertex_map), _addr(d_triangle_map),
+                                                ctypes.byref(st) if stats else None, _addr(stream)))
+        return int(no.value), int(to.value), _stats_dict(st) if stats else None
+
 
 def _stats_dict(st) -> dict:
     return {name: getattr(st, name) for name, _ in st._fields_}
@@ -1059,6 +1115,54 @@ def _stats_dict(st) -> dict:
 def _mesh_entries(who: str, nt: int) -> None:
     if 6 * nt > 2**31 - 1:
         raise ValueError("%s: 6 * n_triangles must be <= 2^31 - 1" % who)
+
+
+def _mesh_pairs(who: str, nt: int) -> None:
+    if 3 * nt > 2**31 - 1:
+        raise ValueError("%s: 3 * n_triangles must be <= 2^31 - 1" % who)
+
+
+def check_mesh_decimate_args(cell, origin=(0.0, 0.0, 0.0), quadric=False):
+    """Argument validation of Engine.mesh_decimate[_device] (the limits of
+    dp_mesh_decimate_options, raised as ValueError before any device call);
+    returns the dp_mesh_decimate_options.  The values are judged as the float32
+    the struct holds."""
+    def real(x):
+        return not isinstance(x, bool) and isinstance(x, (int, float, np.integer, np.floating))
+
+    with np.errstate(over="ignore"):
+        if not real(cell) or not (np.isfinite(np.float32(cell)) and np.float32(cell) > 0):
+            raise ValueError("mesh_decimate: cell must be finite and > 0")
+        try:
+            org = tuple(origin)
+        except TypeError:
+            org = ()
+        if len(org) != 3 or not all(real(o) and np.isfinite(np.float32(o)) for o in org):
+            raise ValueError("mesh_decimate: origin must be three finite numbers")
+    if not isinstance(quadric, (bool, np.bool_)):
+        raise ValueError("mesh_decimate: quadric must be a bool")
+    return N.DpMeshDecimateOptions((ctypes.c_float * 3)(*(float(o) for o in org)), float(cell),
+                                   N.DP_DECIMATE_QUADRIC if quadric else N.DP_DECIMATE_MEAN, 0, 0)
+
+
+def decimate_cell(decimate, voxel) -> dict:
+    """PMVS.mesh's `decimate` dict as Engine.mesh_decimate's options without the
+    origin: `cell` in world units, or `factor` times the volume's voxel (the
+    float32 the volume holds; the product rounded to float32 once), and
+    optionally `quadric`."""
+    d = dict(decimate)
+    unknown = set(d) - {"cell", "factor", "quadric", "origin"}
+    if unknown:
+        raise ValueError("mesh: unknown decimate options %s" % sorted(unknown))
+    if ("cell" in d) == ("factor" in d):
+        raise ValueError("mesh: decimate takes either cell or factor")
+    if "factor" in d:
+        f = d.pop("factor")
+        if isinstance(f, bool) or not isinstance(f, (int, float, np.integer, np.floating)) or not (np.isfinite(f) and f > 0):
+            raise ValueError("mesh: decimate's factor must be finite and > 0")
+        with np.errstate(over="ignore"):
+            d["cell"] = float(np.float32(float(f) * float(np.float32(voxel))))
+    return d
 
 
 def check_mesh_smooth_args(iterations=10, lam=0.5, mu=-0.53, free_boundary=False):
@@ -1507,7 +1611,7 @@ class PMVS:
         return out
 
     def mesh(self, refine: int = 0, voxel=None, dim: int = 256, trunc=None, min_weight: int = 2, clean=None,
-             smooth=None, normals: bool = False, **kw):
+             smooth=None, normals: bool = False, decimate=None, **kw):
         """The last run()'s result as a triangle mesh: (vertices as a
         MESH_VERTEX_DTYPE array, triangles as n x 3 int32).  The depth maps of
         depth_maps(refine, **kw) -- kw: its render and refinement options --
@@ -1520,11 +1624,14 @@ class PMVS:
         components; None (the default) leaves the mesh as extracted.  smooth: a
         dict of Engine.mesh_smooth's options (iterations, lam, mu,
         free_boundary) relaxes the vertex positions after the clean-up; None
-        leaves them.  normals=True returns (vertices, triangles, normals), the
+        leaves them.  decimate: a dict with either cell (world units) or factor
+        (cell = factor x the volume's voxel), and optionally quadric and origin
+        (default: the volume's origin), simplifies the mesh after the smoothing
+        (Engine.mesh_decimate); None leaves it.  normals=True returns (vertices, triangles, normals), the
         normals (Engine.mesh_normals, n x 3 float32) of the mesh as returned.
         The volume and the statistics of the calls are left in
-        self.stats["mesh"] (the later stages' under "clean", "smooth" and
-        "normals")."""
+        self.stats["mesh"] (the later stages' under "clean", "smooth",
+        "decimate" and "normals")."""
         if not self._ran:
             raise ValueError("mesh: call run() first")
         if clean is not None:
@@ -1533,6 +1640,9 @@ class PMVS:
             check_mesh_smooth_args(**dict(smooth))
         refine, mkw, kw = split_refine_args("mesh", refine, kw)
         vol = mesh_volume(self.patches["pos"], voxel, dim, trunc)
+        if decimate is not None:
+            decimate = dict(dict(origin=vol["origin"]), **decimate_cell(decimate, vol["voxel"]))
+            check_mesh_decimate_args(**decimate)
         check_tsdf_args(max(len(self.views), 1), kw.get("views"), min_weight=min_weight, **vol)
         with Engine(self.options, self.device) as eng:
             eng.set_views(self.views)
@@ -1546,6 +1656,8 @@ class PMVS:
                 verts, tris, cst = eng.mesh_clean(verts, tris, **dict(clean))
             if smooth is not None:
                 verts, sst = eng.mesh_smooth(verts, tris, **dict(smooth))
+            if decimate is not None:
+                verts, tris, dst = eng.mesh_decimate(verts, tris, **decimate)
             if normals:
                 nrm, nst = eng.mesh_normals(verts, tris)
         self.stats["mesh"] = dict(vol, min_weight=int(min_weight), integrate=volume["stats"], mesh=mst)
@@ -1553,6 +1665,8 @@ class PMVS:
             self.stats["mesh"]["clean"] = cst
         if smooth is not None:
             self.stats["mesh"]["smooth"] = sst
+        if decimate is not None:
+            self.stats["mesh"]["decimate"] = dst
         if normals:
             self.stats["mesh"]["normals"] = nst
             return verts, tris, nrm

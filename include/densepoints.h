@@ -1073,6 +1073,118 @@ int dp_mesh_normals(dp_ctx *ctx, const dp_mesh_vertex *vertices, int64_t n_verti
 int dp_mesh_normals_device(dp_ctx *ctx, const dp_mesh_vertex *d_vertices, int64_t n_vertices, const int32_t *d_triangles,
                            int64_t n_triangles, float *d_normals, dp_mesh_normals_stats *stats, void *stream);
 
+/* ---- mesh simplification: vertex clustering on a uniform grid -------------------
+ * No reference counterpart.  The mesh of dp_tsdf_mesh is never coarser than the
+ * TSDF lattice, whatever the surface's detail; this merges the vertices of every
+ * cell of a coarser lattice into one (Rossignac-Borrel), placed at their mean or
+ * (DP_DECIMATE_QUADRIC) where the planes of the cell's triangles meet (Lindstrom
+ * 2000), and drops the triangles that collapse or repeat.  No view is read.  The
+ * result does not depend on the order in which lanes or blocks run: clusters and
+ * triangles are sorted sets, every float sum runs over a sorted run in a fixed
+ * order, and there is no floating-point atomic.  Every fp64 expression below is
+ * one IEEE rounding per operation (no contraction), dvdiv is the IEEE-correct
+ * fp64 quotient, (float) and (double) are the IEEE conversions.
+ *
+ * Definitions.  VALID, DEGENERATE and PROPER triangles are as in the smoothing
+ * section; only proper triangles take part, invalid and degenerate ones are
+ * counted (invalid_triangles, degenerate_triangles), and no index is used as an
+ * address before its range check.  A vertex is USED iff a proper triangle names
+ * it (unused_vertices counts the others).
+ * Cell of a position p (also the quadric's acceptance test below), per axis c:
+ *   q = floor(dvdiv((double)p[c] - (double)origin[c], (double)cell))
+ *   k_c = -2^20 if !(q >= -2^20) (a NaN too), 2^20 - 1 if q > 2^20 - 1, else (int64)q
+ * A used vertex with any axis changed by these bounds counts in clamped_vertices.
+ * Cells are ordered by (k_z, k_y, k_x) ascending.
+ * Clusters.  A cluster is the set of used vertices of one cell, its members taken
+ * in ascending vertex index; clusters are numbered 0..K-1 by ascending cell;
+ * clusters = K, max_cluster = the largest member count.
+ * Triangles.  A proper triangle (a, b, c) maps to the clusters (A, B, C) of its
+ * indices.  It is COLLAPSED iff two of them are equal: dropped, counted in
+ * collapsed_triangles.  Otherwise its canonical triple is the rotation of
+ * (A, B, C) that puts the smallest first (the cyclic order, and so the
+ * orientation, is kept), and it is a DUPLICATE iff a non-collapsed triangle of
+ * lower index has the same canonical triple: dropped, counted in
+ * duplicate_triangles.  Oppositely wound triples are different triples: both
+ * stay.  The kept triangles come out in input order, their indices in their
+ * positions (not rotated), each replaced by its cluster's output number; so
+ * dp_tsdf_mesh's winding, and the outward normals, survive.
+ * Output vertices.  A cluster SURVIVES iff a kept triangle names it; the others
+ * count in orphan_clusters, and the output never has an unused vertex.
+ * Survivors are numbered by ascending cluster number.  vertex_map[v] = the output
+ * number of v's cluster, -1 if v is unused or its cluster an orphan;
+ * triangle_map[t] = the output index, -1 for invalid, degenerate, collapsed and
+ * duplicate triangles.
+ * Output record of a surviving cluster with members v_1 < ... < v_n:
+ *   mean, per axis c:    S = 0.0;  for j ascending: S = S + (double)pos_{v_j}[c];  m_c = dvdiv(S, (double)n)
+ *   colour, per channel: R = the integer sum of the members' bytes; rgb = (2R + n) / (2n) in
+ *                        integers (exact, so order-free); pad = 0
+ *   DP_DECIMATE_MEAN:    pos_c = (float)m_c; the vertex counts in mean_vertices
+ *   DP_DECIMATE_QUADRIC: walk the proper triangles that name at least one member
+ *   (collapsed and duplicate ones included, each once per cluster) in ascending
+ *   triangle index, with widened positions p0, p1, p2; the nine sums start at 0.0:
+ *     e1 = p1 - p0;  e2 = p2 - p0;  g = (e1y*e2z - e1z*e2y, e1z*e2x - e1x*e2z, e1x*e2y - e1y*e2x)
+ *     r = p0 - m;    d = (g.x*r.x + g.y*r.y) + g.z*r.z
+ *     Axx += g.x*g.x; Axy += g.x*g.y; Axz += g.x*g.z; Ayy += g.y*g.y; Ayz += g.y*g.z; Azz += g.z*g.z
+ *     bx += d*g.x;  by += d*g.y;  bz += d*g.z
+ *   then
+ *     c00 = Ayy*Azz - Ayz*Ayz;  c01 = Axz*Ayz - Axy*Azz;  c02 = Axy*Ayz - Axz*Ayy
+ *     c11 = Axx*Azz - Axz*Axz;  c12 = Axy*Axz - Axx*Ayz;  c22 = Axx*Ayy - Axy*Axy
+ *     det = (Axx*c00 + Axy*c01) + Axz*c02;  t = dvdiv((Axx + Ayy) + Azz, 3.0)
+ *     solvable iff det is finite and det > DP_DECIMATE_DET_EPS * ((t*t)*t)
+ *     x = (dvdiv((c00*bx + c01*by) + c02*bz, det), dvdiv((c01*bx + c11*by) + c12*bz, det),
+ *          dvdiv((c02*bx + c12*by) + c22*bz, det));  cand_c = (float)(m_c + x_c)
+ *   pos = cand iff the cluster is solvable, all three cand_c are finite and the
+ *   cell of cand (the formula above, bounds included) is the cluster's cell; the
+ *   vertex then counts in quadric_vertices.  Otherwise pos_c = (float)m_c and the
+ *   vertex counts in mean_vertices: flat and crease clusters are unsolvable by
+ *   construction and take the mean, which is intended.
+ * quadric_vertices + mean_vertices = vertices_out.  Positions are expected to be
+ * finite.  Statistics: the counts named above, vertices_in, triangles_in,
+ * vertices_out, triangles_out; decimate_ms = device time of the call's kernels.
+ *
+ * Host and device forms follow dp_mesh_clean's: host arrays, vertex_map /
+ * triangle_map the caller's (may be NULL), *vertices_out and *triangles_out
+ * context-owned, valid until the next dp_mesh_decimate or destroy and NULL when
+ * their count is 0; device arrays, one cap per output buffer, the first
+ * min(cap, count) records written and nothing beyond them, the full counts
+ * returned, everything queued on `stream` (NULL = the context's) and one wait,
+ * for the counts (with stats NULL too).
+ * Errors (DP_E_ARG), counts before pointers: the clean-up section's list (counts,
+ * NULL inputs, caps, an output pointer equal to an input pointer, a NULL count
+ * or, host form, result pointer); 3 * n_triangles > 2^31 - 1 (the (cluster,
+ * triangle) pairs are counted in int32); opts NULL; cell not finite or not > 0; a
+ * non-finite origin; mode outside {0, 1}; flags != 0.  n_triangles = 0 or
+ * n_vertices = 0 is legal and yields empty results. */
+#define DP_DECIMATE_MEAN 0
+#define DP_DECIMATE_QUADRIC 1
+#define DP_DECIMATE_DET_EPS 1e-6   /* design choice, nobody has tuned it */
+typedef struct dp_mesh_decimate_options {
+    float origin[3];   /* 0,0,0  anchor of the cluster lattice (finite)                       */
+    float cell;        /* 0      cluster cell side, world units: must be set, > 0, finite     */
+    int32_t mode;      /* DP_DECIMATE_MEAN                                                    */
+    int32_t flags;     /* none defined; non-zero is DP_E_ARG                                  */
+    int32_t reserved;
+} dp_mesh_decimate_options;
+typedef struct dp_mesh_decimate_stats {
+    int64_t vertices_in, triangles_in, invalid_triangles, degenerate_triangles, unused_vertices,
+        clamped_vertices, clusters, orphan_clusters, max_cluster, collapsed_triangles, duplicate_triangles,
+        quadric_vertices, mean_vertices, vertices_out, triangles_out;
+    double decimate_ms;
+} dp_mesh_decimate_stats;
+
+void dp_default_mesh_decimate_options(dp_mesh_decimate_options *mdo);
+int dp_mesh_decimate(dp_ctx *ctx, const dp_mesh_decimate_options *opts, const dp_mesh_vertex *vertices,
+                     int64_t n_vertices, const int32_t *triangles, int64_t n_triangles,
+                     const dp_mesh_vertex **vertices_out, int64_t *n_vertices_out, const int32_t **triangles_out,
+                     int64_t *n_triangles_out, int32_t *vertex_map, int32_t *triangle_map,
+                     dp_mesh_decimate_stats *stats);
+int dp_mesh_decimate_device(dp_ctx *ctx, const dp_mesh_decimate_options *opts, const dp_mesh_vertex *d_vertices,
+                            int64_t n_vertices, const int32_t *d_triangles, int64_t n_triangles,
+                            dp_mesh_vertex *d_vertices_out, int64_t vertex_cap, int64_t *n_vertices_out,
+                            int32_t *d_triangles_out, int64_t triangle_cap, int64_t *n_triangles_out,
+                            int32_t *d_vertex_map, int32_t *d_triangle_map, dp_mesh_decimate_stats *stats,
+                            void *stream);
+
 /* ---- seed generation: Features::Matcher::GenerateSeeds ---
  * modules/features/matcher.cpp:18-43 with the default MatcherOptions
  * (matcher.h:21-32: ORB detector, kNN matcher, no direct epipolar matching,

@@ -63,6 +63,12 @@ void usage()
                  "                             0.5; M = the inflating factor <= 0, default -0.53, 0 = plain\n"
                  "                             Laplacian; boundary vertices stay unless freed;\n"
                  "                             --mesh-normals: nx ny nz per vertex -- dp_mesh_normals)\n"
+                 "               [--mesh-decimate F [--mesh-decimate-quadric]]\n"
+                 "                            (only with --mesh, between the smoothing and the normals, on\n"
+                 "                             the device: the vertices of every cell of side F voxels, F > 0,\n"
+                 "                             merged into one at their mean -- or, with -quadric, where the\n"
+                 "                             planes of the cell's triangles meet -- and the triangles that\n"
+                 "                             collapse or repeat dropped -- dp_mesh_decimate)\n"
                  "       densify --synthetic V,W,H,KIND --write-scene DIR\n");
 }
 
@@ -114,6 +120,7 @@ bool set_flag(const std::string &o, Args &a)
     else if (o == "--depth-normals") a.depth_normals = true;
     else if (o == "--mesh-smooth-free-boundary") a.mesh_smooth_free_boundary = true;
     else if (o == "--mesh-normals") a.mesh_normals = true;
+    else if (o == "--mesh-decimate-quadric") a.mesh_decimate_quadric = true;
     else if (o == "--epipolar-matching") a.matcher.epipolar_matching = 1;
     else return false;
     return true;
@@ -241,6 +248,11 @@ Parse parse_args(int argc, char **argv, Args &a, std::string &error)
                 a.mesh_smooth_mu = t;
             else
                 error = "--mesh-smooth-mu expects a finite number <= 0";
+        } else if (o == "--mesh-decimate") {
+            if (number_in_range(v, 0.0, 3.0e38, t) && t > 0.0)
+                a.mesh_decimate = t;
+            else
+                error = "--mesh-decimate expects a finite number > 0";
         } else if (o == "--exchange") {
             a.exchange_mode = v;
             if (one_of(v, {"auto", "rccl", "copy"}) < 0)
@@ -273,6 +285,14 @@ Parse parse_args(int argc, char **argv, Args &a, std::string &error)
     }
     if (smooth_detail && a.mesh_smooth < 0) {
         error = "--mesh-smooth-lambda, -mu and -free-boundary need --mesh-smooth";
+        return Parse::UsageError;
+    }
+    if (a.mesh_path.empty() && (a.mesh_decimate > 0.0 || a.mesh_decimate_quadric)) {
+        error = "--mesh-decimate and --mesh-decimate-quadric need --mesh";
+        return Parse::UsageError;
+    }
+    if (a.mesh_decimate_quadric && !(a.mesh_decimate > 0.0)) {
+        error = "--mesh-decimate-quadric needs --mesh-decimate";
         return Parse::UsageError;
     }
     if (a.iterations > 1)

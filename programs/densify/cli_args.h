@@ -50,6 +50,11 @@ struct Args {
     double mesh_smooth_mu = 1.0;       // > 0: the library's default
     bool mesh_smooth_free_boundary = false;
     bool mesh_normals = false;
+    // --mesh-decimate F [--mesh-decimate-quadric]: dp_mesh_decimate on the
+    // (cleaned, smoothed) mesh, cluster cell = F x the volume's voxel, the
+    // lattice anchored at the volume's origin.  Only with --mesh.
+    double mesh_decimate = 0.0; // 0: not given, no simplification
+    bool mesh_decimate_quadric = false;
 
     Args();
 };

@@ -645,6 +645,47 @@ std::string write_mesh(dp_ctx *ctx, const Args &args, int32_t V, const std::vect
                       (long long)ss.nonmanifold_edges, (long long)ss.max_valence, ss.adjacency_ms, ss.smooth_ms);
         cleaned += sbuf;
     }
+    // --mesh-decimate: the vertices of every cell of F voxels merged where the
+    // mesh lies (dp_mesh_decimate_device; the result is no larger than its input)
+    std::string decimated;
+    if (args.mesh_decimate > 0.0) {
+        dp_mesh_decimate_options mdo;
+        dp_default_mesh_decimate_options(&mdo);
+        for (int a = 0; a < 3; ++a)
+            mdo.origin[a] = to.origin[a];
+        mdo.cell = (float)(args.mesh_decimate * (double)to.voxel);
+        mdo.mode = args.mesh_decimate_quadric ? DP_DECIMATE_QUADRIC : DP_DECIMATE_MEAN;
+        dp_mesh_vertex *d_dverts = (dp_mesh_vertex *)m.bytes((size_t)vcap * sizeof(dp_mesh_vertex), "--mesh");
+        int32_t *d_dtris = (int32_t *)m.bytes((size_t)tcap * 3 * sizeof(int32_t), "--mesh");
+        dp_mesh_decimate_stats ds;
+        int64_t dv = 0, dt = 0;
+        check(ctx,
+              dp_mesh_decimate_device(ctx, &mdo, nv ? d_verts : nullptr, nv, nt ? d_tris : nullptr, nt,
+                                      vcap ? d_dverts : nullptr, vcap, &dv, tcap ? d_dtris : nullptr, tcap, &dt, nullptr,
+                                      nullptr, &ds, nullptr),
+              "dp_mesh_decimate_device");
+        if (dv > nv || dt > nt)
+            throw std::runtime_error("--mesh: the simplification returned more than it was given");
+        nv = dv;
+        nt = dt;
+        d_verts = d_dverts;
+        d_tris = d_dtris;
+        char dbuf[800];
+        std::snprintf(dbuf, sizeof dbuf,
+                      ", \"mesh_decimate\": {\"cell\": %.9g, \"quadric\": %s, \"vertices_in\": %lld, "
+                      "\"triangles_in\": %lld, \"invalid_triangles\": %lld, \"degenerate_triangles\": %lld, "
+                      "\"unused_vertices\": %lld, \"clamped_vertices\": %lld, \"clusters\": %lld, "
+                      "\"orphan_clusters\": %lld, \"max_cluster\": %lld, \"collapsed_triangles\": %lld, "
+                      "\"duplicate_triangles\": %lld, \"quadric_vertices\": %lld, \"mean_vertices\": %lld, "
+                      "\"vertices_out\": %lld, \"triangles_out\": %lld, \"decimate_ms\": %.3f}",
+                      (double)mdo.cell, args.mesh_decimate_quadric ? "true" : "false", (long long)ds.vertices_in,
+                      (long long)ds.triangles_in, (long long)ds.invalid_triangles, (long long)ds.degenerate_triangles,
+                      (long long)ds.unused_vertices, (long long)ds.clamped_vertices, (long long)ds.clusters,
+                      (long long)ds.orphan_clusters, (long long)ds.max_cluster, (long long)ds.collapsed_triangles,
+                      (long long)ds.duplicate_triangles, (long long)ds.quadric_vertices, (long long)ds.mean_vertices,
+                      (long long)ds.vertices_out, (long long)ds.triangles_out, ds.decimate_ms);
+        decimated = dbuf;
+    }
     std::vector<float> normals;
     if (args.mesh_normals) {
         float *d_normals = (float *)m.bytes((size_t)vcap * 3 * sizeof(float), "--mesh");
@@ -683,7 +724,7 @@ std::string write_mesh(dp_ctx *ctx, const Args &args, int32_t V, const std::vect
                   (long long)nv, (long long)nt, ts.integrate_ms + ms.mesh_ms, to.dim[0], to.dim[1], to.dim[2],
                   (double)to.voxel, (double)to.trunc, (long long)ts.observed_voxels, (long long)ms.active_cells,
                   ts.integrate_ms, ms.mesh_ms);
-    return m.refined + buf + cleaned + "}";
+    return m.refined + buf + cleaned + "}" + decimated;
 }
 
 using Clock = std::chrono::steady_clock;
