@@ -32,6 +32,7 @@ from .pmvs import (  # noqa: F401
     check_mapref_args,
     check_mesh_clean_args,
     check_mesh_decimate_args,
+    check_mesh_render_args,
     check_mesh_smooth_args,
     check_tsdf_args,
     empty_patches,

@@ -351,6 +351,23 @@ class DpMeshDecimateStats(ctypes.Structure):
 assert ctypes.sizeof(DpMeshDecimateOptions) == 28 and ctypes.sizeof(DpMeshDecimateStats) == 128
 
 
+DP_MESH_RENDER_CULL_BACK = 1
+
+
+class DpMeshRenderOptions(ctypes.Structure):
+    """dp_mesh_render_options: the flags of dp_mesh_render (include/densepoints.h)."""
+    _fields_ = [("flags", ctypes.c_int32)]
+
+
+class DpMeshRenderStats(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int64) for n in (
+        "triangles", "invalid_triangles", "pairs", "clipped_pairs", "culled_pairs", "pixel_tests",
+        "covered_pixels")] + [("render_ms", ctypes.c_double)]
+
+
+assert ctypes.sizeof(DpMeshRenderOptions) == 4 and ctypes.sizeof(DpMeshRenderStats) == 64
+
+
 class DpSynthConfig(ctypes.Structure):
     _fields_ = [
         ("n_views", ctypes.c_int32),
@@ -503,6 +520,9 @@ SIGNATURES = [
     ("dp_mesh_decimate", _I, [_P, _P, _P, ctypes.c_int64, _P, ctypes.c_int64, _P, _P, _P, _P, _P, _P, _P]),
     ("dp_mesh_decimate_device", _I, [_P, _P, _P, ctypes.c_int64, _P, ctypes.c_int64, _P, ctypes.c_int64, _P, _P,
                                      ctypes.c_int64, _P, _P, _P, _P, _P]),
+    ("dp_default_mesh_render_options", None, [_P]),
+    ("dp_mesh_render", _I, [_P, _P, ctypes.c_int64, _P, ctypes.c_int64, _P, _I, _P, _P, _P, _P, _P]),
+    ("dp_mesh_render_device", _I, [_P, _P, ctypes.c_int64, _P, ctypes.c_int64, _P, _I, _P, _P, _P, _P, _P, _P]),
     ("dp_last_kernel_ms", _I, [_P, _P]),
     ("dp_default_matcher_options", None, [_P]),
     ("dp_orb_pattern", _I, [_P]),

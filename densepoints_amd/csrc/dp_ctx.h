@@ -7,7 +7,7 @@
 // dp_render.hip: maps; dp_fuse.hip: their fusion; dp_mapref.hip: their
 // refinement; dp_tsdf.hip: their volume and mesh; dp_meshclean.hip: the mesh's
 // components; dp_meshsmooth.hip: its adjacency, smoothing and normals;
-// dp_meshdecimate.hip: its simplification -- each
+// dp_meshdecimate.hip: its simplification; dp_meshrender.hip: its maps -- each
 // with its scratch as one named member of the context and
 // the host helpers they share at the end of this file).  Every member that
 // owns a device or pinned allocation or an event has an owning type
@@ -193,6 +193,17 @@ struct MeshDecimateScratch {
     Timer time;
 };
 
+// dp_mesh_render: the pair list, the counters (the statistics, then one packed
+// pair / band counter per chunk), the slot table; the host form's staged mesh
+// and planes.  The z-buffer is the context's pix64.
+struct MeshRenderScratch {
+    DevBuf<unsigned long long> count;
+    DevBuf<MeshRenderPair> pairs;
+    DevBuf<MeshRenderSlot> slots;
+    DevBuf<unsigned char> in, out;
+    Timer time;
+};
+
 } // namespace dpk
 
 struct SeedgenFree {
@@ -237,7 +248,7 @@ struct dp_ctx {
     DevBuf<dp_patch> f_pat;
     // Buffers shared on purpose by stages whose calls never overlap on a context:
     //   pix64          8 B per pixel of the requested views: dp_render_maps'
-    //                  z-buffer and dp_fuse_maps' masks
+    //                  and dp_mesh_render's z-buffer and dp_fuse_maps' masks
     //   f_rho          the filter's rho, which is also dp_render_maps' splat radius
     //   f_pat, f_keep  the filter's staging of host patches and flags, which the
     //                  host form of dp_render_maps stages its own in
@@ -249,6 +260,7 @@ struct dp_ctx {
     dpk::CleanScratch clean;
     dpk::MeshSmoothScratch smooth;
     dpk::MeshDecimateScratch decimate;
+    dpk::MeshRenderScratch meshrender;
     HostBuf<dp_patch> result; // dp_densify / dp_densify_result output (pinned)
     // dp_densify_iterate: per iteration {evaluations, filter survivors} on the
     // device (read once, at the end) and the filters' timing events

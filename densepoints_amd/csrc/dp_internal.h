@@ -301,6 +301,23 @@ hipError_t launch_render_pairs(const RenderArgs &a, int64_t i0, int64_t i1, int 
 hipError_t launch_render_raster(const RenderArgs &a, int chunk, hipStream_t s);
 hipError_t launch_render_resolve(const RenderArgs &a, int max_pixels, hipStream_t s);
 
+// depth / triangle-index / normal maps of a mesh (dp_meshrender.hip; spec in
+// include/densepoints.h, dp_mesh_render; its arguments stay in that file)
+struct MeshRenderSlot { // one requested view
+    int32_t view, W, H, pad;
+    int64_t zoff; // first z-buffer word of the view
+    double m;     // determinant of the left 3x3 of its projection
+    float *depth; // output planes, any may be null
+    int32_t *index;
+    float *normal;
+};
+struct MeshRenderPair { // one (triangle, view) pair, its uniform fp64 done once
+    double r[9], D;         // the three edge rows, det [h_0 h_1 h_2]
+    int64_t first;          // number of its first band within the chunk
+    int32_t x0, x1, y0, y1; // clipped box, inclusive
+    int32_t slot, index;
+};
+
 // depth-map fusion (dp_fuse.hip; spec in include/densepoints.h, dp_fuse_maps)
 struct FuseView { // one requested view; indexed wave-uniformly (scalar loads)
     ViewInv inv;

@@ -40,6 +40,7 @@ __all__ = [
     "check_tsdf_args",
     "check_mesh_clean_args",
     "check_mesh_decimate_args",
+    "check_mesh_render_args",
     "check_mesh_smooth_args",
     "mesh_volume",
     "write_mesh_ply",
@@ -1107,6 +1108,60 @@ class Engine:
                                                 ctypes.byref(st) if stats else None, _addr(stream)))
         return int(no.value), int(to.value), _stats_dict(st) if stats else None
 
+    # ---- per-view maps of a mesh (include/densepoints.h dp_mesh_render) ----
+    def mesh_render(self, vertices, triangles, views=None, cull_back: bool = False, normals: bool = False) -> dict:
+        """dp_mesh_render: every triangle rasterised into `views` (None = all) at
+        the current level, nearest triangle per pixel; cull_back skips the
+        triangles that do not face the view.  Returns {"views", "depth" (f32, 0 =
+        empty), "index" (int32 triangle, -1 = empty), "normal" (the winner's unit
+        face normal) when asked for, "stats"}, each map a list of H x W (x 3)
+        arrays in the order of "views"."""
+        verts = np.ascontiguousarray(vertices, dtype=N.MESH_VERTEX_DTYPE).reshape(-1)
+        tris = _mesh_triangles("mesh_render", triangles)
+        nv, nt = len(verts), len(tris)
+        mro, vid = check_mesh_render_args(nv, nt, self.num_views(), views, cull_back)
+        sizes = self.view_sizes(vid)
+        out = {"views": [int(v) for v in vid],
+               "depth": [np.zeros((h, w), np.float32) for w, h in sizes],
+               "index": [np.zeros((h, w), np.int32) for w, h in sizes]}
+        if normals:
+            out["normal"] = [np.zeros((h, w, 3), np.float32) for w, h in sizes]
+
+        def table(key):
+            return (ctypes.c_void_p * len(vid))(*[a.ctypes.data for a in out[key]]) if key in out else None
+
+        st = N.DpMeshRenderStats()
+        self._check(lib.dp_mesh_render(self._ctx, ptr(verts) if nv else None, nv, ptr(tris) if nt else None, nt,
+                                       ptr(vid), len(vid), ctypes.byref(mro), table("depth"), table("index"),
+                                       table("normal"), ctypes.byref(st)))
+        out["stats"] = _stats_dict(st)
+        return out
+
+    def mesh_render_device(self, d_vertices, n_vertices: int, d_triangles, n_triangles: int, views, d_depth=None,
+                           d_index=None, d_normal=None, cull_back: bool = False, stream: int | None = None,
+                           stats: bool = True) -> dict | None:
+        """dp_mesh_render_device: a device mesh (addresses) into device planes --
+        d_depth / d_index / d_normal are lists of device addresses, one per entry
+        of `views` (None or 0 = not wanted).  Queued on `stream`; waits only for
+        the statistics (stats=False: no wait, returns None)."""
+        nv, nt = _mesh_count("mesh_render_device", n_vertices), _mesh_count("mesh_render_device", n_triangles)
+        mro, vid = check_mesh_render_args(nv, nt, self.num_views(), views, cull_back)
+        if (nv and not d_vertices) or (nt and not d_triangles):
+            raise ValueError("mesh_render_device: the vertices and triangles must be given")
+
+        def table(addrs):
+            if addrs is None:
+                return None
+            if len(addrs) != len(vid):
+                raise ValueError("mesh_render_device: one plane address per view")
+            return (ctypes.c_void_p * len(vid))(*[int(a) if a else None for a in addrs])
+
+        st = N.DpMeshRenderStats()
+        self._check(lib.dp_mesh_render_device(self._ctx, _addr(d_vertices), nv, _addr(d_triangles), nt, ptr(vid),
+                                              len(vid), ctypes.byref(mro), table(d_depth), table(d_index),
+                                              table(d_normal), ctypes.byref(st) if stats else None, _addr(stream)))
+        return _stats_dict(st) if stats else None
+
 
 def _stats_dict(st) -> dict:
     return {name: getattr(st, name) for name, _ in st._fields_}
@@ -1143,6 +1198,19 @@ def check_mesh_decimate_args(cell, origin=(0.0, 0.0, 0.0), quadric=False):
         raise ValueError("mesh_decimate: quadric must be a bool")
     return N.DpMeshDecimateOptions((ctypes.c_float * 3)(*(float(o) for o in org)), float(cell),
                                    N.DP_DECIMATE_QUADRIC if quadric else N.DP_DECIMATE_MEAN, 0, 0)
+
+
+def check_mesh_render_args(n_vertices, n_triangles, V: int, views=None, cull_back=False):
+    """Argument validation of Engine.mesh_render[_device] (the limits of
+    dp_mesh_render, raised as ValueError before any device call); returns
+    (dp_mesh_render_options, view ids as int32)."""
+    _mesh_count("mesh_render", n_vertices)
+    _mesh_count("mesh_render", n_triangles)
+    if not isinstance(cull_back, (bool, np.bool_)):
+        raise ValueError("mesh_render: cull_back must be a bool")
+    vid = _check_view_ids("mesh_render", V, views, cap=None)
+    return (N.DpMeshRenderOptions(N.DP_MESH_RENDER_CULL_BACK if cull_back else 0),
+            np.ascontiguousarray(vid, dtype=np.int32))
 
 
 def decimate_cell(decimate, voxel) -> dict:
@@ -1671,6 +1739,25 @@ class PMVS:
             self.stats["mesh"]["normals"] = nst
             return verts, tris, nrm
         return verts, tris
+
+    def mesh_depth_maps(self, vertices, triangles, **kw) -> dict:
+        """A mesh as the views of the last run() see it: Engine.mesh_render's
+        hole-free depth (and, with normals=True, face-normal) maps, whose keyword
+        arguments (views, cull_back, normals) pass through.  The round trip:
+        v, t = pm.mesh(...), then pm.mesh_depth_maps(v, t); the maps feed
+        Engine.fuse_maps and Engine.tsdf_integrate like depth_maps' own.  The
+        statistics are left in self.stats["mesh_render"]."""
+        if not self._ran:
+            raise ValueError("mesh_depth_maps: call run() first")
+        verts = np.ascontiguousarray(vertices, dtype=N.MESH_VERTEX_DTYPE).reshape(-1)
+        tris = _mesh_triangles("mesh_depth_maps", triangles)
+        check_mesh_render_args(len(verts), len(tris), max(len(self.views), 1), kw.get("views"),
+                               kw.get("cull_back", False))
+        with Engine(self.options, self.device) as eng:
+            eng.set_views(self.views)
+            out = eng.mesh_render(verts, tris, **kw)
+        self.stats["mesh_render"] = out["stats"]
+        return out
 
 
 def ncc_score(a: np.ndarray, b: np.ndarray, denom_min: float = 0.1) -> float:

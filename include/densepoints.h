@@ -1185,6 +1185,110 @@ int dp_mesh_decimate_device(dp_ctx *ctx, const dp_mesh_decimate_options *opts, c
                             int32_t *d_vertex_map, int32_t *d_triangle_map, dp_mesh_decimate_stats *stats,
                             void *stream);
 
+/* ---- per-view depth / triangle-index / normal maps of a triangle mesh -----------
+ * No reference counterpart.  The way back from the mesh to the views: every
+ * triangle is rasterised into the requested views of the CURRENT level
+ * (dp_set_level: level-L P, W, H) and each pixel keeps the nearest one.  This is
+ * dp_render_maps' disc rule restated for triangles -- an adjugate per (triangle,
+ * view), a depth D / w, a per-pixel minimum of depth bits << 32 | index -- so the
+ * result does not depend on the triangle order or the launch geometry.  All
+ * arithmetic is fp64, one IEEE rounding per operation, in exactly the order
+ * written (the build has -ffp-contract=off); row_r, dot and the rules of the
+ * requested views (unique ids < V, 1 <= n_views <= V) are dp_render_maps'.
+ *
+ * Inputs: n_vertices 16-byte dp_mesh_vertex records, of which only pos is read,
+ * and n_triangles triangles of three int32 indices; the output of any mesh stage
+ * is a legal input.
+ * Per view v, once on the host:
+ *   m_v = (P0*(P5*P10 - P6*P9) - P1*(P4*P10 - P6*P8)) + P2*(P4*P9 - P5*P8),
+ * the determinant of the left 3x3 of the level's P; an m_v that is not finite or
+ * is 0 is DP_E_ARG.
+ *
+ * Triangle t = (i0, i1, i2) takes part iff its three indices lie in
+ * [0, n_vertices) -- otherwise it counts in invalid_triangles, and its indices
+ * are never used as an address -- and the nine floats of its positions are
+ * finite.  X_k = pos of vertex i_k, widened to fp64.
+ *
+ * (t, v) is a pair iff, tested in this order,
+ *   1. h_k = (row_0(P_v, X_k), row_1(P_v, X_k), row_2(P_v, X_k)) for k = 0, 1, 2:
+ *      all three h_k[2] > 0.  A triangle that touches or crosses the camera plane
+ *      is skipped whole (there is no clipping); such a pair counts in
+ *      clipped_pairs when at least one h_k[2] > 0;
+ *   2. edge rows, for k = 0, 1, 2 with a = h_{(k+1)%3}, b = h_{(k+2)%3}:
+ *        r_k = (a1*b2 - a2*b1, a2*b0 - a0*b2, a0*b1 - a1*b0)
+ *        D = (h_0[0]*r_0[0] + h_0[1]*r_0[1]) + h_0[2]*r_0[2]
+ *      skipped unless D is finite and D != 0.  The triangle is FRONT-facing in v
+ *      iff D and m_v have opposite signs: cross(X1 - X0, X2 - X0) points towards
+ *      the camera, dp_tsdf_mesh's outward winding.  With DP_MESH_RENDER_CULL_BACK
+ *      a pair that is not FRONT is skipped and counts in culled_pairs;
+ *   3. box: u_k = h_k[0] / h_k[2], v_k = h_k[1] / h_k[2]; skipped unless every
+ *      |u_k| < 2e9 and every |v_k| < 2e9 (NaN skips); columns x0 = max(0,
+ *      floor(min u_k)) .. x1 = min(W - 1, ceil(max u_k)), rows y0, y1 the same
+ *      from v_k and H; skipped if x0 > x1 or y0 > y1.
+ * The box is normative: no pixel outside it is ever covered by the pair.  It is
+ * rounded outwards, so a rounding of u_k can never cut a pixel that the edge test
+ * accepts.
+ *
+ * Integer pixel (x, y) of the box: l_k = (r_k[0]*x + r_k[1]*y) + r_k[2] for each
+ * k.  It is covered iff (D > 0 and all three l_k >= 0) or (D < 0 and all three
+ * l_k <= 0).  w = (l_0 + l_1) + l_2; skipped if w == 0; z = (float)(D / w),
+ * accepted iff z is finite and z > 0.  (l / D is the inverse of [h_0 h_1 h_2]
+ * applied to (x, y, 1), the pixel's barycentric weights; D / w is therefore
+ * row_2(P_v, X) at the point X of the triangle's plane on the pixel's ray, the
+ * depth dp_render_maps, dp_fuse_maps and dp_tsdf_integrate use.)  Per pixel the
+ * minimum of key = (f32 bits of z) << 32 | t wins: the nearest depth, ties to
+ * the lowest triangle index.
+ *
+ * Shared edges -- why the rows are cross products of the cyclic pair.  Two
+ * triangles that share an edge with opposite direction (a consistently oriented
+ * mesh) compute that edge's row as exact negations of each other: a*b - c*d and
+ * c*d - a*b round to negated values.  Hence their l at any pixel are exact
+ * negations, and if both face the same way the inclusive tests leave no pixel
+ * between them uncovered; a pixel exactly on the edge goes to the nearer
+ * triangle, or the lower index.  This is zero rounding and zero luck: do not
+ * "optimise" the rows into a shared adjugate routine that reorders operands.
+ *
+ * Outputs, one pointer per requested view in the order of `views`, each
+ * row-major W x H of that view at the current level; an array or an entry may be
+ * NULL: depth f32 (0 where empty), index int32 (the triangle, -1), normal 3 x f32
+ * (0): the winner's unit face normal, e = X1 - X0, f = X2 - X0, N = e x f
+ * (N_0 = e1*f2 - e2*f1, N_1 = e2*f0 - e0*f2, N_2 = e0*f1 - e1*f0), s =
+ * sqrt(dot(N, N)), (float)(N_c / s) when s is finite and s > 0, otherwise 0.  It
+ * is oriented by the winding, not flipped towards the camera.
+ * stats (may be NULL), counted on the device: triangles taking part,
+ * invalid_triangles, pairs, clipped_pairs, culled_pairs, pixel_tests = the sum
+ * of the pairs' box areas, covered_pixels = non-empty pixels after the resolve;
+ * render_ms = device time of the call's kernels.
+ * Options: only flags, the sole flag DP_MESH_RENDER_CULL_BACK; mro NULL = the
+ * defaults.
+ * Errors (DP_E_ARG): a count negative or above 2^31 - 1, a NULL input with a
+ * non-zero count, n_views outside 1..V, a view id repeated or >= V, an m_v as
+ * above, any other flag bit; no views set: DP_E_STATE.  n_triangles = 0 is
+ * legal and yields empty planes.
+ * The host form takes host arrays and host planes.  The device form takes device
+ * vertices and triangles (the outputs of dp_tsdf_mesh_device,
+ * dp_mesh_clean_device and dp_mesh_decimate_device are the intended inputs) and
+ * device planes, queues everything on `stream` (NULL = the context's) and waits
+ * only when stats != NULL, for the statistics read: dp_render_maps_device's
+ * rule. */
+#define DP_MESH_RENDER_CULL_BACK 1
+typedef struct dp_mesh_render_options {
+    int32_t flags;          /* DP_MESH_RENDER_* bits (default 0) */
+} dp_mesh_render_options;
+typedef struct dp_mesh_render_stats {
+    int64_t triangles, invalid_triangles, pairs, clipped_pairs, culled_pairs, pixel_tests, covered_pixels;
+    double render_ms;
+} dp_mesh_render_stats;
+
+void dp_default_mesh_render_options(dp_mesh_render_options *mro);
+int dp_mesh_render(dp_ctx *ctx, const dp_mesh_vertex *vertices, int64_t n_vertices, const int32_t *triangles,
+                   int64_t n_triangles, const int32_t *views, int n_views, const dp_mesh_render_options *mro,
+                   float *const *depth, int32_t *const *index, float *const *normal, dp_mesh_render_stats *stats);
+int dp_mesh_render_device(dp_ctx *ctx, const dp_mesh_vertex *d_vertices, int64_t n_vertices,
+                          const int32_t *d_triangles, int64_t n_triangles, const int32_t *views, int n_views,
+                          const dp_mesh_render_options *mro, float *const *d_depth, int32_t *const *d_index,
+                          float *const *d_normal, dp_mesh_render_stats *stats, void *stream);
+
 /* ---- seed generation: Features::Matcher::GenerateSeeds ---
  * modules/features/matcher.cpp:18-43 with the default MatcherOptions
  * (matcher.h:21-32: ORB detector, kNN matcher, no direct epipolar matching,

@@ -69,6 +69,12 @@ void usage()
                  "                             merged into one at their mean -- or, with -quadric, where the\n"
                  "                             planes of the cell's triangles meet -- and the triangles that\n"
                  "                             collapse or repeat dropped -- dp_mesh_decimate)\n"
+                 "               [--mesh-depth-maps DIR [--mesh-depth-normals] [--mesh-cull-back]]\n"
+                 "                            (only with --mesh, after the final mesh, on the device: the\n"
+                 "                             mesh rendered into every view -- dp_mesh_render -- as\n"
+                 "                             DIR/mesh_depth_NNNN.pfm and, with -normals, the face normals\n"
+                 "                             as mesh_normal_NNNN.pfm; -cull-back skips the triangles that\n"
+                 "                             face away from a view)\n"
                  "       densify --synthetic V,W,H,KIND --write-scene DIR\n");
 }
 
@@ -121,6 +127,8 @@ bool set_flag(const std::string &o, Args &a)
     else if (o == "--mesh-smooth-free-boundary") a.mesh_smooth_free_boundary = true;
     else if (o == "--mesh-normals") a.mesh_normals = true;
     else if (o == "--mesh-decimate-quadric") a.mesh_decimate_quadric = true;
+    else if (o == "--mesh-depth-normals") a.mesh_depth_normals = true;
+    else if (o == "--mesh-cull-back") a.mesh_cull_back = true;
     else if (o == "--epipolar-matching") a.matcher.epipolar_matching = 1;
     else return false;
     return true;
@@ -152,6 +160,7 @@ Parse parse_args(int argc, char **argv, Args &a, std::string &error)
         else if (o == "--synthetic") a.synth = v;
         else if (o == "--write-scene") a.scene_dir = v;
         else if (o == "--depth-maps") a.depth_dir = v;
+        else if (o == "--mesh-depth-maps") a.mesh_depth_dir = v;
         else if (o == "--fuse") a.fuse_path = v;
         else if (o == "--device") a.device = std::atoi(v.c_str());
         else if (o == "--gpus") a.gpus = std::atoi(v.c_str());
@@ -293,6 +302,14 @@ Parse parse_args(int argc, char **argv, Args &a, std::string &error)
     }
     if (a.mesh_decimate_quadric && !(a.mesh_decimate > 0.0)) {
         error = "--mesh-decimate-quadric needs --mesh-decimate";
+        return Parse::UsageError;
+    }
+    if (a.mesh_path.empty() && (!a.mesh_depth_dir.empty() || a.mesh_depth_normals || a.mesh_cull_back)) {
+        error = "--mesh-depth-maps, --mesh-depth-normals and --mesh-cull-back need --mesh";
+        return Parse::UsageError;
+    }
+    if (a.mesh_depth_dir.empty() && (a.mesh_depth_normals || a.mesh_cull_back)) {
+        error = "--mesh-depth-normals and --mesh-cull-back need --mesh-depth-maps";
         return Parse::UsageError;
     }
     if (a.iterations > 1)

@@ -55,6 +55,10 @@ struct Args {
     // lattice anchored at the volume's origin.  Only with --mesh.
     double mesh_decimate = 0.0; // 0: not given, no simplification
     bool mesh_decimate_quadric = false;
+    // --mesh-depth-maps DIR [--mesh-depth-normals] [--mesh-cull-back]:
+    // dp_mesh_render of the final mesh into every view.  Only with --mesh.
+    std::string mesh_depth_dir;
+    bool mesh_depth_normals = false, mesh_cull_back = false;
 
     Args();
 };

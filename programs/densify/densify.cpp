@@ -703,6 +703,59 @@ std::string write_mesh(dp_ctx *ctx, const Args &args, int32_t V, const std::vect
                       (long long)ns.zero_normals, ns.normals_ms);
         cleaned += nbuf;
     }
+    // --mesh-depth-maps: the mesh as it will be written, still on the device,
+    // rendered into every view (dp_mesh_render_device) and written as PFM files
+    std::string rendered;
+    if (!args.mesh_depth_dir.empty()) {
+        if (mkdir(args.mesh_depth_dir.c_str(), 0777) != 0 && errno != EEXIST)
+            throw std::runtime_error("cannot create " + args.mesh_depth_dir);
+        dp_mesh_render_options mro;
+        dp_default_mesh_render_options(&mro);
+        if (args.mesh_cull_back)
+            mro.flags |= DP_MESH_RENDER_CULL_BACK;
+        std::vector<int32_t> views((size_t)V), ws((size_t)V), hs((size_t)V);
+        std::vector<float *> pd((size_t)V), pn((size_t)V, nullptr);
+        for (int32_t v = 0; v < V; ++v) {
+            views[(size_t)v] = v;
+            check(ctx, dp_level_info(ctx, args.level, v, &ws[(size_t)v], &hs[(size_t)v], nullptr), "dp_level_info");
+            const size_t px = (size_t)ws[(size_t)v] * (size_t)hs[(size_t)v];
+            pd[(size_t)v] = (float *)m.bytes(px * sizeof(float), "--mesh-depth-maps");
+            if (args.mesh_depth_normals)
+                pn[(size_t)v] = (float *)m.bytes(px * 3 * sizeof(float), "--mesh-depth-maps");
+        }
+        dp_mesh_render_stats rs;
+        check(ctx,
+              dp_mesh_render_device(ctx, nv ? d_verts : nullptr, nv, nt ? d_tris : nullptr, nt, views.data(), V, &mro,
+                                    pd.data(), nullptr, args.mesh_depth_normals ? pn.data() : nullptr, &rs, nullptr),
+              "dp_mesh_render_device");
+        std::vector<float> plane;
+        for (int32_t v = 0; v < V; ++v) {
+            const int w = ws[(size_t)v], h = hs[(size_t)v];
+            const float *src[2] = {pd[(size_t)v], pn[(size_t)v]};
+            const char *fmt[2] = {"/mesh_depth_%04d.pfm", "/mesh_normal_%04d.pfm"};
+            for (int j = 0; j < 2; ++j) {
+                if (!src[j])
+                    continue;
+                const int ch = j ? 3 : 1;
+                plane.resize((size_t)w * h * ch);
+                if (!plane.empty() &&
+                    hipMemcpy(plane.data(), src[j], plane.size() * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)
+                    throw std::runtime_error("--mesh-depth-maps: copy of a plane failed");
+                char name[64];
+                std::snprintf(name, sizeof name, fmt[j], (int)v);
+                dpio::write_pfm(args.mesh_depth_dir + name, plane.data(), w, h, ch);
+            }
+        }
+        char rbuf[480];
+        std::snprintf(rbuf, sizeof rbuf,
+                      ", \"mesh_render\": {\"views\": %d, \"cull_back\": %s, \"triangles\": %lld, "
+                      "\"invalid_triangles\": %lld, \"pairs\": %lld, \"clipped_pairs\": %lld, \"culled_pairs\": %lld, "
+                      "\"pixel_tests\": %lld, \"covered_pixels\": %lld, \"render_ms\": %.3f}",
+                      (int)V, args.mesh_cull_back ? "true" : "false", (long long)rs.triangles,
+                      (long long)rs.invalid_triangles, (long long)rs.pairs, (long long)rs.clipped_pairs,
+                      (long long)rs.culled_pairs, (long long)rs.pixel_tests, (long long)rs.covered_pixels, rs.render_ms);
+        rendered = rbuf;
+    }
     std::vector<dp_mesh_vertex> verts((size_t)nv);
     std::vector<int32_t> tris((size_t)nt * 3);
     if ((nv > 0 && hipMemcpy(verts.data(), d_verts, verts.size() * sizeof(dp_mesh_vertex), hipMemcpyDeviceToHost) !=
@@ -724,7 +777,7 @@ std::string write_mesh(dp_ctx *ctx, const Args &args, int32_t V, const std::vect
                   (long long)nv, (long long)nt, ts.integrate_ms + ms.mesh_ms, to.dim[0], to.dim[1], to.dim[2],
                   (double)to.voxel, (double)to.trunc, (long long)ts.observed_voxels, (long long)ms.active_cells,
                   ts.integrate_ms, ms.mesh_ms);
-    return m.refined + buf + cleaned + "}" + decimated;
+    return m.refined + buf + cleaned + "}" + decimated + rendered;
 }
 
 using Clock = std::chrono::steady_clock;
