@@ -31,6 +31,7 @@ from .pmvs import (  # noqa: F401
     check_fuse_args,
     check_mapref_args,
     check_mesh_clean_args,
+    check_mesh_colour_args,
     check_mesh_decimate_args,
     check_mesh_render_args,
     check_mesh_smooth_args,

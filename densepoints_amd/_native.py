@@ -368,6 +368,24 @@ class DpMeshRenderStats(ctypes.Structure):
 assert ctypes.sizeof(DpMeshRenderOptions) == 4 and ctypes.sizeof(DpMeshRenderStats) == 64
 
 
+DP_MESH_COLOUR_BILINEAR = 1
+DP_MESH_COLOUR_CLEAR_UNSEEN = 2
+
+
+class DpMeshColourOptions(ctypes.Structure):
+    """dp_mesh_colour_options: the options of dp_mesh_colour (include/densepoints.h)."""
+    _fields_ = [("depth_tol", ctypes.c_float), ("min_cos", ctypes.c_float), ("flags", ctypes.c_int32)]
+
+
+class DpMeshColourStats(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int64) for n in (
+        "vertices", "projected_pairs", "occluded_pairs", "grazing_pairs", "visible_pairs", "coloured_vertices",
+        "unseen_vertices")] + [("colour_ms", ctypes.c_double)]
+
+
+assert ctypes.sizeof(DpMeshColourOptions) == 12 and ctypes.sizeof(DpMeshColourStats) == 64
+
+
 class DpSynthConfig(ctypes.Structure):
     _fields_ = [
         ("n_views", ctypes.c_int32),
@@ -523,6 +541,9 @@ SIGNATURES = [
     ("dp_default_mesh_render_options", None, [_P]),
     ("dp_mesh_render", _I, [_P, _P, ctypes.c_int64, _P, ctypes.c_int64, _P, _I, _P, _P, _P, _P, _P]),
     ("dp_mesh_render_device", _I, [_P, _P, ctypes.c_int64, _P, ctypes.c_int64, _P, _I, _P, _P, _P, _P, _P, _P]),
+    ("dp_default_mesh_colour_options", None, [_P]),
+    ("dp_mesh_colour", _I, [_P, _P, ctypes.c_int64, _P, _P, _I, _P, _P, _P, _P, _P, _P]),
+    ("dp_mesh_colour_device", _I, [_P, _P, ctypes.c_int64, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P]),
     ("dp_last_kernel_ms", _I, [_P, _P]),
     ("dp_default_matcher_options", None, [_P]),
     ("dp_orb_pattern", _I, [_P]),

@@ -7,7 +7,8 @@
 // dp_render.hip: maps; dp_fuse.hip: their fusion; dp_mapref.hip: their
 // refinement; dp_tsdf.hip: their volume and mesh; dp_meshclean.hip: the mesh's
 // components; dp_meshsmooth.hip: its adjacency, smoothing and normals;
-// dp_meshdecimate.hip: its simplification; dp_meshrender.hip: its maps -- each
+// dp_meshdecimate.hip: its simplification; dp_meshrender.hip: its maps;
+// dp_meshcolour.hip: its colours -- each
 // with its scratch as one named member of the context and
 // the host helpers they share at the end of this file).  Every member that
 // owns a device or pinned allocation or an event has an owning type
@@ -204,6 +205,17 @@ struct MeshRenderScratch {
     Timer time;
 };
 
+// dp_mesh_colour: the view table, the counters; the host form's staged vertices,
+// normals and planes, its device results (vertices, seen, best) and the pinned
+// vertices it returns
+struct MeshColourScratch {
+    DevBuf<MeshColourView> tab;
+    StripedCounters count;
+    DevBuf<unsigned char> in, out;
+    HostBuf<dp_mesh_vertex> hverts;
+    Timer time;
+};
+
 } // namespace dpk
 
 struct SeedgenFree {
@@ -261,6 +273,7 @@ struct dp_ctx {
     dpk::MeshSmoothScratch smooth;
     dpk::MeshDecimateScratch decimate;
     dpk::MeshRenderScratch meshrender;
+    dpk::MeshColourScratch meshcolour;
     HostBuf<dp_patch> result; // dp_densify / dp_densify_result output (pinned)
     // dp_densify_iterate: per iteration {evaluations, filter survivors} on the
     // device (read once, at the end) and the filters' timing events

@@ -318,6 +318,15 @@ struct MeshRenderPair { // one (triangle, view) pair, its uniform fp64 done once
     int32_t slot, index;
 };
 
+// vertex colours of a mesh (dp_meshcolour.hip; spec in include/densepoints.h,
+// dp_mesh_colour; its arguments stay in that file)
+struct MeshColourView { // one requested view; indexed wave-uniformly (scalar loads)
+    double P[12], C[3];  // the level's projection, the camera centre
+    const float *depth;  // W x H, the mesh as the view sees it
+    const uint32_t *img; // BGRA8 plane of the current level
+    int32_t W, H, pitch, view;
+};
+
 // depth-map fusion (dp_fuse.hip; spec in include/densepoints.h, dp_fuse_maps)
 struct FuseView { // one requested view; indexed wave-uniformly (scalar loads)
     ViewInv inv;

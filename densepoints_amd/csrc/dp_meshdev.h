@@ -1,5 +1,5 @@
-// dp_meshdev.h -- what the mesh stages (dp_meshclean.hip, dp_meshsmooth.hip, dp_meshdecimate.hip, dp_meshrender.hip)
-// share: the block shape of their one-lane-per-item kernels, the guarded load
+// dp_meshdev.h -- what the mesh stages (dp_meshclean.hip, dp_meshsmooth.hip, dp_meshdecimate.hip, dp_meshrender.hip,
+// dp_meshcolour.hip) share: the block shape of their one-lane-per-item kernels, the guarded load
 // of a triangle, the launch over so many blocks, and the host checks of the
 // counts and pointers both sections of include/densepoints.h list.  The
 // count / scan / emit pieces themselves (block_sum, block_exclusive,

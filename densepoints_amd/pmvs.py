@@ -39,6 +39,7 @@ __all__ = [
     "check_mapref_args",
     "check_tsdf_args",
     "check_mesh_clean_args",
+    "check_mesh_colour_args",
     "check_mesh_decimate_args",
     "check_mesh_render_args",
     "check_mesh_smooth_args",
@@ -1162,6 +1163,74 @@ class Engine:
                                               table(d_normal), ctypes.byref(st) if stats else None, _addr(stream)))
         return _stats_dict(st) if stats else None
 
+    # ---- vertex colours from the views (include/densepoints.h dp_mesh_colour) ----
+    def mesh_colour(self, vertices, views=None, depth=None, triangles=None, normals=None, depth_tol: float = 0.01,
+                    min_cos: float = 0.2, bilinear: bool = False, clear_unseen: bool = False) -> dict:
+        """dp_mesh_colour: every vertex coloured by the mean of the texels of the
+        `views` (None = all, at most 64) that see it at the current level.
+        `depth` is one H x W float32 plane of the mesh per view, in the order of
+        `views` (mesh_render's "depth"); None renders them here from `triangles`
+        (mesh_render without culling).  `normals` (n x 3 float32, mesh_normals'
+        output) weights a view by the cosine between the normal and the ray to
+        its camera and drops it below min_cos; depth_tol is the relative depth by
+        which a vertex may lie behind the plane; bilinear samples four taps
+        instead of the nearest texel; clear_unseen blacks the vertices no view
+        sees instead of keeping their colour.  Returns {"vertices", "seen"
+        (uint64, bit k = views[k]), "best" (int32 position in views, -1 =
+        unseen), "views", "stats"}."""
+        verts = np.ascontiguousarray(vertices, dtype=N.MESH_VERTEX_DTYPE).reshape(-1)
+        nv = len(verts)
+        mco, vid = check_mesh_colour_args(nv, self.num_views(), views, depth, depth_tol, min_cos, bilinear,
+                                          clear_unseen)
+        sizes = self.view_sizes(vid)
+        if depth is None:
+            if triangles is None:
+                raise ValueError("mesh_colour: depth planes or triangles must be given")
+            depth = self.mesh_render(verts, triangles, views=vid)["depth"]
+        planes = [np.ascontiguousarray(d, dtype=np.float32) for d in depth]
+        if any(p.shape != (h, w) for p, (w, h) in zip(planes, sizes)):
+            raise ValueError("mesh_colour: a depth plane must be H x W of its view at the current level")
+        nrm = None
+        if normals is not None:
+            nrm = np.ascontiguousarray(normals, dtype=np.float32)
+            if nrm.shape != (nv, 3):
+                raise ValueError("mesh_colour: normals must be n_vertices x 3")
+        seen, best = np.zeros(nv, np.uint64), np.zeros(nv, np.int32)
+        tab = (ctypes.c_void_p * len(vid))(*[p.ctypes.data for p in planes])
+        pv, st = ctypes.c_void_p(), N.DpMeshColourStats()
+        self._check(lib.dp_mesh_colour(self._ctx, ptr(verts) if nv else None, nv,
+                                       ptr(nrm) if nrm is not None and nv else None, ptr(vid), len(vid),
+                                       ctypes.byref(mco), tab, ctypes.byref(pv), ptr(seen) if nv else None,
+                                       ptr(best) if nv else None, ctypes.byref(st)))
+        out = np.zeros(nv, dtype=N.MESH_VERTEX_DTYPE)
+        if nv:
+            ctypes.memmove(out.ctypes.data, pv.value, out.nbytes)
+        return {"vertices": out, "seen": seen, "best": best, "views": [int(v) for v in vid], "stats": _stats_dict(st)}
+
+    def mesh_colour_device(self, d_vertices, n_vertices: int, views, d_depth, d_vertices_out, d_normals=None,
+                           d_seen=None, d_best=None, depth_tol: float = 0.01, min_cos: float = 0.2,
+                           bilinear: bool = False, clear_unseen: bool = False, stream: int | None = None,
+                           stats: bool = True) -> dict | None:
+        """dp_mesh_colour_device: device vertices (addresses) coloured into the
+        n_vertices records at d_vertices_out; d_depth is a list of device plane
+        addresses, one per entry of `views`; d_normals, d_seen and d_best are
+        optional (None or 0 = not given / not wanted).  Queued on `stream`; waits
+        only for the statistics (stats=False: no wait, returns None)."""
+        nv = _mesh_count("mesh_colour_device", n_vertices)
+        mco, vid = check_mesh_colour_args(nv, self.num_views(), views, d_depth, depth_tol, min_cos, bilinear,
+                                          clear_unseen, inputs=(d_vertices, d_normals), outputs=(d_vertices_out, d_seen,
+                                                                                                 d_best))
+        if d_depth is None:
+            raise ValueError("mesh_colour_device: the depth planes must be given")
+        if nv and not (d_vertices and d_vertices_out):
+            raise ValueError("mesh_colour_device: the vertices and the output must be given")
+        tab = (ctypes.c_void_p * len(vid))(*[int(a) for a in d_depth])
+        st = N.DpMeshColourStats()
+        self._check(lib.dp_mesh_colour_device(self._ctx, _addr(d_vertices), nv, _addr(d_normals), ptr(vid), len(vid),
+                                              ctypes.byref(mco), tab, _addr(d_vertices_out), _addr(d_seen),
+                                              _addr(d_best), ctypes.byref(st) if stats else None, _addr(stream)))
+        return _stats_dict(st) if stats else None
+
 
 def _stats_dict(st) -> dict:
     return {name: getattr(st, name) for name, _ in st._fields_}
@@ -1211,6 +1280,64 @@ def check_mesh_render_args(n_vertices, n_triangles, V: int, views=None, cull_bac
     vid = _check_view_ids("mesh_render", V, views, cap=None)
     return (N.DpMeshRenderOptions(N.DP_MESH_RENDER_CULL_BACK if cull_back else 0),
             np.ascontiguousarray(vid, dtype=np.int32))
+
+
+def check_mesh_colour_args(n_vertices, V: int, views=None, depth=None, depth_tol=0.01, min_cos=0.2, bilinear=False,
+                           clear_unseen=False, inputs=(), outputs=()):
+    """Argument validation of Engine.mesh_colour[_device] (the limits of
+    dp_mesh_colour, raised as ValueError before any device call); returns
+    (dp_mesh_colour_options, view ids as int32).  `depth`: the planes or their
+    addresses, one per view and none of them None or 0 (None here: not checked,
+    Engine.mesh_colour renders them); `inputs` and `outputs`: the device form's
+    addresses, of which no output may equal an input or a plane."""
+    def number(x):
+        return isinstance(x, (int, float, np.integer, np.floating)) and not isinstance(x, bool)
+
+    _mesh_count("mesh_colour", n_vertices)
+    if not (number(depth_tol) and 0 <= depth_tol <= 3.4028234663852886e38):
+        raise ValueError("mesh_colour: depth_tol must be finite and >= 0")
+    if not (number(min_cos) and 0 <= min_cos <= 1):
+        raise ValueError("mesh_colour: min_cos must be in 0..1")
+    if not isinstance(bilinear, (bool, np.bool_)) or not isinstance(clear_unseen, (bool, np.bool_)):
+        raise ValueError("mesh_colour: bilinear and clear_unseen must be bools")
+    vid = _check_view_ids("mesh_colour", V, views)
+    planes = []
+    if depth is not None:
+        planes = list(depth)
+        if len(planes) != len(vid) or any(p is None or (isinstance(p, (int, np.integer)) and not p) for p in planes):
+            raise ValueError("mesh_colour: one depth plane per view, none of them missing")
+    ins = [a for a in list(inputs) + planes if isinstance(a, (int, np.integer)) and a]
+    if any(isinstance(o, (int, np.integer)) and o and o in ins for o in outputs):
+        raise ValueError("mesh_colour: an output equals an input")
+    flags = (N.DP_MESH_COLOUR_BILINEAR if bilinear else 0) | (N.DP_MESH_COLOUR_CLEAR_UNSEEN if clear_unseen else 0)
+    return N.DpMeshColourOptions(float(depth_tol), float(min_cos), flags), np.ascontiguousarray(vid, dtype=np.int32)
+
+
+def _colour_on_device(eng, device: int, verts, tris, normals, colour: dict):
+    """PMVS.mesh's last stage: the host mesh uploaded once, rendered into the
+    views of `colour` and coloured there (mesh_render_device, then
+    mesh_colour_device on the planes it left); returns (vertices, stats)."""
+    import torch
+
+    def up(a):
+        return torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).to(dev)
+
+    nv, nt = len(verts), len(tris)
+    _, vid = check_mesh_colour_args(nv, eng.num_views(), colour.get("views"))
+    dev = torch.device("cuda", device)
+    d_verts, d_tris = up(verts), up(tris)
+    d_nrm = up(normals) if normals is not None else None
+    d_out = torch.empty(max(nv, 1) * N.MESH_VERTEX_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+    depth = [torch.empty((h, w), dtype=torch.float32, device=dev) for w, h in eng.view_sizes(vid)]
+    torch.cuda.synchronize(dev)
+    planes = [t.data_ptr() for t in depth]
+    eng.mesh_render_device(d_verts.data_ptr() if nv else 0, nv, d_tris.data_ptr() if nt else 0, nt, vid, planes,
+                           stats=False)
+    st = eng.mesh_colour_device(d_verts.data_ptr() if nv else 0, nv, vid, planes, d_out.data_ptr() if nv else 0,
+                                d_normals=d_nrm.data_ptr() if d_nrm is not None and nv else 0,
+                                **{k: v for k, v in colour.items() if k != "views"})
+    out = d_out[:nv * N.MESH_VERTEX_DTYPE.itemsize].cpu().numpy().view(N.MESH_VERTEX_DTYPE).copy()
+    return out, st
 
 
 def decimate_cell(decimate, voxel) -> dict:
@@ -1679,7 +1806,7 @@ class PMVS:
         return out
 
     def mesh(self, refine: int = 0, voxel=None, dim: int = 256, trunc=None, min_weight: int = 2, clean=None,
-             smooth=None, normals: bool = False, decimate=None, **kw):
+             smooth=None, normals: bool = False, decimate=None, colour=None, **kw):
         """The last run()'s result as a triangle mesh: (vertices as a
         MESH_VERTEX_DTYPE array, triangles as n x 3 int32).  The depth maps of
         depth_maps(refine, **kw) -- kw: its render and refinement options --
@@ -1697,15 +1824,25 @@ class PMVS:
         (default: the volume's origin), simplifies the mesh after the smoothing
         (Engine.mesh_decimate); None leaves it.  normals=True returns (vertices, triangles, normals), the
         normals (Engine.mesh_normals, n x 3 float32) of the mesh as returned.
+        colour: a dict of Engine.mesh_colour's options (views, depth_tol,
+        min_cos, bilinear, clear_unseen) replaces the vertex colours, as the
+        last stage, by the colours of the views that see each vertex: the mesh
+        as returned is rendered into the views and coloured on the device
+        (Engine.mesh_render_device, Engine.mesh_colour_device), with the normals
+        as weights when normals=True; None leaves the TSDF's colours.
         The volume and the statistics of the calls are left in
         self.stats["mesh"] (the later stages' under "clean", "smooth",
-        "decimate" and "normals")."""
+        "decimate" and "normals"), the colouring's in self.stats["mesh_colour"]."""
         if not self._ran:
             raise ValueError("mesh: call run() first")
         if clean is not None:
             check_mesh_clean_args(**dict(clean))
         if smooth is not None:
             check_mesh_smooth_args(**dict(smooth))
+        if colour is not None:
+            colour = dict(colour)
+            check_mesh_colour_args(0, max(len(self.views), 1), colour.get("views"), None,
+                                   **{k: v for k, v in colour.items() if k != "views"})
         refine, mkw, kw = split_refine_args("mesh", refine, kw)
         vol = mesh_volume(self.patches["pos"], voxel, dim, trunc)
         if decimate is not None:
@@ -1728,6 +1865,9 @@ class PMVS:
                 verts, tris, dst = eng.mesh_decimate(verts, tris, **decimate)
             if normals:
                 nrm, nst = eng.mesh_normals(verts, tris)
+            if colour is not None:
+                verts, self.stats["mesh_colour"] = _colour_on_device(eng, self.device, verts, tris,
+                                                                     nrm if normals else None, colour)
         self.stats["mesh"] = dict(vol, min_weight=int(min_weight), integrate=volume["stats"], mesh=mst)
         if clean is not None:
             self.stats["mesh"]["clean"] = cst

@@ -1289,6 +1289,113 @@ int dp_mesh_render_device(dp_ctx *ctx, const dp_mesh_vertex *d_vertices, int64_t
                           const dp_mesh_render_options *mro, float *const *d_depth, int32_t *const *d_index,
                           float *const *d_normal, dp_mesh_render_stats *stats, void *stream);
 
+/* ---- vertex colours of a mesh from the views that see it -----------------------
+ * No reference counterpart.  dp_tsdf_mesh's vertex colours are the voxels': a
+ * per-voxel mean blurred to the voxel size, which dp_mesh_smooth and
+ * dp_mesh_decimate then carry to places the surface no longer is.  This stage
+ * colours the FINAL vertices: a vertex is projected into every requested view of
+ * the CURRENT level (dp_set_level: level-L P, W, H and BGRA8 planes), a depth
+ * plane of the mesh in that view (dp_mesh_render's depth output is the intended
+ * input) decides whether the view sees it, and the colour is the mean of the
+ * seeing views' texels, weighted by the cosine between the vertex normal and the
+ * ray when normals are given.  All arithmetic is fp64, one IEEE rounding per
+ * operation, in exactly the order written (the build has -ffp-contract=off);
+ * row_r, dot, "is a depth", backproject, A, det and the rules of the requested
+ * views (unique ids < V, 1 <= K <= min(V, 64)) are dp_fuse_maps's.
+ *
+ * Inputs: n_vertices 16-byte dp_mesh_vertex records; optionally `normals`, 3 x
+ * f32 per vertex (dp_mesh_normals' output is the intended input; NULL = none);
+ * the requested views views[0..K-1]; per requested view, in the order of
+ * `views`, an f32 depth plane W x H, row-major, of the mesh at the current level
+ * (the array and every entry are required); the options below.  No triangle is
+ * read.
+ *
+ * Per requested view v, once on the host: A and det as in dp_fuse_maps (a det
+ * that is 0 or not finite: DP_E_ARG) and the camera centre C_v = backproject(v,
+ * 0, 0, 0), that is
+ *   C_j = ((A[3j]*(0 - P[3]) + A[3j+1]*(0 - P[7])) + A[3j+2]*(0 - P[11])) / det;
+ * a C that is not finite: DP_E_ARG.
+ *
+ * Vertex i takes part iff its three pos floats are finite; otherwise its record
+ * is copied byte for byte, its seen is 0 and its best is -1, and it counts in no
+ * statistic.  X = pos widened to fp64.  With normals, n = its normal widened,
+ * l2 = dot(n, n), and the vertex HAS A NORMAL iff l2 is finite and l2 > 0.
+ * Start with wsum = 0.0, s_R = s_G = s_B = 0.0, mask = 0, best = -1, bw = 0.0;
+ * then for k = 0..K-1 in order, v = views[k]:
+ *   1. d, u, v, xi, yi by steps 1-3 of dp_fuse_maps's observe (d > 0; |u|, |v| <
+ *      2e9; rint, round-half-even; 0 <= xi < W_v and 0 <= yi < H_v);
+ *   2. z = depth_v[yi][xi]; require that z is a depth.  A pair that gets this far
+ *      counts in projected_pairs;
+ *   3. occlusion, one-sided: require d - (double)z <= (double)depth_tol * d (a
+ *      surface in front of the vertex hides it; one behind it does not).  A pair
+ *      that fails counts in occluded_pairs;
+ *   4. weight.  Without a normal wgt = 1.0.  With one: ray_j = X_j - C_j; q =
+ *      dot(ray, ray) * l2, require q finite and q > 0; c = (0.0 - dot(n, ray)) /
+ *      sqrt(q), require c > 0 and c >= (double)min_cos; wgt = c.  A pair that
+ *      fails a requirement of this step counts in grazing_pairs;
+ *   5. sample each channel ch of view v's BGRA8 plane (R = bits 16..23, G = bits
+ *      8..15, B = bits 0..7 of the texel word, the bytes dp_tsdf_integrate reads;
+ *      t(x, y) = that byte of texel (x, y)).  Default: val = (double)t(xi, yi).
+ *      With DP_MESH_COLOUR_BILINEAR: x0 = floor(u), y0 = floor(v), fx = u -
+ *      (double)x0, fy = v - (double)y0; taps xa = clamp(x0, 0, W-1), xb =
+ *      clamp(x0 + 1, 0, W-1), ya, yb likewise with H;
+ *        top = (1.0 - fx)*t(xa, ya) + fx*t(xb, ya)
+ *        bot = (1.0 - fx)*t(xa, yb) + fx*t(xb, yb)
+ *        val = (1.0 - fy)*top + fy*bot;
+ *   6. s_ch = s_ch + wgt * val; wsum = wsum + wgt; mask |= 1 << k (64-bit); if
+ *      wgt > bw: bw = wgt, best = k (ties go to the lowest k); the pair counts
+ *      in visible_pairs.
+ * projected_pairs = occluded_pairs + grazing_pairs + visible_pairs.
+ *
+ * Outputs: vertices_out, pos and pad copied; for mask != 0 rgb[ch] =
+ * (uint8)min(255.0, rint(s_ch / wsum)), ch = R, G, B, and the vertex counts in
+ * coloured_vertices; for mask == 0 the input colour -- or 0, 0, 0 with
+ * DP_MESH_COLOUR_CLEAR_UNSEEN -- and it counts in unseen_vertices.  Optional
+ * seen: uint64 per vertex, bit k = position k in `views`.  Optional best: int32
+ * per vertex, the position k of the heaviest view, -1 when unseen.  One vertex's
+ * result is a function of that vertex and the views walked in order: no atomics
+ * on the results, no dependence on the launch geometry.
+ * stats (may be NULL), counted on the device: vertices (those taking part),
+ * projected_pairs, occluded_pairs, grazing_pairs, visible_pairs,
+ * coloured_vertices, unseen_vertices; colour_ms = device time of the call's
+ * kernel.
+ * Options: mco NULL = the defaults.
+ * Errors (DP_E_ARG): n_vertices negative or above 2^31 - 1, vertices NULL with
+ * n_vertices > 0, the view rules, depth NULL or a NULL entry, depth_tol negative
+ * or not finite, min_cos outside 0..1, an unknown flag, an output that equals an
+ * input, a det or C as above; no views set: DP_E_STATE.  n_vertices = 0 is legal.
+ * Host form: host arrays and planes; *vertices_out (required) is context-owned,
+ * valid until the next dp_mesh_colour or destroy, NULL when n_vertices is 0; seen
+ * and best are the caller's arrays.  Device form: device vertices, normals,
+ * planes and caller buffers (d_vertices_out required when n_vertices > 0);
+ * everything is queued on `stream` (NULL = the context's) and the call waits
+ * only when stats != NULL.
+ * Limits: the occlusion test reads the nearest pixel's depth, so on a steep
+ * slant it leans on depth_tol; all K depth planes are resident at once; the
+ * colour is per vertex (seen and best are what a texture atlas would start
+ * from). */
+#define DP_MESH_COLOUR_BILINEAR 1
+#define DP_MESH_COLOUR_CLEAR_UNSEEN 2
+typedef struct dp_mesh_colour_options {
+    float depth_tol;        /* 0.01 relative depth by which a vertex may lie behind the plane */
+    float min_cos;          /* 0.2  least cosine between the normal and the ray to the camera  */
+    int32_t flags;          /* DP_MESH_COLOUR_* bits (default 0)                               */
+} dp_mesh_colour_options;
+typedef struct dp_mesh_colour_stats {
+    int64_t vertices, projected_pairs, occluded_pairs, grazing_pairs, visible_pairs, coloured_vertices,
+        unseen_vertices;
+    double colour_ms;
+} dp_mesh_colour_stats;
+
+void dp_default_mesh_colour_options(dp_mesh_colour_options *mco);
+int dp_mesh_colour(dp_ctx *ctx, const dp_mesh_vertex *vertices, int64_t n_vertices, const float *normals,
+                   const int32_t *views, int n_views, const dp_mesh_colour_options *mco, const float *const *depth,
+                   const dp_mesh_vertex **vertices_out, uint64_t *seen, int32_t *best, dp_mesh_colour_stats *stats);
+int dp_mesh_colour_device(dp_ctx *ctx, const dp_mesh_vertex *d_vertices, int64_t n_vertices, const float *d_normals,
+                          const int32_t *views, int n_views, const dp_mesh_colour_options *mco,
+                          const float *const *d_depth, dp_mesh_vertex *d_vertices_out, uint64_t *d_seen,
+                          int32_t *d_best, dp_mesh_colour_stats *stats, void *stream);
+
 /* ---- seed generation: Features::Matcher::GenerateSeeds ---
  * modules/features/matcher.cpp:18-43 with the default MatcherOptions
  * (matcher.h:21-32: ORB detector, kNN matcher, no direct epipolar matching,

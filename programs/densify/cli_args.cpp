@@ -75,6 +75,13 @@ void usage()
                  "                             DIR/mesh_depth_NNNN.pfm and, with -normals, the face normals\n"
                  "                             as mesh_normal_NNNN.pfm; -cull-back skips the triangles that\n"
                  "                             face away from a view)\n"
+                 "               [--mesh-colour [--mesh-colour-bilinear] [--mesh-colour-tol T]\n"
+                 "                [--mesh-colour-min-cos C]]\n"
+                 "                            (only with --mesh, after the final mesh, on the device: every\n"
+                 "                             vertex coloured by the views that see it -- dp_mesh_colour --\n"
+                 "                             against the mesh's own depth maps, weighted by the cosine\n"
+                 "                             between its normal and the ray; T: relative depth tolerance,\n"
+                 "                             0.01; C: least cosine, 0.2; -bilinear: four taps per view)\n"
                  "       densify --synthetic V,W,H,KIND --write-scene DIR\n");
 }
 
@@ -129,6 +136,8 @@ bool set_flag(const std::string &o, Args &a)
     else if (o == "--mesh-decimate-quadric") a.mesh_decimate_quadric = true;
     else if (o == "--mesh-depth-normals") a.mesh_depth_normals = true;
     else if (o == "--mesh-cull-back") a.mesh_cull_back = true;
+    else if (o == "--mesh-colour") a.mesh_colour = true;
+    else if (o == "--mesh-colour-bilinear") a.mesh_colour_bilinear = true;
     else if (o == "--epipolar-matching") a.matcher.epipolar_matching = 1;
     else return false;
     return true;
@@ -262,6 +271,16 @@ Parse parse_args(int argc, char **argv, Args &a, std::string &error)
                 a.mesh_decimate = t;
             else
                 error = "--mesh-decimate expects a finite number > 0";
+        } else if (o == "--mesh-colour-tol") {
+            if (number_in_range(v, 0.0, 3.0e38, t))
+                a.mesh_colour_tol = t;
+            else
+                error = "--mesh-colour-tol expects a finite number >= 0";
+        } else if (o == "--mesh-colour-min-cos") {
+            if (number_in_range(v, 0.0, 1.0, t))
+                a.mesh_colour_min_cos = t;
+            else
+                error = "--mesh-colour-min-cos expects a number in 0..1";
         } else if (o == "--exchange") {
             a.exchange_mode = v;
             if (one_of(v, {"auto", "rccl", "copy"}) < 0)
@@ -310,6 +329,15 @@ Parse parse_args(int argc, char **argv, Args &a, std::string &error)
     }
     if (a.mesh_depth_dir.empty() && (a.mesh_depth_normals || a.mesh_cull_back)) {
         error = "--mesh-depth-normals and --mesh-cull-back need --mesh-depth-maps";
+        return Parse::UsageError;
+    }
+    const bool colour_detail = a.mesh_colour_bilinear || a.mesh_colour_tol >= 0.0 || a.mesh_colour_min_cos >= 0.0;
+    if (a.mesh_path.empty() && (a.mesh_colour || colour_detail)) {
+        error = "--mesh-colour and its options need --mesh";
+        return Parse::UsageError;
+    }
+    if (!a.mesh_colour && colour_detail) {
+        error = "--mesh-colour-bilinear, -tol and -min-cos need --mesh-colour";
         return Parse::UsageError;
     }
     if (a.iterations > 1)

@@ -59,6 +59,11 @@ struct Args {
     // dp_mesh_render of the final mesh into every view.  Only with --mesh.
     std::string mesh_depth_dir;
     bool mesh_depth_normals = false, mesh_cull_back = false;
+    // --mesh-colour [--mesh-colour-bilinear] [--mesh-colour-tol T]
+    // [--mesh-colour-min-cos C]: dp_mesh_colour of the final mesh from every
+    // view.  Only with --mesh.
+    bool mesh_colour = false, mesh_colour_bilinear = false;
+    double mesh_colour_tol = -1.0, mesh_colour_min_cos = -1.0; // < 0: the library's default
 
     Args();
 };

@@ -686,16 +686,19 @@ std::string write_mesh(dp_ctx *ctx, const Args &args, int32_t V, const std::vect
                       (long long)ds.vertices_out, (long long)ds.triangles_out, ds.decimate_ms);
         decimated = dbuf;
     }
+    // (--mesh-colour weights the views by them, so it computes them too; they
+    // are written only with --mesh-normals)
     std::vector<float> normals;
-    if (args.mesh_normals) {
-        float *d_normals = (float *)m.bytes((size_t)vcap * 3 * sizeof(float), "--mesh");
+    float *d_normals = nullptr;
+    if (args.mesh_normals || args.mesh_colour) {
+        d_normals = (float *)m.bytes((size_t)vcap * 3 * sizeof(float), "--mesh");
         dp_mesh_normals_stats ns;
         check(ctx,
               dp_mesh_normals_device(ctx, nv ? d_verts : nullptr, nv, nt ? d_tris : nullptr, nt, nv ? d_normals : nullptr,
                                      &ns, nullptr),
               "dp_mesh_normals_device");
-        normals.resize((size_t)nv * 3);
-        if (nv > 0 && hipMemcpy(normals.data(), d_normals, normals.size() * sizeof(float), hipMemcpyDeviceToHost) !=
+        normals.resize(args.mesh_normals ? (size_t)nv * 3 : 0);
+        if (!normals.empty() && hipMemcpy(normals.data(), d_normals, normals.size() * sizeof(float), hipMemcpyDeviceToHost) !=
                           hipSuccess)
             throw std::runtime_error("--mesh: copy of the normals failed");
         char nbuf[160];
@@ -704,10 +707,13 @@ std::string write_mesh(dp_ctx *ctx, const Args &args, int32_t V, const std::vect
         cleaned += nbuf;
     }
     // --mesh-depth-maps: the mesh as it will be written, still on the device,
-    // rendered into every view (dp_mesh_render_device) and written as PFM files
+    // rendered into every view (dp_mesh_render_device) and written as PFM files;
+    // --mesh-colour reads the same depth planes, rendered once for both
     std::string rendered;
-    if (!args.mesh_depth_dir.empty()) {
-        if (mkdir(args.mesh_depth_dir.c_str(), 0777) != 0 && errno != EEXIST)
+    std::vector<int32_t> rviews;
+    std::vector<float *> rdepth;
+    if (!args.mesh_depth_dir.empty() || args.mesh_colour) {
+        if (!args.mesh_depth_dir.empty() && mkdir(args.mesh_depth_dir.c_str(), 0777) != 0 && errno != EEXIST)
             throw std::runtime_error("cannot create " + args.mesh_depth_dir);
         dp_mesh_render_options mro;
         dp_default_mesh_render_options(&mro);
@@ -728,8 +734,10 @@ std::string write_mesh(dp_ctx *ctx, const Args &args, int32_t V, const std::vect
               dp_mesh_render_device(ctx, nv ? d_verts : nullptr, nv, nt ? d_tris : nullptr, nt, views.data(), V, &mro,
                                     pd.data(), nullptr, args.mesh_depth_normals ? pn.data() : nullptr, &rs, nullptr),
               "dp_mesh_render_device");
+        rviews = views;
+        rdepth = pd;
         std::vector<float> plane;
-        for (int32_t v = 0; v < V; ++v) {
+        for (int32_t v = 0; v < V && !args.mesh_depth_dir.empty(); ++v) {
             const int w = ws[(size_t)v], h = hs[(size_t)v];
             const float *src[2] = {pd[(size_t)v], pn[(size_t)v]};
             const char *fmt[2] = {"/mesh_depth_%04d.pfm", "/mesh_normal_%04d.pfm"};
@@ -755,6 +763,36 @@ std::string write_mesh(dp_ctx *ctx, const Args &args, int32_t V, const std::vect
                       (long long)rs.invalid_triangles, (long long)rs.pairs, (long long)rs.clipped_pairs,
                       (long long)rs.culled_pairs, (long long)rs.pixel_tests, (long long)rs.covered_pixels, rs.render_ms);
         rendered = rbuf;
+    }
+    // --mesh-colour: the vertices of the mesh as it will be written coloured by
+    // the views that see them (dp_mesh_colour_device), the last stage
+    if (args.mesh_colour) {
+        dp_mesh_colour_options mco;
+        dp_default_mesh_colour_options(&mco);
+        if (args.mesh_colour_tol >= 0.0)
+            mco.depth_tol = (float)args.mesh_colour_tol;
+        if (args.mesh_colour_min_cos >= 0.0)
+            mco.min_cos = (float)args.mesh_colour_min_cos;
+        if (args.mesh_colour_bilinear)
+            mco.flags |= DP_MESH_COLOUR_BILINEAR;
+        dp_mesh_vertex *d_cverts = (dp_mesh_vertex *)m.bytes((size_t)vcap * sizeof(dp_mesh_vertex), "--mesh-colour");
+        dp_mesh_colour_stats cs;
+        check(ctx,
+              dp_mesh_colour_device(ctx, nv ? d_verts : nullptr, nv, nv ? d_normals : nullptr, rviews.data(), V, &mco,
+                                    rdepth.data(), nv ? d_cverts : nullptr, nullptr, nullptr, &cs, nullptr),
+              "dp_mesh_colour_device");
+        d_verts = d_cverts;
+        char cbuf[640];
+        std::snprintf(cbuf, sizeof cbuf,
+                      ", \"mesh_colour\": {\"views\": %d, \"bilinear\": %s, \"depth_tol\": %.9g, \"min_cos\": %.9g, "
+                      "\"vertices\": %lld, \"projected_pairs\": %lld, \"occluded_pairs\": %lld, "
+                      "\"grazing_pairs\": %lld, \"visible_pairs\": %lld, \"coloured_vertices\": %lld, "
+                      "\"unseen_vertices\": %lld, \"colour_ms\": %.3f}",
+                      (int)V, args.mesh_colour_bilinear ? "true" : "false", (double)mco.depth_tol, (double)mco.min_cos,
+                      (long long)cs.vertices, (long long)cs.projected_pairs, (long long)cs.occluded_pairs,
+                      (long long)cs.grazing_pairs, (long long)cs.visible_pairs, (long long)cs.coloured_vertices,
+                      (long long)cs.unseen_vertices, cs.colour_ms);
+        rendered += cbuf;
     }
     std::vector<dp_mesh_vertex> verts((size_t)nv);
     std::vector<int32_t> tris((size_t)nt * 3);
