@@ -28,6 +28,7 @@ from .pmvs import (  # noqa: F401
     FastOptions,
     Options,
     View,
+    check_cloud_nearest_args,
     check_fuse_args,
     check_mapref_args,
     check_mesh_clean_args,
@@ -36,6 +37,7 @@ from .pmvs import (  # noqa: F401
     check_mesh_render_args,
     check_mesh_smooth_args,
     check_tsdf_args,
+    cloud_compare,
     empty_patches,
     mask_from_list,
     ncc_score,

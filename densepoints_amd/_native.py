@@ -386,6 +386,20 @@ class DpMeshColourStats(ctypes.Structure):
 assert ctypes.sizeof(DpMeshColourOptions) == 12 and ctypes.sizeof(DpMeshColourStats) == 64
 
 
+class DpCloudNearestOptions(ctypes.Structure):
+    """dp_cloud_nearest_options: the options of dp_cloud_nearest (include/densepoints.h)."""
+    _fields_ = [("max_dist", ctypes.c_float), ("hist_bins", ctypes.c_int32), ("flags", ctypes.c_int32)]
+
+
+class DpCloudNearestStats(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int64) for n in (
+        "queries", "targets", "skipped_queries", "skipped_targets", "matched", "unmatched", "grid_cells",
+        "max_cell_targets")] + [("build_ms", ctypes.c_double), ("query_ms", ctypes.c_double)]
+
+
+assert ctypes.sizeof(DpCloudNearestOptions) == 12 and ctypes.sizeof(DpCloudNearestStats) == 80
+
+
 class DpSynthConfig(ctypes.Structure):
     _fields_ = [
         ("n_views", ctypes.c_int32),
@@ -544,6 +558,10 @@ SIGNATURES = [
     ("dp_default_mesh_colour_options", None, [_P]),
     ("dp_mesh_colour", _I, [_P, _P, ctypes.c_int64, _P, _P, _I, _P, _P, _P, _P, _P, _P]),
     ("dp_mesh_colour_device", _I, [_P, _P, ctypes.c_int64, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P]),
+    ("dp_cloud_nearest", _I, [_P, _P, ctypes.c_int64, ctypes.c_int64, _P, ctypes.c_int64, ctypes.c_int64, _P, _P, _P, _P,
+                              _P]),
+    ("dp_cloud_nearest_device", _I, [_P, _P, ctypes.c_int64, ctypes.c_int64, _P, ctypes.c_int64, ctypes.c_int64, _P, _P,
+                                     _P, _P, _P, _P]),
     ("dp_last_kernel_ms", _I, [_P, _P]),
     ("dp_default_matcher_options", None, [_P]),
     ("dp_orb_pattern", _I, [_P]),

@@ -8,7 +8,8 @@
 // refinement; dp_tsdf.hip: their volume and mesh; dp_meshclean.hip: the mesh's
 // components; dp_meshsmooth.hip: its adjacency, smoothing and normals;
 // dp_meshdecimate.hip: its simplification; dp_meshrender.hip: its maps;
-// dp_meshcolour.hip: its colours -- each
+// dp_meshcolour.hip: its colours; dp_cloudnearest.hip: nearest points between
+// two clouds -- each
 // with its scratch as one named member of the context and
 // the host helpers they share at the end of this file).  Every member that
 // owns a device or pinned allocation or an event has an owning type
@@ -216,6 +217,33 @@ struct MeshColourScratch {
     Timer time;
 };
 
+// dp_cloud_nearest's search grid, made on the device from the targets' bounding
+// box (cloud_plan_kernel): cell (x, y, z) has the key (z * n[1] + y) * n[0] + x
+struct CloudGrid {
+    double origin[3], cell[3];
+    int32_t n[3];
+    int32_t maxcell; // the most targets in one cell
+    int64_t cells;
+};
+
+// dp_cloud_nearest.  The targets: the per-block bounding boxes, the grid, the
+// cell keys with the target numbers and their sorted copies, the sorted targets'
+// coordinates, the first sorted position of every cell (cap + 1 entries).  The
+// queries: their cell keys and numbers and the sorted copies.  The host form's
+// staged clouds, device results (index, dist, hist) and pinned results.
+struct CloudNearestScratch {
+    DevBuf<float> boxes, tx, ty, tz;
+    DevBuf<CloudGrid> grid;
+    DevBuf<uint32_t> tkeys, tkeys_sorted, qkeys, qkeys_sorted;
+    DevBuf<int32_t> tidx, tidx_sorted, qidx, qidx_sorted, begin;
+    StripedCounters count; // + the grid
+    DevBuf<unsigned char> in, out;
+    HostBuf<int32_t> hindex;
+    HostBuf<float> hdist;
+    HostBuf<uint64_t> hhist;
+    Timer time[2]; // the grid; the queries
+};
+
 } // namespace dpk
 
 struct SeedgenFree {
@@ -274,6 +302,7 @@ struct dp_ctx {
     dpk::MeshDecimateScratch decimate;
     dpk::MeshRenderScratch meshrender;
     dpk::MeshColourScratch meshcolour;
+    dpk::CloudNearestScratch cloudnearest;
     HostBuf<dp_patch> result; // dp_densify / dp_densify_result output (pinned)
     // dp_densify_iterate: per iteration {evaluations, filter survivors} on the
     // device (read once, at the end) and the filters' timing events

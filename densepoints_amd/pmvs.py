@@ -40,6 +40,8 @@ __all__ = [
     "check_tsdf_args",
     "check_mesh_clean_args",
     "check_mesh_colour_args",
+    "check_cloud_nearest_args",
+    "cloud_compare",
     "check_mesh_decimate_args",
     "check_mesh_render_args",
     "check_mesh_smooth_args",
@@ -1231,6 +1233,157 @@ class Engine:
                                               _addr(d_best), ctypes.byref(st) if stats else None, _addr(stream)))
         return _stats_dict(st) if stats else None
 
+    # ---- nearest points between two clouds (include/densepoints.h dp_cloud_nearest) ----
+    def cloud_nearest(self, queries, targets, max_dist: float, hist_bins: int = 0) -> dict:
+        """dp_cloud_nearest: for every query the nearest target within max_dist
+        (ties to the lowest index).  `queries` and `targets` are (n, 3) float32
+        arrays or structured arrays with a `pos` field (patches, FUSED_DTYPE,
+        MESH_VERTEX_DTYPE), which are passed with their own stride, not copied to
+        packed form.  Returns {"index" (int32, -1 = none), "dist" (float32, inf
+        = none), "hist" (uint64 per bin, or None), "stats"}.  Needs no views."""
+        qa, qp, nq, qs = _cloud_points("cloud_nearest", queries)
+        ta, tp, nt, ts = _cloud_points("cloud_nearest", targets)
+        cno = check_cloud_nearest_args(nq, nt, max_dist, hist_bins, qs, ts)
+        pi, pd, ph, st = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p(), N.DpCloudNearestStats()
+        self._check(lib.dp_cloud_nearest(self._ctx, _addr(qp) if nq else None, nq, qs, _addr(tp) if nt else None, nt,
+                                         ts, ctypes.byref(cno), ctypes.byref(pi), ctypes.byref(pd),
+                                         ctypes.byref(ph) if hist_bins else None, ctypes.byref(st)))
+        index, dist = np.zeros(nq, np.int32), np.zeros(nq, np.float32)
+        if nq:
+            ctypes.memmove(index.ctypes.data, pi.value, index.nbytes)
+            ctypes.memmove(dist.ctypes.data, pd.value, dist.nbytes)
+        hist = None
+        if hist_bins:
+            hist = np.zeros(hist_bins, np.uint64)
+            ctypes.memmove(hist.ctypes.data, ph.value, hist.nbytes)
+        del qa, ta
+        return {"index": index, "dist": dist, "hist": hist, "stats": _stats_dict(st)}
+
+    def cloud_nearest_device(self, d_queries, n_queries: int, query_stride: int, d_targets, n_targets: int,
+                             target_stride: int, max_dist: float, d_index, d_dist, d_hist=None, hist_bins: int = 0,
+                             stream: int | None = None, stats: bool = True) -> dict | None:
+        """dp_cloud_nearest_device: device clouds (the addresses of their first
+        points, strides in bytes) searched into n_queries int32 at d_index and
+        float32 at d_dist, and hist_bins uint64 at d_hist when that is given.
+        Queued on `stream`; waits only for the statistics (stats=False: no wait,
+        returns None)."""
+        nq, nt = _mesh_count("cloud_nearest_device", n_queries), _mesh_count("cloud_nearest_device", n_targets)
+        cno = check_cloud_nearest_args(nq, nt, max_dist, hist_bins, query_stride, target_stride,
+                                       inputs=(d_queries, d_targets), outputs=(d_index, d_dist, d_hist))
+        if (nq and not d_queries) or (nt and not d_targets):
+            raise ValueError("cloud_nearest_device: the queries and the targets must be given")
+        if nq and not (d_index and d_dist):
+            raise ValueError("cloud_nearest_device: d_index and d_dist must be given")
+        st = N.DpCloudNearestStats()
+        self._check(lib.dp_cloud_nearest_device(self._ctx, _addr(d_queries), nq, query_stride, _addr(d_targets), nt,
+                                                target_stride, ctypes.byref(cno), _addr(d_index), _addr(d_dist),
+                                                _addr(d_hist), ctypes.byref(st) if stats else None, _addr(stream)))
+        return _stats_dict(st) if stats else None
+
+
+def _cloud_points(who: str, a):
+    """A cloud as dp_cloud_nearest takes it: (the array that owns the memory,
+    the address of the first point, the count, the stride in bytes)."""
+    a = np.asarray(a)
+    if a.dtype.names:
+        if "pos" not in a.dtype.names or a.dtype.fields["pos"][0] != np.dtype(("<f4", 3)):
+            raise ValueError("%s: a structured cloud needs a pos field of three float32" % who)
+        a = np.ascontiguousarray(a).reshape(-1)
+        stride = a.dtype.itemsize
+        if stride % 4 or a.dtype.fields["pos"][1] % 4:
+            raise ValueError("%s: a record's size and its pos offset must be multiples of 4" % who)
+        return a, a.ctypes.data + a.dtype.fields["pos"][1], _mesh_count(who, len(a)), stride
+    a = np.ascontiguousarray(a, dtype=np.float32)
+    if a.ndim != 2 or a.shape[1] != 3:
+        raise ValueError("%s: a cloud must be n x 3 float32 or a structured array with a pos field" % who)
+    return a, a.ctypes.data, _mesh_count(who, len(a)), 12
+
+
+def check_cloud_nearest_args(n_queries, n_targets, max_dist, hist_bins=0, query_stride=12, target_stride=12, flags=0,
+                             inputs=(), outputs=()):
+    """Argument validation of Engine.cloud_nearest[_device] (the limits of
+    dp_cloud_nearest, raised as ValueError before any device call); returns the
+    dp_cloud_nearest_options.  max_dist is judged as the float32 the struct
+    holds; `inputs` and `outputs`: the device form's addresses, of which no
+    output may equal an input."""
+    def whole(x):
+        return isinstance(x, (int, np.integer)) and not isinstance(x, bool)
+
+    _mesh_count("cloud_nearest", n_queries)
+    _mesh_count("cloud_nearest", n_targets)
+    for name, s in (("query_stride", query_stride), ("target_stride", target_stride)):
+        if not whole(s) or s < 12 or s % 4:
+            raise ValueError("cloud_nearest: %s must be a multiple of 4 and at least 12" % name)
+    with np.errstate(over="ignore"):
+        if isinstance(max_dist, bool) or not isinstance(max_dist, (int, float, np.integer, np.floating)) or \
+                not (np.isfinite(np.float32(max_dist)) and np.float32(max_dist) > 0):
+            raise ValueError("cloud_nearest: max_dist must be finite and > 0")
+    if not whole(hist_bins) or not 0 <= hist_bins <= 65536:
+        raise ValueError("cloud_nearest: hist_bins must be in 0..65536")
+    if not whole(flags) or flags != 0:
+        raise ValueError("cloud_nearest: unknown flags")
+    ins = [a for a in inputs if isinstance(a, (int, np.integer)) and a]
+    if any(isinstance(o, (int, np.integer)) and o and o in ins for o in outputs):
+        raise ValueError("cloud_nearest: an output equals an input")
+    return N.DpCloudNearestOptions(float(max_dist), int(hist_bins), int(flags))
+
+
+def cloud_quantile(sorted_d: np.ndarray, p: float) -> float:
+    """The p-quantile (0 <= p <= 1) of ascending fp64 values by linear
+    interpolation between the two nearest ranks: pos = p * (m - 1), lo =
+    floor(pos), d[lo] + (d[min(lo + 1, m - 1)] - d[lo]) * (pos - lo); NaN when
+    there are none."""
+    m = len(sorted_d)
+    if m == 0:
+        return float("nan")
+    pos = p * (m - 1)
+    lo = int(np.floor(pos))
+    hi = min(lo + 1, m - 1)
+    return float(sorted_d[lo] + (sorted_d[hi] - sorted_d[lo]) * (pos - lo))
+
+
+def cloud_side(nearest: dict, tau: float) -> dict:
+    """One direction of cloud_compare from a cloud_nearest result: n (queries
+    taking part), matched, within_tau (matched with dist <= tau), ratio =
+    within_tau / n (0.0 when n is 0), and mean, median (the 0.5-quantile) and p90
+    (cloud_quantile) of the matched float32 distances in fp64, NaN when none
+    matched."""
+    d = nearest["dist"][nearest["index"] >= 0].astype(np.float64)
+    n, matched = int(nearest["stats"]["queries"]), int(nearest["stats"]["matched"])
+    within = int(np.count_nonzero(d <= float(tau)))
+    ds = np.sort(d)
+    return {"n": n, "matched": matched, "within_tau": within, "ratio": within / n if n else 0.0,
+            "mean": float(d.mean()) if len(d) else float("nan"), "median": cloud_quantile(ds, 0.5),
+            "p90": cloud_quantile(ds, 0.9)}
+
+
+def check_cloud_compare_args(tau, max_dist=None) -> float:
+    """tau must be finite and > 0; max_dist (None = 10 * tau) at least tau.
+    Returns max_dist."""
+    def number(x):
+        return isinstance(x, (int, float, np.integer, np.floating)) and not isinstance(x, bool)
+
+    if not number(tau) or not (np.isfinite(tau) and tau > 0):
+        raise ValueError("cloud_compare: tau must be finite and > 0")
+    if max_dist is None:
+        max_dist = 10.0 * float(tau)
+    if not number(max_dist) or not (np.isfinite(max_dist) and max_dist >= tau):
+        raise ValueError("cloud_compare: max_dist must be finite and at least tau")
+    return float(max_dist)
+
+
+def cloud_compare(eng, recon, truth, tau: float, max_dist=None) -> dict:
+    """Accuracy, completeness and F-score of a reconstructed cloud against a
+    ground truth at the threshold tau, by two Engine.cloud_nearest calls with the
+    radius max_dist (None = 10 * tau): accuracy is recon -> truth, completeness
+    truth -> recon (each a cloud_side), fscore = 2pr / (p + r) of their ratios,
+    0.0 when p + r is 0.  The clouds are what cloud_nearest takes."""
+    max_dist = check_cloud_compare_args(tau, max_dist)
+    acc = cloud_side(eng.cloud_nearest(recon, truth, max_dist), tau)
+    com = cloud_side(eng.cloud_nearest(truth, recon, max_dist), tau)
+    p, r = acc["ratio"], com["ratio"]
+    return {"accuracy": acc, "completeness": com, "fscore": 2.0 * p * r / (p + r) if p + r > 0 else 0.0}
+
 
 def _stats_dict(st) -> dict:
     return {name: getattr(st, name) for name, _ in st._fields_}
@@ -1898,6 +2051,22 @@ class PMVS:
             out = eng.mesh_render(verts, tris, **kw)
         self.stats["mesh_render"] = out["stats"]
         return out
+
+    def evaluate(self, truth, tau: float, max_dist=None, cloud="patches") -> dict:
+        """Accuracy, completeness and F-score (cloud_compare) of a cloud of the
+        last run() against the ground-truth cloud `truth` at the threshold tau.
+        cloud: "patches" (the stored patches), "fused" (fused_cloud()'s points),
+        or a cloud of the caller's -- an (n, 3) array or a structured array with
+        a pos field, for example the vertices mesh() returned."""
+        check_cloud_compare_args(tau, max_dist)
+        if isinstance(cloud, str):
+            if cloud not in ("patches", "fused"):
+                raise ValueError('evaluate: cloud must be "patches", "fused" or an array')
+            if not self._ran:
+                raise ValueError("evaluate: call run() first")
+            cloud = self.patches if cloud == "patches" else self.fused_cloud()
+        with Engine(self.options, self.device) as eng:
+            return cloud_compare(eng, cloud, truth, tau, max_dist)
 
 
 def ncc_score(a: np.ndarray, b: np.ndarray, denom_min: float = 0.1) -> float:

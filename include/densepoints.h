@@ -1396,6 +1396,85 @@ int dp_mesh_colour_device(dp_ctx *ctx, const dp_mesh_vertex *d_vertices, int64_t
                           const float *const *d_depth, dp_mesh_vertex *d_vertices_out, uint64_t *d_seen,
                           int32_t *d_best, dp_mesh_colour_stats *stats, void *stream);
 
+/* ---- nearest-point distances between two point clouds ----------------------------
+ * No reference counterpart.  For every point of cloud A (the queries) the nearest
+ * point of cloud B (the targets) within a radius: the primitive under accuracy,
+ * completeness and F-score of a reconstruction against a ground truth (see
+ * cloud_compare in the Python package and densify --evaluate).  All arithmetic
+ * is fp64, one IEEE rounding per operation, in exactly the order written (the
+ * build has -ffp-contract=off).
+ *
+ * Inputs: n_queries and n_targets points.  Point i of an array is three
+ * consecutive f32 at base + i * stride; the stride is in bytes, a multiple of 4
+ * and at least 12, so dp_patch (64, pointing at pos), dp_fused_point (40),
+ * dp_mesh_vertex (16) and packed xyz (12) records are passed as they are.
+ * Nothing but the twelve bytes of each point is read (the host form copies an
+ * array from its first point to the end of its last, the bytes between the
+ * points with it, and nothing behind that).  No view is read: the call
+ * works on a context on which dp_set_views was never called.
+ *
+ * A point TAKES PART iff its three floats are finite.  A query that does not gets
+ * index -1 and dist +inf and counts in skipped_queries; a target that does not is
+ * never a candidate and counts in skipped_targets.  For a query q and a target t
+ * that both take part:
+ *   dx = (double)q.x - (double)t.x, dy and dz likewise;
+ *   d2 = (dx*dx + dy*dy) + dz*dz;
+ *   R2 = (double)max_dist * (double)max_dist;
+ *   t is a CANDIDATE iff d2 <= R2 (the bound is inclusive).
+ * The answer of q is the candidate with the smallest d2; equal d2 goes to the
+ * lowest target index.  index[q] = that target's index in the caller's array,
+ * dist[q] = (float)sqrt(d2), and q counts in matched.  A query with no candidate
+ * gets index -1 and dist +inf and counts in unmatched.
+ * With hist_bins = B > 0 every matched query adds 1 to bin
+ *   min(B - 1, (int64)floor((double)dist / (double)max_dist * (double)B)),
+ * dist being the f32 output; the counts are uint64 and the bins sum to matched
+ * (integer atomics; there is no floating-point atomic anywhere).
+ * queries + skipped_queries = n_queries, targets + skipped_targets = n_targets,
+ * matched + unmatched = queries.  n_queries = 0 and n_targets = 0 are legal;
+ * with no targets every query is unmatched.
+ *
+ * The result is a function of the two point sets and max_dist alone: not of the
+ * search grid, the launch geometry or the order of the queries; a permutation of
+ * the targets permutes `index` and nothing else, except where d2 ties.
+ * grid_cells and max_cell_targets describe the search grid of the implementation
+ * (its cells, at most 2^24, and the most targets in one of them), not the spec.
+ * build_ms = device time of the grid's construction, query_ms = of the queries'
+ * sort and walk.
+ * Errors (DP_E_ARG): a count negative or above 2^31 - 1, a NULL array with a
+ * positive count, a stride that is no multiple of 4 or below 12, opts NULL,
+ * max_dist not finite or not positive, hist_bins outside 0..65536, a non-zero
+ * flag, an output that equals an input; device form: d_index or d_dist NULL with
+ * n_queries > 0.
+ * Host form: host arrays; *index, *dist (both required) and *hist are
+ * context-owned, valid until the next dp_cloud_nearest or destroy (*index and
+ * *dist NULL when n_queries is 0); *hist is written only when hist is non-NULL
+ * and hist_bins > 0.  Device form: device arrays and caller buffers (d_hist
+ * optional: with hist_bins > 0 and d_hist NULL no histogram is written);
+ * everything is queued on `stream` (NULL = the context's) and the call waits
+ * only when stats != NULL.
+ * Limits: one nearest neighbour, point to point (not point to triangle); scratch
+ * is 28 bytes per target, 16 per query and the cell table (4 bytes per cell). */
+typedef struct dp_cloud_nearest_options {
+    float max_dist;     /* search radius, world units (> 0, finite; no default) */
+    int32_t hist_bins;  /* 0 = no histogram; else 1..65536                     */
+    int32_t flags;      /* none defined; non-zero is DP_E_ARG                  */
+} dp_cloud_nearest_options;
+typedef struct dp_cloud_nearest_stats {
+    int64_t queries, targets;          /* those taking part                      */
+    int64_t skipped_queries, skipped_targets, matched, unmatched;
+    int64_t grid_cells, max_cell_targets;  /* facts of the implementation, not of the spec */
+    double build_ms, query_ms;
+} dp_cloud_nearest_stats;
+
+int dp_cloud_nearest(dp_ctx *ctx, const void *queries, int64_t n_queries, int64_t query_stride,
+                     const void *targets, int64_t n_targets, int64_t target_stride,
+                     const dp_cloud_nearest_options *opts, const int32_t **index, const float **dist,
+                     const uint64_t **hist, dp_cloud_nearest_stats *stats);
+int dp_cloud_nearest_device(dp_ctx *ctx, const void *d_queries, int64_t n_queries, int64_t query_stride,
+                            const void *d_targets, int64_t n_targets, int64_t target_stride,
+                            const dp_cloud_nearest_options *opts, int32_t *d_index, float *d_dist,
+                            uint64_t *d_hist, dp_cloud_nearest_stats *stats, void *stream);
+
 /* ---- seed generation: Features::Matcher::GenerateSeeds ---
  * modules/features/matcher.cpp:18-43 with the default MatcherOptions
  * (matcher.h:21-32: ORB detector, kNN matcher, no direct epipolar matching,

@@ -82,6 +82,13 @@ void usage()
                  "                             against the mesh's own depth maps, weighted by the cosine\n"
                  "                             between its normal and the ray; T: relative depth tolerance,\n"
                  "                             0.01; C: least cosine, 0.2; -bilinear: four taps per view)\n"
+                 "               [--evaluate truth.xyz --eval-tau T [--eval-max-dist D]]\n"
+                 "                            (after the outputs are written: the patches -- and the fused\n"
+                 "                             cloud and the mesh's vertices, with --fuse and --mesh --\n"
+                 "                             against the ground-truth points of the file, one x y z per\n"
+                 "                             line as --seeds reads them, on the device -- dp_cloud_nearest;\n"
+                 "                             the report gains accuracy, completeness and F-score at the\n"
+                 "                             threshold T > 0; D = search radius >= T, default 10 T)\n"
                  "       densify --synthetic V,W,H,KIND --write-scene DIR\n");
 }
 
@@ -171,6 +178,7 @@ Parse parse_args(int argc, char **argv, Args &a, std::string &error)
         else if (o == "--depth-maps") a.depth_dir = v;
         else if (o == "--mesh-depth-maps") a.mesh_depth_dir = v;
         else if (o == "--fuse") a.fuse_path = v;
+        else if (o == "--evaluate") a.eval_path = v;
         else if (o == "--device") a.device = std::atoi(v.c_str());
         else if (o == "--gpus") a.gpus = std::atoi(v.c_str());
         else if (o == "--replicate-below") a.replicate_below = std::atoll(v.c_str());
@@ -281,6 +289,16 @@ Parse parse_args(int argc, char **argv, Args &a, std::string &error)
                 a.mesh_colour_min_cos = t;
             else
                 error = "--mesh-colour-min-cos expects a number in 0..1";
+        } else if (o == "--eval-tau") {
+            if (number_in_range(v, 0.0, 3.0e38, t) && (float)t > 0.0f)
+                a.eval_tau = t;
+            else
+                error = "--eval-tau expects a finite number > 0";
+        } else if (o == "--eval-max-dist") {
+            if (number_in_range(v, 0.0, 3.0e38, t) && (float)t > 0.0f)
+                a.eval_max_dist = t;
+            else
+                error = "--eval-max-dist expects a finite number > 0";
         } else if (o == "--exchange") {
             a.exchange_mode = v;
             if (one_of(v, {"auto", "rccl", "copy"}) < 0)
@@ -339,6 +357,22 @@ Parse parse_args(int argc, char **argv, Args &a, std::string &error)
     if (!a.mesh_colour && colour_detail) {
         error = "--mesh-colour-bilinear, -tol and -min-cos need --mesh-colour";
         return Parse::UsageError;
+    }
+    if (a.eval_path.empty() && (a.eval_tau > 0.0 || a.eval_max_dist > 0.0)) {
+        error = "--eval-tau and --eval-max-dist need --evaluate";
+        return Parse::UsageError;
+    }
+    if (!a.eval_path.empty()) {
+        if (!(a.eval_tau > 0.0)) {
+            error = "--evaluate needs --eval-tau";
+            return Parse::UsageError;
+        }
+        if (a.eval_max_dist == 0.0)
+            a.eval_max_dist = 10.0 * a.eval_tau;
+        if (!(a.eval_max_dist >= a.eval_tau) || !((float)a.eval_max_dist <= 3.0e38f)) {
+            error = "--eval-max-dist expects a finite number of at least --eval-tau";
+            return Parse::UsageError;
+        }
     }
     if (a.iterations > 1)
         a.do_filter = true; // the filter is what tells the rounds apart

@@ -64,6 +64,12 @@ struct Args {
     // view.  Only with --mesh.
     bool mesh_colour = false, mesh_colour_bilinear = false;
     double mesh_colour_tol = -1.0, mesh_colour_min_cos = -1.0; // < 0: the library's default
+    // --evaluate truth.xyz --eval-tau T [--eval-max-dist D]: accuracy,
+    // completeness and F-score of the written clouds against the ground-truth
+    // points of the file (dp_cloud_nearest, both directions) in the report
+    std::string eval_path;
+    double eval_tau = 0.0;      // 0: not given
+    double eval_max_dist = 0.0; // 0: not given; parse_args resolves it to 10 x eval_tau
 
     Args();
 };

@@ -19,6 +19,7 @@
 #include <cerrno>
 #include <chrono>
 #include <cmath>
+#include <cstddef>
 #include <cstdio>
 #include <cstring>
 #include <memory>
@@ -104,6 +105,7 @@ struct SceneData {
     std::vector<dpio::Image> imgs;
     std::vector<double> P;     // 12 per view
     std::vector<double> seeds; // xyz triples: of --seeds, else generate_or_read_seeds fills them
+    std::vector<double> truth; // xyz triples of --evaluate
 };
 
 SceneData load_scene(const Args &args)
@@ -120,6 +122,11 @@ SceneData load_scene(const Args &args)
     }
     if (!args.seeds_path.empty())
         sc.seeds = dpio::read_seeds(args.seeds_path);
+    if (!args.eval_path.empty()) {
+        sc.truth = dpio::read_seeds(args.eval_path);
+        if (sc.truth.size() / 3 > 0x7FFFFFFFull)
+            throw std::runtime_error("--evaluate: more than 2^31 - 1 points");
+    }
     return sc;
 }
 
@@ -135,7 +142,10 @@ void print_check_only(const SceneData &sc)
             h = (h ^ b) * 1099511628211ull;
         std::printf("%s\"%016llx\"", v ? ", " : "", (unsigned long long)h);
     }
-    std::printf("]}\n");
+    std::printf("]");
+    if (!sc.truth.empty()) // --evaluate
+        std::printf(", \"truth\": %zu", sc.truth.size() / 3);
+    std::printf("}\n");
 }
 
 struct CtxDestroy {
@@ -427,6 +437,110 @@ struct DeviceMaps {
     }
 };
 
+// --evaluate: the ground-truth points on the device and, per evaluated cloud,
+// the report's entry.  A cloud is searched where it lies (dp_cloud_nearest_device,
+// both directions, radius --eval-max-dist); only index and dist come back, and
+// the host sums the matched distances in fp64 in index order.
+struct Evaluation {
+    dp_ctx *ctx = nullptr;
+    double tau = 0.0;
+    float max_dist = 0.0f;
+    int64_t n_truth = 0;
+    DeviceMaps mem;
+    float *d_truth = nullptr;
+    std::string entries; // "name": {...}, ...
+
+    Evaluation(dp_ctx *c, const Args &args, const std::vector<double> &truth)
+        : ctx(c), tau(args.eval_tau), max_dist((float)args.eval_max_dist), n_truth((int64_t)(truth.size() / 3))
+    {
+        std::vector<float> xyz(truth.begin(), truth.end());
+        d_truth = (float *)mem.bytes(xyz.size() * sizeof(float), "--evaluate");
+        if (!xyz.empty() && hipMemcpy(d_truth, xyz.data(), xyz.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
+            throw std::runtime_error("--evaluate: copy of the ground truth failed");
+    }
+
+    // d[lo] + (d[min(lo + 1, m - 1)] - d[lo]) * (pos - lo), pos = p (m - 1), of ascending values
+    static double quantile(const std::vector<double> &d, double p)
+    {
+        if (d.empty())
+            return std::nan("");
+        const double pos = p * (double)(d.size() - 1);
+        const size_t lo = (size_t)std::floor(pos), hi = std::min(lo + 1, d.size() - 1);
+        return d[lo] + (d[hi] - d[lo]) * (pos - (double)lo);
+    }
+
+    static std::string number(double v)
+    {
+        if (!std::isfinite(v))
+            return "null"; // no distance matched
+        char buf[40];
+        std::snprintf(buf, sizeof buf, "%.17g", v);
+        return buf;
+    }
+
+    // one direction: its entry; *ratio = within_tau / n
+    std::string side(const void *d_q, int64_t nq, int64_t qs, const void *d_t, int64_t nt, int64_t ts, double *ratio)
+    {
+        DeviceMaps out;
+        int32_t *d_index = (int32_t *)out.bytes((size_t)nq * 4, "--evaluate");
+        float *d_dist = (float *)out.bytes((size_t)nq * 4, "--evaluate");
+        const dp_cloud_nearest_options o{max_dist, 0, 0};
+        dp_cloud_nearest_stats st;
+        check(ctx,
+              dp_cloud_nearest_device(ctx, nq ? d_q : nullptr, nq, qs, nt ? d_t : nullptr, nt, ts, &o, d_index, d_dist,
+                                      nullptr, &st, nullptr),
+              "dp_cloud_nearest_device");
+        std::vector<int32_t> index((size_t)nq);
+        std::vector<float> dist((size_t)nq);
+        if (nq > 0 && (hipMemcpy(index.data(), d_index, (size_t)nq * 4, hipMemcpyDeviceToHost) != hipSuccess ||
+                       hipMemcpy(dist.data(), d_dist, (size_t)nq * 4, hipMemcpyDeviceToHost) != hipSuccess))
+            throw std::runtime_error("--evaluate: copy of the distances failed");
+        std::vector<double> d;
+        double sum = 0.0;
+        int64_t within = 0;
+        for (size_t i = 0; i < index.size(); ++i)
+            if (index[i] >= 0) {
+                d.push_back((double)dist[i]);
+                sum += (double)dist[i];
+                within += (double)dist[i] <= tau ? 1 : 0;
+            }
+        std::sort(d.begin(), d.end());
+        *ratio = st.queries > 0 ? (double)within / (double)st.queries : 0.0;
+        char buf[200];
+        std::snprintf(buf, sizeof buf, "{\"n\": %lld, \"matched\": %lld, \"within_tau\": %lld, \"ratio\": %.17g, ",
+                      (long long)st.queries, (long long)st.matched, (long long)within, *ratio);
+        return std::string(buf) + "\"mean\": " + number(d.empty() ? std::nan("") : sum / (double)d.size()) +
+               ", \"median\": " + number(quantile(d, 0.5)) + ", \"p90\": " + number(quantile(d, 0.9)) + "}";
+    }
+
+    // the cloud of n points at d_points (device memory, `stride` bytes apart) against the truth
+    void add(const char *name, const void *d_points, int64_t n, int64_t stride)
+    {
+        double p = 0.0, r = 0.0;
+        const std::string acc = side(d_points, n, stride, d_truth, n_truth, 12, &p);
+        const std::string com = side(d_truth, n_truth, 12, d_points, n, stride, &r);
+        char buf[64];
+        std::snprintf(buf, sizeof buf, "%.17g", p + r > 0.0 ? 2.0 * p * r / (p + r) : 0.0);
+        entries += std::string(entries.empty() ? "" : ", ") + "\"" + name + "\": {\"accuracy\": " + acc +
+                   ", \"completeness\": " + com + ", \"fscore\": " + buf + "}";
+    }
+
+    // host records, uploaded first
+    template <typename T> void add_host(const char *name, const std::vector<T> &recs, size_t pos_offset)
+    {
+        DeviceMaps up;
+        char *d = (char *)up.bytes(recs.size() * sizeof(T), "--evaluate");
+        if (!recs.empty() && hipMemcpy(d, recs.data(), recs.size() * sizeof(T), hipMemcpyHostToDevice) != hipSuccess)
+            throw std::runtime_error("--evaluate: copy of a cloud failed");
+        add(name, d + pos_offset, (int64_t)recs.size(), (int64_t)sizeof(T));
+    }
+
+    std::string report() const
+    {
+        return ", \"evaluate\": {" + entries + "}";
+    }
+};
+
 void render_device_maps(dp_ctx *ctx, const Args &args, int32_t V, const std::vector<dp_patch> &kept, const char *who,
                         const char *refined_name, DeviceMaps &m)
 {
@@ -486,7 +600,7 @@ void render_device_maps(dp_ctx *ctx, const Args &args, int32_t V, const std::vec
 // come back.  An empty pixel is never emitted, so the pixels that hold a depth
 // size the point buffer; should the fusion report more, it is reallocated once
 // and re-run.  Returns the report's "fused" member.
-std::string write_fused(dp_ctx *ctx, const Args &args, int32_t V, const std::vector<dp_patch> &kept)
+std::string write_fused(dp_ctx *ctx, const Args &args, int32_t V, const std::vector<dp_patch> &kept, Evaluation *ev)
 {
     DeviceMaps m;
     render_device_maps(ctx, args, V, kept, "--fuse", "refined", m);
@@ -512,7 +626,9 @@ std::string write_fused(dp_ctx *ctx, const Args &args, int32_t V, const std::vec
     if (n_fused > 0 &&
         hipMemcpy(pts.data(), d_pts, pts.size() * sizeof(dp_fused_point), hipMemcpyDeviceToHost) != hipSuccess)
         throw std::runtime_error("--fuse: copy of the points failed");
-    dpio::write_ply(args.fuse_path, to_cloud(pts));
+    dpio::write_ply(args.fuse_path, to_cloud(pts), ev != nullptr);
+    if (ev)
+        ev->add("fused", (const char *)d_pts + offsetof(dp_fused_point, pos), n_fused, sizeof(dp_fused_point));
     char buf[240];
     std::snprintf(buf, sizeof buf,
                   ", \"fused\": {\"points\": %lld, \"fusable\": %lld, \"depth_pixels\": %lld, \"fuse_ms\": %.3f}",
@@ -527,7 +643,7 @@ std::string write_fused(dp_ctx *ctx, const Args &args, int32_t V, const std::vec
 // back.  The volume is the patches' bounding box padded by the truncation;
 // the voxel defaults to the box's longest side / --mesh-dim, the truncation to
 // four voxels.  Returns the report's "mesh" member.
-std::string write_mesh(dp_ctx *ctx, const Args &args, int32_t V, const std::vector<dp_patch> &kept)
+std::string write_mesh(dp_ctx *ctx, const Args &args, int32_t V, const std::vector<dp_patch> &kept, Evaluation *ev)
 {
     double lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
     bool any = false;
@@ -807,6 +923,8 @@ std::string write_mesh(dp_ctx *ctx, const Args &args, int32_t V, const std::vect
             out[i].rgb[k] = verts[i].rgb[k];
         }
     dpio::write_mesh_ply(args.mesh_path, out, tris, args.mesh_normals ? &normals : nullptr);
+    if (ev)
+        ev->add("mesh_vertices", d_verts, nv, sizeof(dp_mesh_vertex));
     char buf[400];
     std::snprintf(buf, sizeof buf,
                   ", \"mesh\": {\"vertices\": %lld, \"triangles\": %lld, \"ms\": %.3f, \"dim\": [%d, %d, %d], "
@@ -903,14 +1021,25 @@ int main(int argc, char **argv)
         const dp_seed_stats sst = generate_or_read_seeds(ctx.get(), args, sc);
         DensifyResult res = run_densify(ctx.get(), args, sc);
         const std::vector<dp_patch> kept = filter_survivors(ctx.get(), args, res);
-        dpio::write_ply(args.output, to_cloud(kept));
+        // with --evaluate the clouds' PLYs carry every digit of their positions:
+        // the report describes the files as written
+        std::unique_ptr<Evaluation> ev;
+        if (!args.eval_path.empty())
+            ev.reset(new Evaluation(ctx.get(), args, sc.truth));
+        dpio::write_ply(args.output, to_cloud(kept), ev != nullptr);
         std::string extra;
         if (!args.depth_dir.empty())
             extra += write_depth_maps(ctx.get(), args, V, kept);
+        if (ev)
+            ev->add_host("patches", kept, offsetof(dp_patch, pos));
         if (!args.fuse_path.empty())
-            extra += write_fused(ctx.get(), args, V, kept);
+            extra += write_fused(ctx.get(), args, V, kept, ev.get());
         if (!args.mesh_path.empty())
-            extra += write_mesh(ctx.get(), args, V, kept);
+            extra += write_mesh(ctx.get(), args, V, kept, ev.get());
+        if (ev) {
+            extra += ev->report();
+            ev.reset(); // its device memory goes before the context
+        }
         ctx.reset(); // wall_ms includes the context's teardown
         print_report(args, res, kept.size(), sc.seeds.size() / 3, sst, t0, extra);
         return 0;

@@ -356,7 +356,7 @@ std::vector<double> read_seeds(const std::string &path)
     return xyz;
 }
 
-void write_ply(const std::string &path, const std::vector<CloudPoint> &pts)
+void write_ply(const std::string &path, const std::vector<CloudPoint> &pts, bool exact_positions)
 {
     FILE *f = std::fopen(path.c_str(), "wb");
     if (!f)
@@ -365,8 +365,9 @@ void write_ply(const std::string &path, const std::vector<CloudPoint> &pts)
     std::fprintf(f, "property float x\nproperty float y\nproperty float z\n");
     std::fprintf(f, "property uchar red\nproperty uchar green\nproperty uchar blue\n");
     std::fprintf(f, "property float nx\nproperty float ny\nproperty float nz\nend_header\n");
+    const char *fmt = exact_positions ? "%.9g %.9g %.9g %u %u %u %g %g %g\n" : "%g %g %g %u %u %u %g %g %g\n";
     for (const CloudPoint &p : pts)
-        std::fprintf(f, "%g %g %g %u %u %u %g %g %g\n", (double)p.pos[0], (double)p.pos[1], (double)p.pos[2],
+        std::fprintf(f, fmt, (double)p.pos[0], (double)p.pos[1], (double)p.pos[2],
                      (unsigned)p.rgb[0], (unsigned)p.rgb[1], (unsigned)p.rgb[2], (double)p.normal[0],
                      (double)p.normal[1], (double)p.normal[2]);
     if (std::fclose(f) != 0)

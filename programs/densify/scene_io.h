@@ -72,8 +72,9 @@ struct CloudPoint {
     float normal[3];
 };
 
-// ASCII PLY exactly as PrintCloud writes it (%g floats, uchar colours)
-void write_ply(const std::string &path, const std::vector<CloudPoint> &pts);
+// ASCII PLY exactly as PrintCloud writes it (%g floats, uchar colours); with
+// exact_positions x y z are %.9g, which reads back to the same float
+void write_ply(const std::string &path, const std::vector<CloudPoint> &pts, bool exact_positions = false);
 
 struct MeshPoint {
     float pos[3];
