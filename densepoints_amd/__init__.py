@@ -34,12 +34,15 @@ from .pmvs import (  # noqa: F401
     check_mesh_clean_args,
     check_mesh_colour_args,
     check_mesh_decimate_args,
+    check_mesh_nearest_args,
     check_mesh_render_args,
     check_mesh_smooth_args,
     check_tsdf_args,
     cloud_compare,
     empty_patches,
     mask_from_list,
+    mesh_compare,
+    mesh_deviation,
     ncc_score,
     read_pfm,
     read_scene_json,

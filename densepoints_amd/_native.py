@@ -400,6 +400,21 @@ class DpCloudNearestStats(ctypes.Structure):
 assert ctypes.sizeof(DpCloudNearestOptions) == 12 and ctypes.sizeof(DpCloudNearestStats) == 80
 
 
+class DpMeshNearestOptions(ctypes.Structure):
+    """dp_mesh_nearest_options: the options of dp_mesh_nearest (include/densepoints.h)."""
+    _fields_ = [("max_dist", ctypes.c_float), ("hist_bins", ctypes.c_int32), ("flags", ctypes.c_int32)]
+
+
+class DpMeshNearestStats(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int64) for n in (
+        "queries", "skipped_queries", "matched", "unmatched", "triangles", "invalid_triangles", "degenerate_triangles",
+        "nonfinite_triangles", "grid_cells", "grid_entries", "max_cell_entries")] + [
+        ("build_ms", ctypes.c_double), ("query_ms", ctypes.c_double)]
+
+
+assert ctypes.sizeof(DpMeshNearestOptions) == 12 and ctypes.sizeof(DpMeshNearestStats) == 104
+
+
 class DpSynthConfig(ctypes.Structure):
     _fields_ = [
         ("n_views", ctypes.c_int32),
@@ -562,6 +577,10 @@ SIGNATURES = [
                               _P]),
     ("dp_cloud_nearest_device", _I, [_P, _P, ctypes.c_int64, ctypes.c_int64, _P, ctypes.c_int64, ctypes.c_int64, _P, _P,
                                      _P, _P, _P, _P]),
+    ("dp_mesh_nearest", _I, [_P, _P, ctypes.c_int64, ctypes.c_int64, _P, ctypes.c_int64, _P, ctypes.c_int64, _P, _P, _P, _P,
+                             _P, _P]),
+    ("dp_mesh_nearest_device", _I, [_P, _P, ctypes.c_int64, ctypes.c_int64, _P, ctypes.c_int64, _P, ctypes.c_int64, _P,
+                                    _P, _P, _P, _P, _P, _P]),
     ("dp_last_kernel_ms", _I, [_P, _P]),
     ("dp_default_matcher_options", None, [_P]),
     ("dp_orb_pattern", _I, [_P]),

@@ -9,7 +9,7 @@
 // components; dp_meshsmooth.hip: its adjacency, smoothing and normals;
 // dp_meshdecimate.hip: its simplification; dp_meshrender.hip: its maps;
 // dp_meshcolour.hip: its colours; dp_cloudnearest.hip: nearest points between
-// two clouds -- each
+// two clouds; dp_meshnearest.hip: nearest triangles of a mesh -- each
 // with its scratch as one named member of the context and
 // the host helpers they share at the end of this file).  Every member that
 // owns a device or pinned allocation or an event has an owning type
@@ -244,6 +244,39 @@ struct CloudNearestScratch {
     Timer time[2]; // the grid; the queries
 };
 
+// dp_mesh_nearest's search grid, made on the device (meshnear_plan_kernel,
+// meshnear_pick_kernel): isotropic cells of side0 * 2^level from one origin,
+// cell (x, y, z) with the key (z * n[1] + y) * n[0] + x
+struct MeshNearGrid {
+    double origin[3], ext[3], side0, side;
+    int32_t n[3];
+    int32_t level_min; // the first level whose cells fit the cap
+    int32_t level;     // the chosen one
+    int32_t maxcell;   // the most registrations in one cell
+    int64_t cells, entries;
+};
+
+// dp_mesh_nearest.  The triangles: the per-block bounding boxes, the grid, the
+// per-level registration counts, the cells' counts and first entries (cap + 1
+// each), the registrations (triangle and first-cell bits).  The queries: their
+// cell keys and numbers and the sorted copies.  The host form's staged inputs,
+// device results (index, dist, closest, hist) and pinned results.
+struct MeshNearestScratch {
+    DevBuf<float> boxes;
+    DevBuf<MeshNearGrid> grid;
+    DevBuf<unsigned long long> levels;
+    DevBuf<int32_t> cellcount, begin, entries;
+    DevBuf<uint8_t> first;
+    DevBuf<uint32_t> qkeys, qkeys_sorted;
+    DevBuf<int32_t> qidx, qidx_sorted;
+    StripedCounters count; // + the grid
+    DevBuf<unsigned char> in, out;
+    HostBuf<int32_t> hindex;
+    HostBuf<float> hdist, hclosest;
+    HostBuf<uint64_t> hhist;
+    Timer time[2]; // the grid; the queries
+};
+
 } // namespace dpk
 
 struct SeedgenFree {
@@ -303,6 +336,7 @@ struct dp_ctx {
     dpk::MeshRenderScratch meshrender;
     dpk::MeshColourScratch meshcolour;
     dpk::CloudNearestScratch cloudnearest;
+    dpk::MeshNearestScratch meshnearest;
     HostBuf<dp_patch> result; // dp_densify / dp_densify_result output (pinned)
     // dp_densify_iterate: per iteration {evaluations, filter survivors} on the
     // device (read once, at the end) and the filters' timing events

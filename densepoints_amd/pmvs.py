@@ -42,6 +42,9 @@ __all__ = [
     "check_mesh_colour_args",
     "check_cloud_nearest_args",
     "cloud_compare",
+    "check_mesh_nearest_args",
+    "mesh_compare",
+    "mesh_deviation",
     "check_mesh_decimate_args",
     "check_mesh_render_args",
     "check_mesh_smooth_args",
@@ -1281,6 +1284,67 @@ class Engine:
         return _stats_dict(st) if stats else None
 
 
+    # ---- nearest triangles of a mesh (include/densepoints.h dp_mesh_nearest) ----
+    def mesh_nearest(self, queries, vertices, triangles, max_dist: float, hist_bins: int = 0,
+                     closest: bool = False) -> dict:
+        """dp_mesh_nearest: for every query the nearest triangle of the mesh
+        within max_dist (ties to the lowest index).  `queries` is what
+        cloud_nearest takes; `vertices` MESH_VERTEX_DTYPE records or an (n, 3)
+        array; `triangles` n x 3 integers.  Returns {"index" (int32, -1 = none),
+        "dist" (float32, inf = none), "closest" (n x 3 float32, or None), "hist"
+        (uint64 per bin, or None), "stats"}.  Needs no views."""
+        qa, qp, nq, qs = _cloud_points("mesh_nearest", queries)
+        verts = _mesh_vertices("mesh_nearest", vertices)
+        tris = _mesh_triangles("mesh_nearest", triangles)
+        nv, nt = len(verts), len(tris)
+        mno = check_mesh_nearest_args(nq, nv, nt, max_dist, hist_bins, qs)
+        pi, pd, pc, ph = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
+        st = N.DpMeshNearestStats()
+        self._check(lib.dp_mesh_nearest(self._ctx, _addr(qp) if nq else None, nq, qs, ptr(verts) if nv else None, nv,
+                                        ptr(tris) if nt else None, nt, ctypes.byref(mno), ctypes.byref(pi),
+                                        ctypes.byref(pd), ctypes.byref(pc) if closest else None,
+                                        ctypes.byref(ph) if hist_bins else None, ctypes.byref(st)))
+        index, dist = np.zeros(nq, np.int32), np.zeros(nq, np.float32)
+        where = np.zeros((nq, 3), np.float32) if closest else None
+        if nq:
+            ctypes.memmove(index.ctypes.data, pi.value, index.nbytes)
+            ctypes.memmove(dist.ctypes.data, pd.value, dist.nbytes)
+            if closest:
+                ctypes.memmove(where.ctypes.data, pc.value, where.nbytes)
+        hist = None
+        if hist_bins:
+            hist = np.zeros(hist_bins, np.uint64)
+            ctypes.memmove(hist.ctypes.data, ph.value, hist.nbytes)
+        del qa
+        return {"index": index, "dist": dist, "closest": where, "hist": hist, "stats": _stats_dict(st)}
+
+    def mesh_nearest_device(self, d_queries, n_queries: int, query_stride: int, d_vertices, n_vertices: int,
+                            d_triangles, n_triangles: int, max_dist: float, d_index, d_dist, d_closest=None,
+                            d_hist=None, hist_bins: int = 0, stream: int | None = None,
+                            stats: bool = True) -> dict | None:
+        """dp_mesh_nearest_device: device queries (the address of the first
+        point, the stride in bytes) against a device mesh (addresses) into
+        n_queries int32 at d_index and float32 at d_dist, 3 * n_queries float32 at
+        d_closest and hist_bins uint64 at d_hist when those are given.  Queued on
+        `stream`; waits only for the statistics (stats=False: no wait, returns
+        None)."""
+        who = "mesh_nearest_device"
+        nq, nv, nt = _mesh_count(who, n_queries), _mesh_count(who, n_vertices), _mesh_count(who, n_triangles)
+        mno = check_mesh_nearest_args(nq, nv, nt, max_dist, hist_bins, query_stride,
+                                      inputs=(d_queries, d_vertices, d_triangles),
+                                      outputs=(d_index, d_dist, d_closest, d_hist))
+        if (nq and not d_queries) or (nv and not d_vertices) or (nt and not d_triangles):
+            raise ValueError("mesh_nearest_device: the queries, the vertices and the triangles must be given")
+        if nq and not (d_index and d_dist):
+            raise ValueError("mesh_nearest_device: d_index and d_dist must be given")
+        st = N.DpMeshNearestStats()
+        self._check(lib.dp_mesh_nearest_device(self._ctx, _addr(d_queries), nq, query_stride, _addr(d_vertices), nv,
+                                               _addr(d_triangles), nt, ctypes.byref(mno), _addr(d_index),
+                                               _addr(d_dist), _addr(d_closest), _addr(d_hist),
+                                               ctypes.byref(st) if stats else None, _addr(stream)))
+        return _stats_dict(st) if stats else None
+
+
 def _cloud_points(who: str, a):
     """A cloud as dp_cloud_nearest takes it: (the array that owns the memory,
     the address of the first point, the count, the stride in bytes)."""
@@ -1383,6 +1447,74 @@ def cloud_compare(eng, recon, truth, tau: float, max_dist=None) -> dict:
     com = cloud_side(eng.cloud_nearest(truth, recon, max_dist), tau)
     p, r = acc["ratio"], com["ratio"]
     return {"accuracy": acc, "completeness": com, "fscore": 2.0 * p * r / (p + r) if p + r > 0 else 0.0}
+
+
+def _mesh_vertices(who: str, vertices) -> np.ndarray:
+    """Mesh vertices as dp_mesh_vertex records: MESH_VERTEX_DTYPE as it is, an
+    (n, 3) array as records with zero colours."""
+    v = np.asarray(vertices)
+    if v.dtype.names:
+        return np.ascontiguousarray(v, dtype=N.MESH_VERTEX_DTYPE).reshape(-1)
+    if v.size == 0:
+        return np.zeros(0, N.MESH_VERTEX_DTYPE)
+    if v.ndim != 2 or v.shape[1] != 3:
+        raise ValueError("%s: vertices must be MESH_VERTEX_DTYPE records or an n x 3 array" % who)
+    out = np.zeros(len(v), N.MESH_VERTEX_DTYPE)
+    out["pos"] = v
+    return out
+
+
+def check_mesh_nearest_args(n_queries, n_vertices, n_triangles, max_dist, hist_bins=0, query_stride=12, flags=0,
+                            inputs=(), outputs=()):
+    """Argument validation of Engine.mesh_nearest[_device] (the limits of
+    dp_mesh_nearest, raised as ValueError before any device call); returns the
+    dp_mesh_nearest_options.  The rules are check_cloud_nearest_args'."""
+    try:
+        _mesh_count("mesh_nearest", n_vertices)
+        cno = check_cloud_nearest_args(n_queries, n_triangles, max_dist, hist_bins, query_stride, 12, flags, inputs,
+                                       outputs)
+    except ValueError as e:
+        raise ValueError(str(e).replace("cloud_nearest", "mesh_nearest").replace("n_targets", "n_triangles")) from None
+    return N.DpMeshNearestOptions(cno.max_dist, cno.hist_bins, cno.flags)
+
+
+def mesh_compare(eng, vertices, triangles, truth, tau: float, max_dist=None) -> dict:
+    """cloud_compare for a mesh: accuracy is the mesh's vertices -> the truth
+    points (Engine.cloud_nearest, as for a cloud), completeness the truth points
+    -> the mesh's surface (Engine.mesh_nearest), each a cloud_side, and fscore
+    from their ratios as in cloud_compare."""
+    max_dist = check_cloud_compare_args(tau, max_dist)
+    verts = _mesh_vertices("mesh_compare", vertices)
+    acc = cloud_side(eng.cloud_nearest(verts, truth, max_dist), tau)
+    com = cloud_side(eng.mesh_nearest(truth, verts, triangles, max_dist), tau)
+    p, r = acc["ratio"], com["ratio"]
+    return {"accuracy": acc, "completeness": com, "fscore": 2.0 * p * r / (p + r) if p + r > 0 else 0.0}
+
+
+def deviation_side(nearest: dict) -> dict:
+    """One direction of mesh_deviation from a mesh_nearest result: n (queries
+    taking part), matched, and mean, median, p90 (cloud_quantile) and max of the
+    matched float32 distances in fp64, NaN when none matched."""
+    d = np.sort(nearest["dist"][nearest["index"] >= 0].astype(np.float64))
+    nan = float("nan")
+    return {"n": int(nearest["stats"]["queries"]), "matched": int(nearest["stats"]["matched"]),
+            "mean": float(d.mean()) if len(d) else nan, "median": cloud_quantile(d, 0.5), "p90": cloud_quantile(d, 0.9),
+            "max": float(d[-1]) if len(d) else nan}
+
+
+def mesh_deviation(eng, a, b, max_dist: float) -> dict:
+    """How far two meshes a = (vertices, triangles) and b lie apart: the vertices
+    of a against the surface of b ("a_to_b") and b's against a's ("b_to_a"), each
+    a deviation_side of an Engine.mesh_nearest call with the radius max_dist, and
+    "max", the larger of the two maxima (NaN when nothing matched either way).
+    Vertices beyond max_dist of the other surface are unmatched and enter no
+    figure but n - matched."""
+    (va, ta), (vb, tb) = a, b
+    va, vb = _mesh_vertices("mesh_deviation", va), _mesh_vertices("mesh_deviation", vb)
+    ab = deviation_side(eng.mesh_nearest(va, vb, tb, max_dist))
+    ba = deviation_side(eng.mesh_nearest(vb, va, ta, max_dist))
+    tops = [s["max"] for s in (ab, ba) if not np.isnan(s["max"])]
+    return {"a_to_b": ab, "b_to_a": ba, "max": max(tops) if tops else float("nan")}
 
 
 def _stats_dict(st) -> dict:
@@ -2052,13 +2184,17 @@ class PMVS:
         self.stats["mesh_render"] = out["stats"]
         return out
 
-    def evaluate(self, truth, tau: float, max_dist=None, cloud="patches") -> dict:
+    def evaluate(self, truth, tau: float, max_dist=None, cloud="patches", mesh=None) -> dict:
         """Accuracy, completeness and F-score (cloud_compare) of a cloud of the
         last run() against the ground-truth cloud `truth` at the threshold tau.
         cloud: "patches" (the stored patches), "fused" (fused_cloud()'s points),
         or a cloud of the caller's -- an (n, 3) array or a structured array with
-        a pos field, for example the vertices mesh() returned."""
+        a pos field, for example the vertices mesh() returned.  mesh = (vertices,
+        triangles) evaluates that mesh's surface instead (mesh_compare)."""
         check_cloud_compare_args(tau, max_dist)
+        if mesh is not None:
+            with Engine(self.options, self.device) as eng:
+                return mesh_compare(eng, mesh[0], mesh[1], truth, tau, max_dist)
         if isinstance(cloud, str):
             if cloud not in ("patches", "fused"):
                 raise ValueError('evaluate: cloud must be "patches", "fused" or an array')

@@ -1475,6 +1475,114 @@ int dp_cloud_nearest_device(dp_ctx *ctx, const void *d_queries, int64_t n_querie
                             const dp_cloud_nearest_options *opts, int32_t *d_index, float *d_dist,
                             uint64_t *d_hist, dp_cloud_nearest_stats *stats, void *stream);
 
+/* ---- nearest-triangle distances from points to a mesh surface ---------------------
+ * No reference counterpart.  For every query point the nearest triangle of a
+ * mesh within a radius, its distance and the closest point on it: the primitive
+ * under the completeness of a mesh against a ground truth and under the
+ * deviation between two meshes (mesh_compare and mesh_deviation in the Python
+ * package, densify --eval-mesh-surface).  The conventions are dp_cloud_nearest's
+ * except where stated.  All arithmetic is fp64, one IEEE rounding per operation,
+ * in exactly the order written (the build has -ffp-contract=off); dvdiv and
+ * dvsqrt are the IEEE-correct fp64 quotient and square root, (float) and
+ * (double) the IEEE conversions.
+ *
+ * Inputs: n_queries points, three consecutive f32 at base + i * stride (bytes, a
+ * multiple of 4, at least 12); n_vertices 16-byte dp_mesh_vertex records, of
+ * which only pos is read; n_triangles index triples.  No view is read.
+ *
+ * Who takes part.  A query TAKES PART iff its three floats are finite; one that
+ * does not gets index -1, dist +inf and closest (+inf, +inf, +inf) and counts in
+ * skipped_queries.  A triangle is VALID, DEGENERATE or PROPER as in the smoothing
+ * section (by its indices alone; no index is used as an address before its range
+ * check); invalid and degenerate ones count in invalid_triangles and
+ * degenerate_triangles.  A proper triangle TAKES PART iff its nine coordinates
+ * are finite; the others count in nonfinite_triangles, those taking part in
+ * `triangles`:  triangles + invalid_triangles + degenerate_triangles +
+ * nonfinite_triangles = n_triangles.  A proper triangle whose positions coincide
+ * or are collinear takes part: its edges answer for it.
+ *
+ * Distance of q to the triangle (a, b, c), everything widened to double first:
+ *   ab = b - a, ac = c - a, bc = c - b, ca = a - c, ap = q - a, bp = q - b,
+ *   cp = q - c (componentwise);  dot(u, v) = (ux*vx + uy*vy) + uz*vz;
+ *   cross(u, v) = (uy*vz - uz*vy, uz*vx - ux*vz, ux*vy - uy*vx)   (dp_mesh_normals' order).
+ *   Segment (s, e) with sp = q - s:  se = e - s;  den = dot(se, se);
+ *     t = den > 0 ? dvdiv(dot(sp, se), den) : 0, then t < 0 becomes 0 and t > 1
+ *     becomes 1;  r_k = sp_k - t * se_k;  d2 = dot(r, r);  point_k = (float)(s_k +
+ *     t * se_k).  The segments are (a, b) with sp = ap and se = ab, (b, c) with bp
+ *     and bc, (c, a) with cp and ca.
+ *   Plane:  n = cross(ab, ac);  nn = dot(n, n).  The plane is USED iff
+ *     nn > (dot(ab, ab) * dot(ac, ac)) * 2^-40  (the conditioning of the cross
+ *     product: below it the edges describe the sliver to better than 10^-6 of its
+ *     length) and dot(cross(ab, ap), n) >= 0 and dot(cross(bc, bp), n) >= 0 and
+ *     dot(cross(ca, cp), n) >= 0.  Then s = dvdiv(dot(ap, n), nn);  r_k = s * n_k;
+ *     d2 = dot(r, r);  point_k = (float)(q_k - r_k).
+ *   The triangle's d2 and point are those of the smallest d2 among the plane (if
+ *   used), (a, b), (b, c), (c, a), in that order; a later one replaces an earlier
+ *   one only when strictly smaller.
+ *
+ * Candidates.  R = (double)max_dist, R2 = R * R, G = R + R * 2^-20.  With lo_k and
+ * hi_k the smallest and the largest of the triangle's three f32 coordinates on
+ * axis k, triangle T is a CANDIDATE of q iff
+ *   (double)lo_k - G <= (double)q_k  and  (double)q_k <= (double)hi_k + G  on every axis k,
+ *   and d2 <= R2 (inclusive).
+ * The box test is part of the spec on purpose.  Mathematically it excludes no
+ * triangle within max_dist, since the closest point lies in the box; it makes the
+ * answer a function of the mesh, the queries and max_dist alone even for slivers
+ * whose computed d2 is noise, so that a grid implementation can be proved equal
+ * to brute force.
+ * The answer of q is the candidate with the smallest d2; equal d2 goes to the
+ * lowest triangle index.  index[q] = that triangle's index in the caller's array,
+ * dist[q] = (float)dvsqrt(d2), closest[3q .. 3q + 2] = its point, and q counts in
+ * matched.  A query with no candidate gets -1, +inf and (+inf, +inf, +inf) and
+ * counts in unmatched.  The histogram is exactly dp_cloud_nearest's.
+ * queries + skipped_queries = n_queries, matched + unmatched = queries.
+ * n_queries = 0 and n_triangles = 0 are legal.
+ *
+ * Tie to dp_cloud_nearest: every vertex of a triangle starts one of its three
+ * segments, and t = 0 gives the point-to-point d2 bit for bit, so with the same
+ * max_dist dist[q] here is never above dp_cloud_nearest's against the vertices
+ * that triangles taking part name.
+ *
+ * grid_cells (at most 2^24), grid_entries (triangle registrations, at most 8 *
+ * n_triangles) and max_cell_entries describe the search grid of the
+ * implementation, not the spec.  build_ms = device time of the grid's
+ * construction, query_ms = of the queries' sort and walk.
+ * Errors (DP_E_ARG): dp_cloud_nearest's (counts, strides, opts, max_dist,
+ * hist_bins, flags, an output that equals an input), and vertices or triangles
+ * NULL with a positive count; device form: d_index or d_dist NULL with n_queries
+ * > 0.
+ * Host form: *index, *dist (both required), *closest (3 floats per query; pass
+ * closest = NULL when not wanted) and *hist are context-owned, valid until the
+ * next dp_mesh_nearest or destroy.  Device form: caller buffers, d_closest and
+ * d_hist optional; everything is queued on `stream` (NULL = the context's) and
+ * the call waits only when stats != NULL.
+ * Limits: one nearest triangle, unsigned distance.  Scratch is at most 8
+ * registrations of 5 bytes per triangle, 16 bytes per query and the cell table
+ * (8 bytes per cell, at most 2^24 + 1 cells), whatever the extent, max_dist and
+ * the triangles' sizes are. */
+typedef struct dp_mesh_nearest_options {
+    float max_dist;     /* search radius, world units (> 0, finite; no default) */
+    int32_t hist_bins;  /* 0 = no histogram; else 1..65536                     */
+    int32_t flags;      /* none defined; non-zero is DP_E_ARG                  */
+} dp_mesh_nearest_options;
+typedef struct dp_mesh_nearest_stats {
+    int64_t queries, skipped_queries, matched, unmatched;
+    int64_t triangles, invalid_triangles, degenerate_triangles, nonfinite_triangles;
+    int64_t grid_cells, grid_entries, max_cell_entries;  /* facts of the implementation, not of the spec */
+    double build_ms, query_ms;
+} dp_mesh_nearest_stats;
+
+int dp_mesh_nearest(dp_ctx *ctx, const void *queries, int64_t n_queries, int64_t query_stride,
+                    const dp_mesh_vertex *vertices, int64_t n_vertices, const int32_t *triangles,
+                    int64_t n_triangles, const dp_mesh_nearest_options *opts, const int32_t **index,
+                    const float **dist, const float **closest, const uint64_t **hist,
+                    dp_mesh_nearest_stats *stats);
+int dp_mesh_nearest_device(dp_ctx *ctx, const void *d_queries, int64_t n_queries, int64_t query_stride,
+                           const dp_mesh_vertex *d_vertices, int64_t n_vertices, const int32_t *d_triangles,
+                           int64_t n_triangles, const dp_mesh_nearest_options *opts, int32_t *d_index,
+                           float *d_dist, float *d_closest, uint64_t *d_hist, dp_mesh_nearest_stats *stats,
+                           void *stream);
+
 /* ---- seed generation: Features::Matcher::GenerateSeeds ---
  * modules/features/matcher.cpp:18-43 with the default MatcherOptions
  * (matcher.h:21-32: ORB detector, kNN matcher, no direct epipolar matching,

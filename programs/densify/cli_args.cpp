@@ -89,6 +89,12 @@ void usage()
                  "                             line as --seeds reads them, on the device -- dp_cloud_nearest;\n"
                  "                             the report gains accuracy, completeness and F-score at the\n"
                  "                             threshold T > 0; D = search radius >= T, default 10 T)\n"
+                 "               [--eval-mesh-surface]\n"
+                 "                            (with --evaluate and --mesh: the report gains mesh_surface, the\n"
+                 "                             mesh's vertices against the truth and the truth against the\n"
+                 "                             mesh's surface -- dp_mesh_nearest -- and, with --mesh-decimate,\n"
+                 "                             decimate_deviation: how far the decimated surface lies from\n"
+                 "                             the one it was made of, within the radius D)\n"
                  "       densify --synthetic V,W,H,KIND --write-scene DIR\n");
 }
 
@@ -145,6 +151,7 @@ bool set_flag(const std::string &o, Args &a)
     else if (o == "--mesh-cull-back") a.mesh_cull_back = true;
     else if (o == "--mesh-colour") a.mesh_colour = true;
     else if (o == "--mesh-colour-bilinear") a.mesh_colour_bilinear = true;
+    else if (o == "--eval-mesh-surface") a.eval_mesh_surface = true;
     else if (o == "--epipolar-matching") a.matcher.epipolar_matching = 1;
     else return false;
     return true;
@@ -360,6 +367,10 @@ Parse parse_args(int argc, char **argv, Args &a, std::string &error)
     }
     if (a.eval_path.empty() && (a.eval_tau > 0.0 || a.eval_max_dist > 0.0)) {
         error = "--eval-tau and --eval-max-dist need --evaluate";
+        return Parse::UsageError;
+    }
+    if (a.eval_mesh_surface && (a.eval_path.empty() || a.mesh_path.empty())) {
+        error = "--eval-mesh-surface needs --evaluate and --mesh";
         return Parse::UsageError;
     }
     if (!a.eval_path.empty()) {

@@ -70,6 +70,10 @@ struct Args {
     std::string eval_path;
     double eval_tau = 0.0;      // 0: not given
     double eval_max_dist = 0.0; // 0: not given; parse_args resolves it to 10 x eval_tau
+    // --eval-mesh-surface: with --evaluate and --mesh, the mesh's surface against
+    // the truth (dp_mesh_nearest) and, with --mesh-decimate, the deviation of the
+    // decimated surface from the one before, in the report
+    bool eval_mesh_surface = false;
 
     Args();
 };

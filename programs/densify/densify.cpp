@@ -478,39 +478,118 @@ struct Evaluation {
         return buf;
     }
 
-    // one direction: its entry; *ratio = within_tau / n
-    std::string side(const void *d_q, int64_t nq, int64_t qs, const void *d_t, int64_t nt, int64_t ts, double *ratio)
-    {
+    // the results of one search: nq indices and distances on the device
+    struct Found {
         DeviceMaps out;
-        int32_t *d_index = (int32_t *)out.bytes((size_t)nq * 4, "--evaluate");
-        float *d_dist = (float *)out.bytes((size_t)nq * 4, "--evaluate");
-        const dp_cloud_nearest_options o{max_dist, 0, 0};
-        dp_cloud_nearest_stats st;
-        check(ctx,
-              dp_cloud_nearest_device(ctx, nq ? d_q : nullptr, nq, qs, nt ? d_t : nullptr, nt, ts, &o, d_index, d_dist,
-                                      nullptr, &st, nullptr),
-              "dp_cloud_nearest_device");
+        int32_t *d_index = nullptr;
+        float *d_dist = nullptr;
+        Found(int64_t nq)
+        {
+            d_index = (int32_t *)out.bytes((size_t)nq * 4, "--evaluate");
+            d_dist = (float *)out.bytes((size_t)nq * 4, "--evaluate");
+        }
+    };
+
+    // the matched distances of a search, ascending, and their sum in index order
+    static std::vector<double> matched_distances(const Found &f, int64_t nq, double *sum)
+    {
         std::vector<int32_t> index((size_t)nq);
         std::vector<float> dist((size_t)nq);
-        if (nq > 0 && (hipMemcpy(index.data(), d_index, (size_t)nq * 4, hipMemcpyDeviceToHost) != hipSuccess ||
-                       hipMemcpy(dist.data(), d_dist, (size_t)nq * 4, hipMemcpyDeviceToHost) != hipSuccess))
+        if (nq > 0 && (hipMemcpy(index.data(), f.d_index, (size_t)nq * 4, hipMemcpyDeviceToHost) != hipSuccess ||
+                       hipMemcpy(dist.data(), f.d_dist, (size_t)nq * 4, hipMemcpyDeviceToHost) != hipSuccess))
             throw std::runtime_error("--evaluate: copy of the distances failed");
         std::vector<double> d;
-        double sum = 0.0;
-        int64_t within = 0;
+        *sum = 0.0;
         for (size_t i = 0; i < index.size(); ++i)
             if (index[i] >= 0) {
                 d.push_back((double)dist[i]);
-                sum += (double)dist[i];
-                within += (double)dist[i] <= tau ? 1 : 0;
+                *sum += (double)dist[i];
             }
         std::sort(d.begin(), d.end());
-        *ratio = st.queries > 0 ? (double)within / (double)st.queries : 0.0;
+        return d;
+    }
+
+    // one direction's entry from its search; *ratio = within_tau / n
+    std::string entry(const Found &f, int64_t nq, int64_t queries, int64_t matched, double *ratio) const
+    {
+        double sum = 0.0;
+        const std::vector<double> d = matched_distances(f, nq, &sum);
+        const int64_t within = (int64_t)(std::upper_bound(d.begin(), d.end(), tau) - d.begin());
+        *ratio = queries > 0 ? (double)within / (double)queries : 0.0;
         char buf[200];
         std::snprintf(buf, sizeof buf, "{\"n\": %lld, \"matched\": %lld, \"within_tau\": %lld, \"ratio\": %.17g, ",
-                      (long long)st.queries, (long long)st.matched, (long long)within, *ratio);
+                      (long long)queries, (long long)matched, (long long)within, *ratio);
         return std::string(buf) + "\"mean\": " + number(d.empty() ? std::nan("") : sum / (double)d.size()) +
                ", \"median\": " + number(quantile(d, 0.5)) + ", \"p90\": " + number(quantile(d, 0.9)) + "}";
+    }
+
+    // one direction between two clouds
+    std::string side(const void *d_q, int64_t nq, int64_t qs, const void *d_t, int64_t nt, int64_t ts, double *ratio)
+    {
+        Found f(nq);
+        const dp_cloud_nearest_options o{max_dist, 0, 0};
+        dp_cloud_nearest_stats st;
+        check(ctx,
+              dp_cloud_nearest_device(ctx, nq ? d_q : nullptr, nq, qs, nt ? d_t : nullptr, nt, ts, &o, f.d_index, f.d_dist,
+                                      nullptr, &st, nullptr),
+              "dp_cloud_nearest_device");
+        return entry(f, nq, st.queries, st.matched, ratio);
+    }
+
+    // points against the surface of a device mesh (dp_mesh_nearest_device)
+    dp_mesh_nearest_stats surface(const Found &f, const void *d_q, int64_t nq, int64_t qs, const dp_mesh_vertex *d_v,
+                                  int64_t nv, const int32_t *d_t, int64_t nt)
+    {
+        const dp_mesh_nearest_options o{max_dist, 0, 0};
+        dp_mesh_nearest_stats st;
+        check(ctx,
+              dp_mesh_nearest_device(ctx, nq ? d_q : nullptr, nq, qs, nv ? d_v : nullptr, nv, nt ? d_t : nullptr, nt, &o,
+                                     f.d_index, f.d_dist, nullptr, nullptr, &st, nullptr),
+              "dp_mesh_nearest_device");
+        return st;
+    }
+
+    // --eval-mesh-surface: the mesh's vertices against the truth and the truth
+    // against the mesh's surface
+    void add_mesh_surface(const dp_mesh_vertex *d_v, int64_t nv, const int32_t *d_t, int64_t nt)
+    {
+        double p = 0.0, r = 0.0;
+        const std::string acc = side(d_v, nv, sizeof(dp_mesh_vertex), d_truth, n_truth, 12, &p);
+        Found f(n_truth);
+        const dp_mesh_nearest_stats st = surface(f, d_truth, n_truth, 12, d_v, nv, d_t, nt);
+        const std::string com = entry(f, n_truth, st.queries, st.matched, &r);
+        char buf[64];
+        std::snprintf(buf, sizeof buf, "%.17g", p + r > 0.0 ? 2.0 * p * r / (p + r) : 0.0);
+        entries += std::string(entries.empty() ? "" : ", ") + "\"mesh_surface\": {\"accuracy\": " + acc +
+                   ", \"completeness\": " + com + ", \"fscore\": " + buf + "}";
+    }
+
+    // the vertices of one mesh against the surface of another: the entry and the largest distance
+    std::string deviation_side(const dp_mesh_vertex *d_q, int64_t nq, const dp_mesh_vertex *d_v, int64_t nv,
+                               const int32_t *d_t, int64_t nt, double *top)
+    {
+        Found f(nq);
+        const dp_mesh_nearest_stats st = surface(f, d_q, nq, sizeof(dp_mesh_vertex), d_v, nv, d_t, nt);
+        double sum = 0.0;
+        const std::vector<double> d = matched_distances(f, nq, &sum);
+        *top = d.empty() ? std::nan("") : d.back();
+        char buf[120];
+        std::snprintf(buf, sizeof buf, "{\"n\": %lld, \"matched\": %lld, ", (long long)st.queries, (long long)st.matched);
+        return std::string(buf) + "\"mean\": " + number(d.empty() ? std::nan("") : sum / (double)d.size()) +
+               ", \"median\": " + number(quantile(d, 0.5)) + ", \"p90\": " + number(quantile(d, 0.9)) +
+               ", \"max\": " + number(*top) + "}";
+    }
+
+    // --eval-mesh-surface with --mesh-decimate: mesh a (before) and mesh b (after), both ways
+    void add_deviation(const char *name, const dp_mesh_vertex *d_va, int64_t nva, const int32_t *d_ta, int64_t nta,
+                       const dp_mesh_vertex *d_vb, int64_t nvb, const int32_t *d_tb, int64_t ntb)
+    {
+        double ta = 0.0, tb = 0.0;
+        const std::string ab = deviation_side(d_va, nva, d_vb, nvb, d_tb, ntb, &ta);
+        const std::string ba = deviation_side(d_vb, nvb, d_va, nva, d_ta, nta, &tb);
+        const double top = std::isnan(ta) ? tb : (std::isnan(tb) ? ta : std::max(ta, tb));
+        entries += std::string(entries.empty() ? "" : ", ") + "\"" + name + "\": {\"a_to_b\": " + ab + ", \"b_to_a\": " +
+                   ba + ", \"max\": " + number(top) + "}";
     }
 
     // the cloud of n points at d_points (device memory, `stride` bytes apart) against the truth
@@ -764,6 +843,9 @@ std::string write_mesh(dp_ctx *ctx, const Args &args, int32_t V, const std::vect
     // --mesh-decimate: the vertices of every cell of F voxels merged where the
     // mesh lies (dp_mesh_decimate_device; the result is no larger than its input)
     std::string decimated;
+    const dp_mesh_vertex *d_before_verts = d_verts; // what --mesh-decimate was given (--eval-mesh-surface)
+    const int32_t *d_before_tris = d_tris;
+    const int64_t nv_before = nv, nt_before = nt;
     if (args.mesh_decimate > 0.0) {
         dp_mesh_decimate_options mdo;
         dp_default_mesh_decimate_options(&mdo);
@@ -925,6 +1007,12 @@ std::string write_mesh(dp_ctx *ctx, const Args &args, int32_t V, const std::vect
     dpio::write_mesh_ply(args.mesh_path, out, tris, args.mesh_normals ? &normals : nullptr);
     if (ev)
         ev->add("mesh_vertices", d_verts, nv, sizeof(dp_mesh_vertex));
+    if (ev && args.eval_mesh_surface) {
+        ev->add_mesh_surface(d_verts, nv, d_tris, nt);
+        if (args.mesh_decimate > 0.0)
+            ev->add_deviation("decimate_deviation", d_before_verts, nv_before, d_before_tris, nt_before, d_verts, nv,
+                              d_tris, nt);
+    }
     char buf[400];
     std::snprintf(buf, sizeof buf,
                   ", \"mesh\": {\"vertices\": %lld, \"triangles\": %lld, \"ms\": %.3f, \"dim\": [%d, %d, %d], "
