@@ -9,7 +9,8 @@ import pytest
 
 import densepoints_amd as dp
 from densepoints_amd import _native as N
-from densepoints_amd import synth
+
+from refinecases import Base, _unsafe_camera  # built per cell there; here at the default, 11
 
 pytestmark = pytest.mark.gpu
 
@@ -23,50 +24,6 @@ def same(gp, op, fields=FIELDS):
     assert len(gp) == len(op)
     for f in fields:
         assert gp[f].tobytes() == op[f].tobytes(), f"field {f} differs"
-
-
-class Base:
-    """30 views of the height field; per seed, the views in which the oracle
-    finds a window map at the seed's stored pose (checked pairwise: with two
-    visible views the score is -1 exactly when either map fails)."""
-
-    def __init__(self, orc):
-        cfg = synth.config(V, W, H, 1, seed_stride_px=12.0)
-        self.P, self.imgs, seeds = synth.scene_host(cfg)
-        self.S = orc.Scene(self.P, self.imgs)
-        pat = self.S.seeds_to_patches(seeds)
-        good = np.zeros((len(pat), V), bool)
-        for v in range(V):
-            for t0 in (0, 1):
-                if t0 == v:
-                    continue
-                q = pat.copy()
-                q["vis"][:, 0] = np.uint64((1 << t0) | (1 << v))
-                q["vis"][:, 1] = 0
-                self.S.refine(q, CELL, orc.MODE_EVAL)
-                ok = q["score"] > -1.0
-                if t0 == 0:
-                    ok0 = ok
-                else:
-                    ok1 = ok
-            # view v maps if it scores against either possible texture 0
-            good[:, v] = ok0 if v != 0 else ok1
-        good[:, 0] &= good[:, 1:].any(axis=1)
-        self.pat, self.good = pat, good
-
-    def with_visible(self, m, n=NCAND, spread=False):
-        """n patches whose visible set is m views that map at the stored pose
-        (the lowest ones, or spread over the whole range)."""
-        rows = np.flatnonzero(self.good.sum(axis=1) >= m)[:n]
-        assert len(rows) >= 32, f"only {len(rows)} seeds map in {m} views"
-        out = self.pat[rows].copy()
-        for k, r in enumerate(rows):
-            vs = np.flatnonzero(self.good[r])
-            vs = vs[np.linspace(0, len(vs) - 1, m).round().astype(int)] if spread else vs[:m]
-            assert len(set(vs.tolist())) == m
-            out["vis"][k, 0] = np.uint64(sum(1 << int(v) for v in vs))
-            out["vis"][k, 1] = 0
-        return out
 
 
 @pytest.fixture(scope="module")
@@ -138,24 +95,6 @@ def test_texture0_invalid_no_view_scores(engine, base, orc):
     assert (chk["score"] == -1.0).all()
     engine.set_views(views_of(P, imgs))
     run_both(engine, S, pat, (N.MODE_EVAL, N.MODE_FILTER, N.MODE_NM, N.MODE_EXPAND))
-
-
-def _unsafe_camera(X, n, s, angle):
-    """A camera 0.1 s above the patch centre X (normal n, side s) that looks
-    along the patch plane: its principal plane cuts the window, so two
-    corners project from behind it -- the square -> quad map's W changes sign
-    on the window, which TexMap::safe excludes -- and with a 30 px focal
-    length all four land inside the image."""
-    a = np.cross(n, [0.0, 0.0, 1.0] if abs(n[2]) < 0.9 else [1.0, 0.0, 0.0])
-    a /= np.linalg.norm(a)
-    b = np.cross(n, a)
-    z = np.cos(angle) * a + np.sin(angle) * b
-    y = -n
-    x = np.cross(y, z)
-    R = np.stack([x, y, z])
-    C = X + 0.1 * s * n
-    K = np.array([[30.0, 0, W / 2], [0, 30.0, H / 2], [0, 0, 1]])
-    return K @ np.hstack([R, -(R @ C)[:, None]])
 
 
 def test_unsafe_window_in_one_slot(engine, base, orc):
