@@ -415,6 +415,35 @@ class DpMeshNearestStats(ctypes.Structure):
 assert ctypes.sizeof(DpMeshNearestOptions) == 12 and ctypes.sizeof(DpMeshNearestStats) == 104
 
 
+class DpCloudKnnOptions(ctypes.Structure):
+    """dp_cloud_knn_options: the options of dp_cloud_knn (include/densepoints.h)."""
+    _fields_ = [("max_dist", ctypes.c_float), ("k", ctypes.c_int32), ("flags", ctypes.c_int32)]
+
+
+class DpCloudKnnStats(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int64) for n in (
+        "queries", "targets", "skipped_queries", "skipped_targets", "full", "partial", "empty", "neighbours",
+        "grid_cells", "max_cell_targets")] + [("build_ms", ctypes.c_double), ("query_ms", ctypes.c_double)]
+
+
+class DpCloudCleanOptions(ctypes.Structure):
+    """dp_cloud_clean_options: the options of dp_cloud_clean (include/densepoints.h)."""
+    _fields_ = [("max_dist", ctypes.c_float), ("k", ctypes.c_int32), ("min_neighbours", ctypes.c_int32),
+                ("std_mul", ctypes.c_float), ("flags", ctypes.c_int32)]
+
+
+class DpCloudCleanStats(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int64) for n in (
+        "points", "skipped", "eligible", "kept", "removed_sparse", "removed_far", "grid_cells",
+        "max_cell_targets")] + [(n, ctypes.c_double) for n in ("mu", "sigma", "threshold", "knn_ms", "clean_ms")]
+
+
+assert ctypes.sizeof(DpCloudKnnOptions) == 12 and ctypes.sizeof(DpCloudKnnStats) == 96
+assert ctypes.sizeof(DpCloudCleanOptions) == 20 and ctypes.sizeof(DpCloudCleanStats) == 104
+CLOUD_KNN_EXCLUDE_SELF = 1
+CLOUD_CLEAN_RADIUS_ONLY = 1
+
+
 class DpSynthConfig(ctypes.Structure):
     _fields_ = [
         ("n_views", ctypes.c_int32),
@@ -581,6 +610,11 @@ SIGNATURES = [
                              _P, _P]),
     ("dp_mesh_nearest_device", _I, [_P, _P, ctypes.c_int64, ctypes.c_int64, _P, ctypes.c_int64, _P, ctypes.c_int64, _P,
                                     _P, _P, _P, _P, _P, _P]),
+    ("dp_cloud_knn", _I, [_P, _P, ctypes.c_int64, ctypes.c_int64, _P, ctypes.c_int64, ctypes.c_int64, _P, _P, _P, _P, _P]),
+    ("dp_cloud_knn_device", _I, [_P, _P, ctypes.c_int64, ctypes.c_int64, _P, ctypes.c_int64, ctypes.c_int64, _P, _P, _P,
+                                 _P, _P, _P]),
+    ("dp_cloud_clean", _I, [_P, _P, ctypes.c_int64, ctypes.c_int64, _P, _P, _P, _P, _P, _P, _P]),
+    ("dp_cloud_clean_device", _I, [_P, _P, ctypes.c_int64, ctypes.c_int64, _P, _P, _P, _P, _P, _P, _P, _P]),
     ("dp_last_kernel_ms", _I, [_P, _P]),
     ("dp_default_matcher_options", None, [_P]),
     ("dp_orb_pattern", _I, [_P]),

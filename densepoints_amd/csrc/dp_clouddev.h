@@ -1,0 +1,74 @@
+// dp_clouddev.h -- what the searches over a point cloud's uniform grid share
+// (dp_cloudnearest.hip: one nearest target; dp_cloudknn.hip: the k nearest and
+// the outlier filter on them): the kernels' argument block, the guarded load of
+// a point, the cell expression, and the host entry that queues the grid.  The
+// grid kernels themselves (box, plan, keys, gather, begin, maxcell, query keys)
+// and the margin proof live in dp_cloudnearest.hip, which exports
+// cloud_grid_queue below; both searches use the scratch of c->cloudnearest,
+// since their calls never overlap on a context.
+#pragma once
+
+#include "dp_meshdev.h"
+
+namespace dpk {
+
+// targets, queries (taking part); then dp_cloud_nearest: matched, unmatched;
+// dp_cloud_knn: full, partial, empty, neighbours
+constexpr int kCloudCounters = 6;
+constexpr int kCloudStripes = 64;
+constexpr int kCloudBoxBlocks = 1024; // cloud_box_kernel's blocks, at most
+constexpr int kCloudCapMinBits = 16, kCloudCapMaxBits = 24;
+
+struct CloudArgs {
+    const char *targets, *queries;
+    int64_t nt, nq, tstride, qstride;
+    int32_t cap, nboxes; // the cell cap (a power of two); the boxes cloud_box_kernel wrote
+    int32_t bins, pad;
+    double R, R2; // (double)max_dist and its square
+    float *boxes;
+    CloudGrid *grid;
+    uint32_t *tkeys, *tkeys_sorted, *qkeys, *qkeys_sorted;
+    int32_t *tidx, *tidx_sorted, *qidx, *qidx_sorted, *begin;
+    float *tx, *ty, *tz;
+    int32_t *index;
+    float *dist;
+    unsigned long long *hist; // optional
+    unsigned long long *count; // kCloudStripes x kCloudCounters
+};
+
+__device__ __forceinline__ bool finite_f32(float x) { return fabsf(x) <= 3.402823466e+38f; }
+
+// point i of an array; false unless its three floats are finite
+__device__ __forceinline__ bool load_point(const char *base, int64_t stride, int64_t i, float p[3])
+{
+    const float *f = (const float *)(base + i * stride);
+    p[0] = f[0];
+    p[1] = f[1];
+    p[2] = f[2];
+    return finite_f32(p[0]) && finite_f32(p[1]) && finite_f32(p[2]);
+}
+
+// the cell coordinate of x on axis k, clamped to [lo, n + hi] in fp64 first: a
+// coordinate of 1e30 must not reach the conversion
+__device__ __forceinline__ int32_t cell_coord(const CloudGrid &g, int k, float x, double lo, double hi)
+{
+    double u = dpg::dvdiv((double)x - g.origin[k], g.cell[k]);
+    u = fmin(fmax(u, lo), (double)g.n[k] + hi);
+    return (int32_t)floor(u);
+}
+
+__device__ __forceinline__ uint32_t wave_stripe() { return blockIdx.x * (kMeshLanes / 64) + (threadIdx.x >> 6); }
+
+} // namespace dpk
+
+// Queues on s, into the scratch of c->cloudnearest, everything of a search but
+// its walk: the counters zeroed, the grid over the targets (timed by time[0]),
+// the queries' cell keys and their sort (time[1] begun; the caller ends it
+// after its own query kernel).  In: a's clouds, counts, strides, R and R2; out:
+// its cap and every scratch pointer.  index, dist, hist and bins stay the
+// caller's.  (dp_cloudnearest.hip)
+int cloud_grid_queue(dp_ctx *c, dpk::CloudArgs &a, hipStream_t s);
+
+// the counts, pointers and strides both searches check the same way
+int cloud_check_clouds(dp_ctx *c, const std::string &w, const void *queries, int64_t nq, int64_t qstride,
+                       const void *targets, int64_t nt, int64_t tstride);

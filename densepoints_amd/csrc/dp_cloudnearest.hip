@@ -41,7 +41,9 @@
 // integer, is monotonic and leaves the targets' range [0, n - 1] alone, so it
 // keeps that; a query more than a cell outside the box finds every run empty.
 // The cell only bounds the walk: the fp64 test d2 <= R2 decides.
-#include "dp_meshdev.h"
+// The argument block, load_point, cell_coord and the constants are
+// dp_clouddev.h's; cloud_grid_queue below is what dp_cloudknn.hip shares.
+#include "dp_clouddev.h"
 
 #include <hipcub/hipcub.hpp>
 
@@ -50,51 +52,6 @@
 
 namespace dpk {
 namespace {
-
-constexpr int kCloudCounters = 4; // targets, queries (taking part), matched, unmatched
-constexpr int kCloudStripes = 64;
-constexpr int kCloudBoxBlocks = 1024; // cloud_box_kernel's blocks, at most
-constexpr int kCloudCapMinBits = 16, kCloudCapMaxBits = 24;
-
-struct CloudArgs {
-    const char *targets, *queries;
-    int64_t nt, nq, tstride, qstride;
-    int32_t cap, nboxes; // the cell cap (a power of two); the boxes cloud_box_kernel wrote
-    int32_t bins, pad;
-    double R, R2; // (double)max_dist and its square
-    float *boxes;
-    CloudGrid *grid;
-    uint32_t *tkeys, *tkeys_sorted, *qkeys, *qkeys_sorted;
-    int32_t *tidx, *tidx_sorted, *qidx, *qidx_sorted, *begin;
-    float *tx, *ty, *tz;
-    int32_t *index;
-    float *dist;
-    unsigned long long *hist; // optional
-    unsigned long long *count; // kCloudStripes x kCloudCounters
-};
-
-__device__ __forceinline__ bool finite_f32(float x) { return fabsf(x) <= 3.402823466e+38f; }
-
-// point i of an array; false unless its three floats are finite
-__device__ __forceinline__ bool load_point(const char *base, int64_t stride, int64_t i, float p[3])
-{
-    const float *f = (const float *)(base + i * stride);
-    p[0] = f[0];
-    p[1] = f[1];
-    p[2] = f[2];
-    return finite_f32(p[0]) && finite_f32(p[1]) && finite_f32(p[2]);
-}
-
-// the cell coordinate of x on axis k, clamped to [lo, n + hi] in fp64 first: a
-// coordinate of 1e30 must not reach the conversion
-__device__ __forceinline__ int32_t cell_coord(const CloudGrid &g, int k, float x, double lo, double hi)
-{
-    double u = dpg::dvdiv((double)x - g.origin[k], g.cell[k]);
-    u = fmin(fmax(u, lo), (double)g.n[k] + hi);
-    return (int32_t)floor(u);
-}
-
-__device__ __forceinline__ uint32_t wave_stripe() { return blockIdx.x * (kMeshLanes / 64) + (threadIdx.x >> 6); }
 
 __global__ __launch_bounds__(kMeshLanes) void cloud_box_kernel(CloudArgs a)
 {
@@ -316,9 +273,9 @@ __global__ __launch_bounds__(kMeshLanes) void cloud_query_kernel(CloudArgs a)
 // C ABI
 // ---------------------------------------------------------------------------
 
-// argument checks shared by both forms (they need no device)
-static int cloud_check(dp_ctx *c, const std::string &w, const void *queries, int64_t nq, int64_t qstride,
-                       const void *targets, int64_t nt, int64_t tstride, const dp_cloud_nearest_options *o)
+// the counts, pointers and strides (dp_clouddev.h)
+int cloud_check_clouds(dp_ctx *c, const std::string &w, const void *queries, int64_t nq, int64_t qstride,
+                       const void *targets, int64_t nt, int64_t tstride)
 {
     if (nq < 0 || nt < 0 || nq > 0x7FFFFFFFll || nt > 0x7FFFFFFFll)
         return fail(c, DP_E_ARG, w + ": n_queries and n_targets must be in 0..2^31 - 1");
@@ -330,6 +287,16 @@ static int cloud_check(dp_ctx *c, const std::string &w, const void *queries, int
         return fail(c, DP_E_ARG, w + ": query_stride must be a multiple of 4 and at least 12");
     if (tstride < 12 || tstride % 4)
         return fail(c, DP_E_ARG, w + ": target_stride must be a multiple of 4 and at least 12");
+    return DP_OK;
+}
+
+// argument checks shared by both forms (they need no device)
+static int cloud_check(dp_ctx *c, const std::string &w, const void *queries, int64_t nq, int64_t qstride,
+                       const void *targets, int64_t nt, int64_t tstride, const dp_cloud_nearest_options *o)
+{
+    const int rc = cloud_check_clouds(c, w, queries, nq, qstride, targets, nt, tstride);
+    if (rc != DP_OK)
+        return rc;
     if (!o)
         return fail(c, DP_E_ARG, w + ": opts must be given");
     if (!(o->max_dist > 0.0f) || !std::isfinite(o->max_dist))
@@ -341,11 +308,10 @@ static int cloud_check(dp_ctx *c, const std::string &w, const void *queries, int
     return DP_OK;
 }
 
-// queues the search of device clouds on s
-static int cloud_queue(dp_ctx *c, const dp_cloud_nearest_options &o, const void *d_queries, int64_t nq, int64_t qstride,
-                       const void *d_targets, int64_t nt, int64_t tstride, int32_t *d_index, float *d_dist,
-                       uint64_t *d_hist, hipStream_t s)
+// the grid and the queries' cell order (dp_clouddev.h)
+int cloud_grid_queue(dp_ctx *c, dpk::CloudArgs &a, hipStream_t s)
 {
+    const int64_t nt = a.nt, nq = a.nq;
     dpk::CloudNearestScratch &r = c->cloudnearest;
     // the cap: the power of two at or above 2 * n_targets, within 2^16..2^24
     int cap_bits = dpk::kCloudCapMinBits;
@@ -371,18 +337,8 @@ static int cloud_queue(dp_ctx *c, const dp_cloud_nearest_options &o, const void 
     DP_HIP(c, r.qidx_sorted.reserve(q));
     DP_HIP(c, r.count.reserve(dpk::kCloudStripes, dpk::kCloudCounters, (sizeof(dpk::CloudGrid) + 7) / 8));
 
-    dpk::CloudArgs a{};
-    a.targets = (const char *)d_targets;
-    a.queries = (const char *)d_queries;
-    a.nt = nt;
-    a.nq = nq;
-    a.tstride = tstride;
-    a.qstride = qstride;
     a.cap = cap;
     a.nboxes = (int32_t)box_blocks;
-    a.bins = o.hist_bins;
-    a.R = (double)o.max_dist;
-    a.R2 = (double)o.max_dist * (double)o.max_dist;
     a.boxes = r.boxes.p;
     a.grid = r.grid.p;
     a.tkeys = r.tkeys.p;
@@ -397,9 +353,6 @@ static int cloud_queue(dp_ctx *c, const dp_cloud_nearest_options &o, const void 
     a.tx = r.tx.p;
     a.ty = r.ty.p;
     a.tz = r.tz.p;
-    a.index = d_index;
-    a.dist = d_dist;
-    a.hist = o.hist_bins > 0 ? (unsigned long long *)d_hist : nullptr;
     a.count = r.count.dev.p;
 
     size_t tmp = 0, b = 0;
@@ -416,8 +369,6 @@ static int cloud_queue(dp_ctx *c, const dp_cloud_nearest_options &o, const void 
     DP_HIP(c, c->scan_tmp.reserve(tmp ? tmp : 1));
 
     DP_HIP(c, r.count.zero(s));
-    if (a.hist)
-        DP_HIP(c, hipMemsetAsync(a.hist, 0, sizeof(unsigned long long) * (size_t)o.hist_bins, s));
     // the grid
     DP_HIP(c, r.time[0].begin(s));
     DP_HIP(c, dpk::launch_over(dpk::cloud_box_kernel, box_blocks, a, s));
@@ -440,8 +391,34 @@ static int cloud_queue(dp_ctx *c, const dp_cloud_nearest_options &o, const void 
         DP_HIP(c, hipcub::DeviceRadixSort::SortPairs(c->scan_tmp.p, b, a.qkeys, a.qkeys_sorted, a.qidx, a.qidx_sorted,
                                                      (int)nq, 0, end_bit, s));
     }
+    return DP_OK;
+}
+
+// queues the search of device clouds on s
+static int cloud_queue(dp_ctx *c, const dp_cloud_nearest_options &o, const void *d_queries, int64_t nq, int64_t qstride,
+                       const void *d_targets, int64_t nt, int64_t tstride, int32_t *d_index, float *d_dist,
+                       uint64_t *d_hist, hipStream_t s)
+{
+    dpk::CloudArgs a{};
+    a.targets = (const char *)d_targets;
+    a.queries = (const char *)d_queries;
+    a.nt = nt;
+    a.nq = nq;
+    a.tstride = tstride;
+    a.qstride = qstride;
+    a.bins = o.hist_bins;
+    a.R = (double)o.max_dist;
+    a.R2 = (double)o.max_dist * (double)o.max_dist;
+    a.index = d_index;
+    a.dist = d_dist;
+    a.hist = o.hist_bins > 0 ? (unsigned long long *)d_hist : nullptr;
+    if (a.hist)
+        DP_HIP(c, hipMemsetAsync(a.hist, 0, sizeof(unsigned long long) * (size_t)o.hist_bins, s));
+    const int rc = cloud_grid_queue(c, a, s);
+    if (rc != DP_OK)
+        return rc;
     DP_HIP(c, dpk::launch_over(dpk::cloud_query_kernel, dpk::mesh_blocks(nq), a, s));
-    DP_HIP(c, r.time[1].end(s));
+    DP_HIP(c, c->cloudnearest.time[1].end(s));
     return DP_OK;
 }
 

@@ -244,6 +244,30 @@ struct CloudNearestScratch {
     Timer time[2]; // the grid; the queries
 };
 
+// what dp_cloud_clean's one-lane statistics kernel keeps on the device between
+// its kernels: the eligible points, mu, sigma and the threshold T, the kept count
+struct CloudCleanDev {
+    double mu, sigma, threshold;
+    int64_t eligible, kept;
+};
+
+// dp_cloud_knn and dp_cloud_clean (dp_cloudknn.hip).  The grid, the sorted
+// targets and the queries' order are CloudNearestScratch's: the two searches
+// never overlap on a context.  Here: the host forms' staged inputs, device
+// results and pinned results (one buffer each, laid out by a PlanePacker); the
+// filter's self-search rows and counts, the points' mean distances, the two
+// buffers the pairwise-sum passes alternate between, the statistics block, the
+// keep flags as int32 with their exclusive scan (n + 1 entries each).
+struct CloudKnnScratch {
+    DevBuf<unsigned char> in, out;
+    HostBuf<unsigned char> hout;
+    DevBuf<int32_t> rows, rowcount, flag, pos;
+    DevBuf<double> mean, sum[2];
+    DevBuf<CloudCleanDev> dev;
+    StripedCounters count; // dp_cloud_clean's; + the grid and the statistics block
+    Timer time[2];         // dp_cloud_clean: the search; the filter
+};
+
 // dp_mesh_nearest's search grid, made on the device (meshnear_plan_kernel,
 // meshnear_pick_kernel): isotropic cells of side0 * 2^level from one origin,
 // cell (x, y, z) with the key (z * n[1] + y) * n[0] + x
@@ -336,6 +360,7 @@ struct dp_ctx {
     dpk::MeshRenderScratch meshrender;
     dpk::MeshColourScratch meshcolour;
     dpk::CloudNearestScratch cloudnearest;
+    dpk::CloudKnnScratch cloudknn;
     dpk::MeshNearestScratch meshnearest;
     HostBuf<dp_patch> result; // dp_densify / dp_densify_result output (pinned)
     // dp_densify_iterate: per iteration {evaluations, filter survivors} on the

@@ -1283,6 +1283,98 @@ class Engine:
                                                 _addr(d_hist), ctypes.byref(st) if stats else None, _addr(stream)))
         return _stats_dict(st) if stats else None
 
+    # ---- the k nearest neighbours between two clouds (include/densepoints.h dp_cloud_knn) ----
+    def cloud_knn(self, queries, targets, k: int, max_dist: float, exclude_self: bool = False) -> dict:
+        """dp_cloud_knn: for every query its k nearest targets within max_dist,
+        ordered by (distance, index).  The clouds are what cloud_nearest takes.
+        With exclude_self target i is never a neighbour of query i (the clouds
+        must have the same length).  Returns {"index" (n x k int32, -1 = none),
+        "dist" (n x k float32, inf = none), "count" (int32 per query), "stats"}.
+        Needs no views."""
+        qa, qp, nq, qs = _cloud_points("cloud_knn", queries)
+        ta, tp, nt, ts = _cloud_points("cloud_knn", targets)
+        cko = check_cloud_knn_args(nq, nt, k, max_dist, exclude_self, qs, ts)
+        pi, pd, pc, st = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p(), N.DpCloudKnnStats()
+        self._check(lib.dp_cloud_knn(self._ctx, _addr(qp) if nq else None, nq, qs, _addr(tp) if nt else None, nt, ts,
+                                     ctypes.byref(cko), ctypes.byref(pi), ctypes.byref(pd), ctypes.byref(pc),
+                                     ctypes.byref(st)))
+        index, dist = np.zeros((nq, cko.k), np.int32), np.zeros((nq, cko.k), np.float32)
+        count = np.zeros(nq, np.int32)
+        if nq:
+            ctypes.memmove(index.ctypes.data, pi.value, index.nbytes)
+            ctypes.memmove(dist.ctypes.data, pd.value, dist.nbytes)
+            ctypes.memmove(count.ctypes.data, pc.value, count.nbytes)
+        del qa, ta
+        return {"index": index, "dist": dist, "count": count, "stats": _stats_dict(st)}
+
+    def cloud_knn_device(self, d_queries, n_queries: int, query_stride: int, d_targets, n_targets: int,
+                         target_stride: int, k: int, max_dist: float, d_index, d_dist, d_count,
+                         exclude_self: bool = False, stream: int | None = None, stats: bool = True) -> dict | None:
+        """dp_cloud_knn_device: device clouds (the addresses of their first
+        points, strides in bytes) searched into n_queries x k int32 at d_index
+        and float32 at d_dist and n_queries int32 at d_count.  Queued on `stream`;
+        waits only for the statistics (stats=False: no wait, returns None)."""
+        nq, nt = _mesh_count("cloud_knn_device", n_queries), _mesh_count("cloud_knn_device", n_targets)
+        cko = check_cloud_knn_args(nq, nt, k, max_dist, exclude_self, query_stride, target_stride,
+                                   inputs=(d_queries, d_targets), outputs=(d_index, d_dist, d_count))
+        if (nq and not d_queries) or (nt and not d_targets):
+            raise ValueError("cloud_knn_device: the queries and the targets must be given")
+        if nq and not (d_index and d_dist and d_count):
+            raise ValueError("cloud_knn_device: d_index, d_dist and d_count must be given")
+        st = N.DpCloudKnnStats()
+        self._check(lib.dp_cloud_knn_device(self._ctx, _addr(d_queries), nq, query_stride, _addr(d_targets), nt,
+                                            target_stride, ctypes.byref(cko), _addr(d_index), _addr(d_dist),
+                                            _addr(d_count), ctypes.byref(st) if stats else None, _addr(stream)))
+        return _stats_dict(st) if stats else None
+
+    # ---- outlier removal of a cloud (include/densepoints.h dp_cloud_clean) ----
+    def cloud_clean(self, points, k: int, max_dist: float, std_mul: float = 2.0, min_neighbours: int = 1,
+                    radius_only: bool = False) -> dict:
+        """dp_cloud_clean: statistical (or, with radius_only, radius) outlier
+        removal.  `points` is what cloud_nearest takes; a structured array's pos
+        field must come first, and its records move whole.  Returns {"keep"
+        (uint8 per point), "mean_dist" (float32, inf = no neighbour), "map"
+        (int32, -1 = removed), "points" (the kept records, of the input's
+        dtype), "stats"}.  Needs no views."""
+        pa, pp, n, stride = _cloud_points("cloud_clean", points)
+        if pp != pa.ctypes.data:
+            raise ValueError("cloud_clean: the pos field must be the first of a record")
+        cco = check_cloud_clean_args(n, k, max_dist, std_mul, min_neighbours, radius_only, stride)
+        pk, pm, pi, po = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
+        n_out, st = ctypes.c_int64(0), N.DpCloudCleanStats()
+        self._check(lib.dp_cloud_clean(self._ctx, _addr(pp) if n else None, n, stride, ctypes.byref(cco),
+                                       ctypes.byref(pk), ctypes.byref(pm), ctypes.byref(pi), ctypes.byref(po),
+                                       ctypes.byref(n_out), ctypes.byref(st)))
+        keep, mean, where = np.zeros(n, np.uint8), np.zeros(n, np.float32), np.zeros(n, np.int32)
+        if n:
+            ctypes.memmove(keep.ctypes.data, pk.value, keep.nbytes)
+            ctypes.memmove(mean.ctypes.data, pm.value, mean.nbytes)
+            ctypes.memmove(where.ctypes.data, pi.value, where.nbytes)
+        kept = np.zeros((n_out.value,) + pa.shape[1:], pa.dtype)
+        if n_out.value:
+            ctypes.memmove(kept.ctypes.data, po.value, kept.nbytes)
+        return {"keep": keep, "mean_dist": mean, "map": where, "points": kept, "stats": _stats_dict(st)}
+
+    def cloud_clean_device(self, d_points, n: int, stride: int, k: int, max_dist: float, d_keep, d_mean_dist=None,
+                           d_map=None, d_out=None, d_n_out=None, std_mul: float = 2.0, min_neighbours: int = 1,
+                           radius_only: bool = False, stream: int | None = None, stats: bool = True) -> dict | None:
+        """dp_cloud_clean_device: n device records of `stride` bytes filtered
+        into n uint8 at d_keep and, where given, n float32 at d_mean_dist, n
+        int32 at d_map, the kept records at d_out (room for n) and their count as
+        one int64 at d_n_out.  Queued on `stream`; waits only for the statistics
+        (stats=False: no wait, returns None)."""
+        n = _mesh_count("cloud_clean_device", n)
+        cco = check_cloud_clean_args(n, k, max_dist, std_mul, min_neighbours, radius_only, stride,
+                                     inputs=(d_points,), outputs=(d_keep, d_mean_dist, d_map, d_out, d_n_out))
+        if n and not d_points:
+            raise ValueError("cloud_clean_device: the points must be given")
+        if n and not d_keep:
+            raise ValueError("cloud_clean_device: d_keep must be given")
+        st = N.DpCloudCleanStats()
+        self._check(lib.dp_cloud_clean_device(self._ctx, _addr(d_points), n, stride, ctypes.byref(cco), _addr(d_keep),
+                                              _addr(d_mean_dist), _addr(d_map), _addr(d_out), _addr(d_n_out),
+                                              ctypes.byref(st) if stats else None, _addr(stream)))
+        return _stats_dict(st) if stats else None
 
     # ---- nearest triangles of a mesh (include/densepoints.h dp_mesh_nearest) ----
     def mesh_nearest(self, queries, vertices, triangles, max_dist: float, hist_bins: int = 0,
@@ -1390,6 +1482,67 @@ def check_cloud_nearest_args(n_queries, n_targets, max_dist, hist_bins=0, query_
     if any(isinstance(o, (int, np.integer)) and o and o in ins for o in outputs):
         raise ValueError("cloud_nearest: an output equals an input")
     return N.DpCloudNearestOptions(float(max_dist), int(hist_bins), int(flags))
+
+
+def _cloud_search_args(who: str, k, max_dist):
+    """k and max_dist as dp_cloud_knn and dp_cloud_clean judge them."""
+    with np.errstate(over="ignore"):
+        if isinstance(max_dist, bool) or not isinstance(max_dist, (int, float, np.integer, np.floating)) or \
+                not (np.isfinite(np.float32(max_dist)) and np.float32(max_dist) > 0):
+            raise ValueError("%s: max_dist must be finite and > 0" % who)
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= k <= 32:
+        raise ValueError("%s: k must be in 1..32" % who)
+
+
+def _cloud_aliases(who: str, inputs, outputs, among_outputs=False):
+    ins = [a for a in inputs if isinstance(a, (int, np.integer)) and a]
+    outs = [o for o in outputs if isinstance(o, (int, np.integer)) and o]
+    if any(o in ins for o in outs):
+        raise ValueError("%s: an output equals an input" % who)
+    if among_outputs and len(set(outs)) != len(outs):
+        raise ValueError("%s: two outputs are equal" % who)
+
+
+def check_cloud_knn_args(n_queries, n_targets, k, max_dist, exclude_self=False, query_stride=12, target_stride=12,
+                         inputs=(), outputs=()):
+    """Argument validation of Engine.cloud_knn[_device] (the limits of
+    dp_cloud_knn, raised as ValueError before any device call); returns the
+    dp_cloud_knn_options.  max_dist is judged as the float32 the struct holds."""
+    nq, nt = _mesh_count("cloud_knn", n_queries), _mesh_count("cloud_knn", n_targets)
+    for name, s in (("query_stride", query_stride), ("target_stride", target_stride)):
+        if isinstance(s, bool) or not isinstance(s, (int, np.integer)) or s < 12 or s % 4:
+            raise ValueError("cloud_knn: %s must be a multiple of 4 and at least 12" % name)
+    _cloud_search_args("cloud_knn", k, max_dist)
+    if not isinstance(exclude_self, (bool, np.bool_)):
+        raise ValueError("cloud_knn: exclude_self must be a bool")
+    if exclude_self and nq != nt:
+        raise ValueError("cloud_knn: exclude_self needs as many queries as targets")
+    _cloud_aliases("cloud_knn", inputs, outputs)
+    return N.DpCloudKnnOptions(float(max_dist), int(k), N.CLOUD_KNN_EXCLUDE_SELF if exclude_self else 0)
+
+
+def check_cloud_clean_args(n, k, max_dist, std_mul=2.0, min_neighbours=1, radius_only=False, stride=12, inputs=(),
+                           outputs=()):
+    """Argument validation of Engine.cloud_clean[_device] (the limits of
+    dp_cloud_clean, raised as ValueError before any device call); returns the
+    dp_cloud_clean_options.  max_dist and std_mul are judged as the float32 the
+    struct holds."""
+    _mesh_count("cloud_clean", n)
+    if isinstance(stride, bool) or not isinstance(stride, (int, np.integer)) or stride < 12 or stride % 4:
+        raise ValueError("cloud_clean: stride must be a multiple of 4 and at least 12")
+    _cloud_search_args("cloud_clean", k, max_dist)
+    if isinstance(min_neighbours, bool) or not isinstance(min_neighbours, (int, np.integer)) or \
+            not 1 <= min_neighbours <= k:
+        raise ValueError("cloud_clean: min_neighbours must be in 1..k")
+    with np.errstate(over="ignore"):
+        if isinstance(std_mul, bool) or not isinstance(std_mul, (int, float, np.integer, np.floating)) or \
+                not (np.isfinite(np.float32(std_mul)) and np.float32(std_mul) >= 0):
+            raise ValueError("cloud_clean: std_mul must be finite and >= 0")
+    if not isinstance(radius_only, (bool, np.bool_)):
+        raise ValueError("cloud_clean: radius_only must be a bool")
+    _cloud_aliases("cloud_clean", inputs, outputs, among_outputs=True)
+    return N.DpCloudCleanOptions(float(max_dist), int(k), int(min_neighbours), float(std_mul),
+                                 N.CLOUD_CLEAN_RADIUS_ONLY if radius_only else 0)
 
 
 def cloud_quantile(sorted_d: np.ndarray, p: float) -> float:
@@ -2036,16 +2189,27 @@ class PMVS:
             return out
 
     def fused_cloud(self, views=None, splat_scale: float = 1.0, max_radius_px: int = 32, all_facing: bool = False,
-                    normals: bool = True, refine: int = 0, **fuse_kw) -> np.ndarray:
+                    normals: bool = True, refine: int = 0, clean=None, **fuse_kw) -> np.ndarray:
         """The last run()'s result as a dense fused cloud (a FUSED_DTYPE array):
         its depth and normal maps rendered on the device (Engine.render_maps_device)
         and fused there (Engine.fuse_maps_device, whose keyword arguments pass
         through) -- the planes never visit the host.  refine = N > 0 runs N
         passes of Engine.refine_maps_device between the two (its options pass
-        through; it needs normals).  The statistics of the calls are left in
-        self.stats["render"], self.stats["refine"] (a list) and self.stats["fused"]."""
+        through; it needs normals).  clean = dict(k=8, max_dist=R, std_mul=2.0,
+        min_neighbours=1, radius_only=False) removes the outliers of the fused
+        cloud on the device (Engine.cloud_clean_device; max_dist is required)
+        and returns the cleaned cloud.  The statistics of the calls are left in
+        self.stats["render"], self.stats["refine"] (a list), self.stats["fused"]
+        and self.stats["cloud_clean"]."""
         if not self._ran:
             raise ValueError("fused_cloud: call run() first")
+        if clean is not None:
+            if not isinstance(clean, dict) or "max_dist" not in clean or \
+                    set(clean) - {"k", "max_dist", "std_mul", "min_neighbours", "radius_only"}:
+                raise ValueError("fused_cloud: clean is a dict of k, max_dist (required), std_mul, min_neighbours "
+                                 "and radius_only")
+            clean = dict(dict(k=8), **clean)
+            check_cloud_clean_args(0, stride=FUSED_DTYPE.itemsize, **clean)
         refine, mkw, fuse_kw = split_refine_args("fused_cloud", refine, fuse_kw)
         if refine and not normals:
             raise ValueError("fused_cloud: refine needs normals")
@@ -2086,6 +2250,15 @@ class PMVS:
             n, fst = eng.fuse_maps_device(vid, [t.data_ptr() for t in depth],
                                           [t.data_ptr() for t in normal] if normals else None, pts.data_ptr(), cap,
                                           **fuse_kw)
+            if clean is not None:
+                keep = torch.empty(max(n, 1), dtype=torch.uint8, device=dev)
+                kept = torch.empty_like(pts)
+                n_out = torch.zeros(1, dtype=torch.int64, device=dev)
+                torch.cuda.synchronize(dev)
+                self.stats["cloud_clean"] = eng.cloud_clean_device(pts.data_ptr() if n else 0, n, FUSED_DTYPE.itemsize,
+                                                                   d_keep=keep.data_ptr(), d_out=kept.data_ptr(),
+                                                                   d_n_out=n_out.data_ptr(), **clean)
+                pts, n = kept, int(n_out.item())
             out = pts[:n].cpu().numpy().reshape(-1).view(FUSED_DTYPE).copy()
         self.stats["render"], self.stats["fused"] = rst, fst
         return out

@@ -1475,6 +1475,147 @@ int dp_cloud_nearest_device(dp_ctx *ctx, const void *d_queries, int64_t n_querie
                             const dp_cloud_nearest_options *opts, int32_t *d_index, float *d_dist,
                             uint64_t *d_hist, dp_cloud_nearest_stats *stats, void *stream);
 
+/* ---- the k nearest neighbours between two point clouds ---------------------------
+ * No reference counterpart.  dp_cloud_nearest for k neighbours: the primitive
+ * under outlier removal (dp_cloud_clean below), normal estimation, smoothing and
+ * density weights of a cloud.  Everything dp_cloud_nearest says holds here unless
+ * stated: points read in place at any stride >= 12 that is a multiple of 4; a
+ * point TAKES PART iff its three floats are finite; d2 = (dx*dx + dy*dy) + dz*dz in
+ * fp64; a target is a CANDIDATE iff d2 <= R2, R2 = (double)max_dist *
+ * (double)max_dist, inclusive; counts up to 2^31 - 1; no views.
+ *
+ * Options.  max_dist finite and > 0; k in 1..32; flags = 0 or
+ * DP_CLOUD_KNN_EXCLUDE_SELF.  With EXCLUDE_SELF target i is never a candidate of
+ * query i: the rule is on the index, not on the pointer or the position, so it
+ * means the same in the host form, and it requires n_queries == n_targets.  A
+ * duplicate of the point under another index stays a candidate at distance 0.
+ *
+ * Answer.  The answer of query q is its candidates ordered by (d2 ascending,
+ * target index ascending), cut to the first k.  index[q * k + j] = the index of
+ * the j-th of them in the caller's target array, dist[q * k + j] = (float)
+ * dvsqrt(d2) of it; the rest of the row is -1 and +inf.  count[q] (int32, 0..k)
+ * is the number of real entries.  A query that does not take part gets count 0
+ * and a padded row and counts in skipped_queries.
+ * Statistics.  queries, targets, skipped_queries, skipped_targets as in
+ * dp_cloud_nearest; full = queries with count == k, partial = with 0 < count <
+ * k, empty = with count == 0 (full + partial + empty = queries); neighbours =
+ * the sum of all counts.  grid_cells, max_cell_targets, build_ms and query_ms
+ * are facts of the implementation, as in dp_cloud_nearest.
+ *
+ * The result is a function of the two point sets, max_dist, k and the flag
+ * alone: not of the grid, the launch geometry or the order of the queries (the
+ * order (d2, index) is total, so the list is the same in whatever order the
+ * candidates are met).  With k = 1 and no flag, index and dist equal
+ * dp_cloud_nearest's bit for bit.
+ * Errors (DP_E_ARG): dp_cloud_nearest's on the counts, pointers, strides, opts and
+ * max_dist; k outside 1..32; an unknown flag; EXCLUDE_SELF with n_queries !=
+ * n_targets; an output that equals an input; host form: index, dist or count
+ * NULL; device form: d_index, d_dist or d_count NULL with n_queries > 0.
+ * Host form: *index, *dist and *count are context-owned, valid until the next
+ * dp_cloud_knn, dp_cloud_clean or destroy (NULL when n_queries is 0).  Device
+ * form: caller buffers of n_queries * k int32, n_queries * k f32 and n_queries
+ * int32; everything is queued on `stream` (NULL = the context's) and the call
+ * waits only when stats != NULL.
+ * Limits: k <= 32, nothing beyond max_dist; one lane per query, its list in
+ * registers (lists of 8, 16 or 32 entries, the smallest that holds k).  Scratch
+ * is dp_cloud_nearest's and shared with it. */
+#define DP_CLOUD_KNN_EXCLUDE_SELF 1
+typedef struct dp_cloud_knn_options {
+    float max_dist;     /* search radius, world units (> 0, finite; no default) */
+    int32_t k;          /* neighbours per query, 1..32                         */
+    int32_t flags;      /* DP_CLOUD_KNN_*; another bit is DP_E_ARG             */
+} dp_cloud_knn_options;
+typedef struct dp_cloud_knn_stats {
+    int64_t queries, targets;          /* those taking part                      */
+    int64_t skipped_queries, skipped_targets, full, partial, empty, neighbours;
+    int64_t grid_cells, max_cell_targets;  /* facts of the implementation, not of the spec */
+    double build_ms, query_ms;
+} dp_cloud_knn_stats;
+
+int dp_cloud_knn(dp_ctx *ctx, const void *queries, int64_t n_queries, int64_t query_stride,
+                 const void *targets, int64_t n_targets, int64_t target_stride,
+                 const dp_cloud_knn_options *opts, const int32_t **index, const float **dist,
+                 const int32_t **count, dp_cloud_knn_stats *stats);
+int dp_cloud_knn_device(dp_ctx *ctx, const void *d_queries, int64_t n_queries, int64_t query_stride,
+                        const void *d_targets, int64_t n_targets, int64_t target_stride,
+                        const dp_cloud_knn_options *opts, int32_t *d_index, float *d_dist,
+                        int32_t *d_count, dp_cloud_knn_stats *stats, void *stream);
+
+/* ---- statistical and radius outlier removal of a point cloud ----------------------
+ * No reference counterpart (the reference links PCL's filters for this).  One
+ * cloud: n records of `stride` bytes (a multiple of 4, at least 12), the point in
+ * the first 12 bytes of each.  A record is kept when it has enough neighbours
+ * within max_dist and its mean distance to them is not far above the cloud's.
+ *
+ * Options.  max_dist finite and > 0; k in 1..32; min_neighbours in 1..k;
+ * std_mul finite and >= 0; flags = 0 or DP_CLOUD_CLEAN_RADIUS_ONLY.
+ *
+ * Per point.  dp_cloud_knn of the cloud against itself with EXCLUDE_SELF, max_dist
+ * and k.  c_i = the point's count.  m_i = its mean neighbour distance: the fp64
+ * sum, in rank order and starting from the first term, of dvsqrt(d2) over the
+ * c_i neighbours, then dvdiv(sum, (double)c_i).  A point is ELIGIBLE iff it takes
+ * part and c_i >= min_neighbours.
+ *
+ * Global statistics (skipped with RADIUS_ONLY, which reports mu = sigma =
+ * threshold = 0).  N = the number of eligible points.
+ *   mu    = dvdiv(S(x), (double)N),  x_i = m_i for eligible points, +0.0 otherwise;
+ *   var   = dvdiv(S(y), (double)(N - 1)),  y_i = (m_i - mu) * (m_i - mu) for eligible
+ *           points, +0.0 otherwise; var = 0 when N < 2;
+ *   sigma = dvsqrt(var);   T = mu + (double)std_mul * sigma;
+ *   with N = 0, mu = sigma = T = 0.
+ * S is the balanced pairwise sum: the n-vector padded with +0.0 to the next
+ * power of two, then replaced by x[2j] + x[2j+1] until one value is left (numpy:
+ * while len(x) > 1: x = x[0::2] + x[1::2]).  The order is fixed, there is no
+ * floating-point atomic, and the tree is the one xor-shuffles compute.
+ *
+ * Decision.  keep[i] = eligible_i && (RADIUS_ONLY || m_i <= T).
+ * Outputs.  keep: uint8 per point, 0 or 1.  mean_dist (optional): (float)m_i,
+ * +inf where c_i = 0 or the point does not take part.  map (optional): int32 per
+ * point, its index among the kept points in input order, -1 for a removed one.
+ * out (optional): the kept records, `stride` bytes each, copied whole and packed
+ * in input order.  The kept count: *n_out (host form), *d_n_out (device form, an
+ * optional device int64).
+ * Statistics.  points = those taking part, skipped = the others (points + skipped
+ * = n); eligible; kept; removed_sparse = takes part and c_i < min_neighbours;
+ * removed_far = eligible and m_i > T; kept + removed_sparse + removed_far =
+ * points.  mu, sigma, threshold as above.  grid_cells and max_cell_targets are
+ * the search's; knn_ms = device time of the search, clean_ms = of the rest.
+ * n = 0 is legal.
+ * Errors (DP_E_ARG): n negative or above 2^31 - 1; points NULL with n > 0; a
+ * stride that is no multiple of 4 or below 12; opts NULL; an option outside the
+ * ranges above; an output that equals the input or another output; host form:
+ * keep NULL; device form: d_keep NULL with n > 0.
+ * Host form: *keep, *mean_dist, *map and *out are context-owned, valid until the
+ * next dp_cloud_knn, dp_cloud_clean or destroy; pass NULL for those of
+ * mean_dist, map, out and n_out that are not wanted.  Device form: caller buffers
+ * (d_out of n * stride bytes); everything is queued on `stream` (NULL = the
+ * context's), mu, sigma and T never leave the device before the end, and the
+ * call waits only when stats != NULL.
+ * Limits: dp_cloud_knn's.  Scratch is the search's plus 4 * k + 20 bytes per
+ * point. */
+#define DP_CLOUD_CLEAN_RADIUS_ONLY 1
+typedef struct dp_cloud_clean_options {
+    float max_dist;          /* neighbourhood radius (> 0, finite; no default)   */
+    int32_t k;               /* neighbours per point, 1..32                      */
+    int32_t min_neighbours;  /* 1..k                                             */
+    float std_mul;           /* T = mu + std_mul * sigma (>= 0, finite)          */
+    int32_t flags;           /* DP_CLOUD_CLEAN_*; another bit is DP_E_ARG        */
+} dp_cloud_clean_options;
+typedef struct dp_cloud_clean_stats {
+    int64_t points, skipped, eligible, kept, removed_sparse, removed_far;
+    int64_t grid_cells, max_cell_targets;  /* facts of the implementation, not of the spec */
+    double mu, sigma, threshold;
+    double knn_ms, clean_ms;
+} dp_cloud_clean_stats;
+
+int dp_cloud_clean(dp_ctx *ctx, const void *points, int64_t n, int64_t stride,
+                   const dp_cloud_clean_options *opts, const uint8_t **keep, const float **mean_dist,
+                   const int32_t **map, const void **out, int64_t *n_out, dp_cloud_clean_stats *stats);
+int dp_cloud_clean_device(dp_ctx *ctx, const void *d_points, int64_t n, int64_t stride,
+                          const dp_cloud_clean_options *opts, uint8_t *d_keep, float *d_mean_dist,
+                          int32_t *d_map, void *d_out, int64_t *d_n_out, dp_cloud_clean_stats *stats,
+                          void *stream);
+
 /* ---- nearest-triangle distances from points to a mesh surface ---------------------
  * No reference counterpart.  For every query point the nearest triangle of a
  * mesh within a radius, its distance and the closest point on it: the primitive

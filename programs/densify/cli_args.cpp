@@ -82,6 +82,13 @@ void usage()
                  "                             against the mesh's own depth maps, weighted by the cosine\n"
                  "                             between its normal and the ray; T: relative depth tolerance,\n"
                  "                             0.01; C: least cosine, 0.2; -bilinear: four taps per view)\n"
+                 "               [--fuse-clean-k K --fuse-clean-radius R [--fuse-clean-std A]\n"
+                 "                [--fuse-clean-min-neighbours M] [--fuse-clean-radius-only]]\n"
+                 "                            (with --fuse: outlier removal of the fused cloud on the device\n"
+                 "                             before it is written and evaluated -- dp_cloud_clean; a point\n"
+                 "                             stays when it has M (1) of its K (1..32) nearest neighbours\n"
+                 "                             within R and its mean distance to them is at most the cloud's\n"
+                 "                             mean + A (2) standard deviations; -radius-only: the first alone)\n"
                  "               [--evaluate truth.xyz --eval-tau T [--eval-max-dist D]]\n"
                  "                            (after the outputs are written: the patches -- and the fused\n"
                  "                             cloud and the mesh's vertices, with --fuse and --mesh --\n"
@@ -144,6 +151,7 @@ bool set_flag(const std::string &o, Args &a)
     else if (o == "--filter") a.do_filter = true;
     else if (o == "--check-only") a.check_only = true;
     else if (o == "--depth-normals") a.depth_normals = true;
+    else if (o == "--fuse-clean-radius-only") a.fuse_clean_radius_only = true;
     else if (o == "--mesh-smooth-free-boundary") a.mesh_smooth_free_boundary = true;
     else if (o == "--mesh-normals") a.mesh_normals = true;
     else if (o == "--mesh-decimate-quadric") a.mesh_decimate_quadric = true;
@@ -214,6 +222,26 @@ Parse parse_args(int argc, char **argv, Args &a, std::string &error)
                 a.fuse.depth_tol = (float)t;
             else
                 error = "--fuse-depth-tol expects a finite number >= 0";
+        } else if (o == "--fuse-clean-k") {
+            if (int_in_range(v, 1, 32, k))
+                a.fuse_clean_k = (int)k;
+            else
+                error = "--fuse-clean-k expects 1..32";
+        } else if (o == "--fuse-clean-radius") {
+            if (number_in_range(v, 0.0, 3.0e38, t) && (float)t > 0.0f)
+                a.fuse_clean_radius = t;
+            else
+                error = "--fuse-clean-radius expects a finite number > 0";
+        } else if (o == "--fuse-clean-std") {
+            if (number_in_range(v, 0.0, 3.0e38, t))
+                a.fuse_clean_std = t;
+            else
+                error = "--fuse-clean-std expects a finite number >= 0";
+        } else if (o == "--fuse-clean-min-neighbours") {
+            if (int_in_range(v, 1, 32, k))
+                a.fuse_clean_min_neighbours = (int)k;
+            else
+                error = "--fuse-clean-min-neighbours expects 1..32";
         } else if (o == "--refine-maps") {
             if (int_in_range(v, 0, 64, k))
                 a.refine_passes = (int)k;
@@ -331,6 +359,26 @@ Parse parse_args(int argc, char **argv, Args &a, std::string &error)
     }
     if (a.synth.empty() && a.input.empty())
         return Parse::UsageError;
+    const bool clean_any = a.fuse_clean_k > 0 || a.fuse_clean_radius > 0.0 || a.fuse_clean_std >= 0.0 ||
+                           a.fuse_clean_min_neighbours > 0 || a.fuse_clean_radius_only;
+    if (clean_any && a.fuse_path.empty()) {
+        error = "--fuse-clean-k, -radius, -std, -min-neighbours and -radius-only need --fuse";
+        return Parse::UsageError;
+    }
+    if (clean_any && !(a.fuse_clean_k > 0 && a.fuse_clean_radius > 0.0)) {
+        error = "--fuse-clean-k and --fuse-clean-radius go together, and the other --fuse-clean options need both";
+        return Parse::UsageError;
+    }
+    if (a.fuse_clean_min_neighbours > a.fuse_clean_k) {
+        error = "--fuse-clean-min-neighbours expects 1..K of --fuse-clean-k";
+        return Parse::UsageError;
+    }
+    if (a.fuse_clean()) {
+        if (a.fuse_clean_std < 0.0)
+            a.fuse_clean_std = 2.0;
+        if (a.fuse_clean_min_neighbours == 0)
+            a.fuse_clean_min_neighbours = 1;
+    }
     const bool smooth_detail = a.mesh_smooth_lambda != 0.0 || a.mesh_smooth_mu <= 0.0 || a.mesh_smooth_free_boundary;
     if (a.mesh_path.empty() && (a.mesh_smooth >= 0 || smooth_detail || a.mesh_normals)) {
         error = "--mesh-smooth, its options and --mesh-normals need --mesh";

@@ -23,6 +23,16 @@ struct Args {
     double splat_scale = 1.0;
     bool depth_normals = false;
     dp_fuse_options fuse;
+    // --fuse-clean-k K --fuse-clean-radius R [--fuse-clean-std A]
+    // [--fuse-clean-min-neighbours M] [--fuse-clean-radius-only]: dp_cloud_clean of
+    // the fused cloud on the device before it is written and evaluated.  Only
+    // with --fuse; K and R go together.
+    int fuse_clean_k = 0;              // 0: not given, no clean-up
+    double fuse_clean_radius = 0.0;    // 0: not given
+    double fuse_clean_std = -1.0;      // < 0: not given; parse_args resolves it to 2 with K
+    int fuse_clean_min_neighbours = 0; // 0: not given; parse_args resolves it to 1 with K
+    bool fuse_clean_radius_only = false;
+    bool fuse_clean() const { return fuse_clean_k > 0; }
     // --refine-maps N: dp_refine_maps passes between the render and its users
     int refine_passes = 0;
     int refine_window = 0;        // 0: the library's default

@@ -701,6 +701,31 @@ std::string write_fused(dp_ctx *ctx, const Args &args, int32_t V, const std::vec
     }
     if (n_fused > cap)
         throw std::runtime_error("--fuse: the point count changed between two runs");
+    // --fuse-clean-k: the outliers go before anything reads the cloud
+    std::string cleaned;
+    if (args.fuse_clean()) {
+        const int64_t n_all = n_fused;
+        uint8_t *d_keep = (uint8_t *)m.bytes((size_t)n_all, "--fuse-clean-k");
+        dp_fused_point *d_kept = (dp_fused_point *)m.bytes((size_t)n_all * sizeof(dp_fused_point), "--fuse-clean-k");
+        int64_t *d_n = (int64_t *)m.bytes(sizeof(int64_t), "--fuse-clean-k");
+        dp_cloud_clean_options co{(float)args.fuse_clean_radius, args.fuse_clean_k, args.fuse_clean_min_neighbours,
+                                  (float)args.fuse_clean_std,
+                                  args.fuse_clean_radius_only ? DP_CLOUD_CLEAN_RADIUS_ONLY : 0};
+        dp_cloud_clean_stats cs;
+        check(ctx,
+              dp_cloud_clean_device(ctx, d_pts, n_all, sizeof(dp_fused_point), &co, d_keep, nullptr, nullptr, d_kept, d_n,
+                                    &cs, nullptr),
+              "dp_cloud_clean_device");
+        d_pts = d_kept;
+        n_fused = cs.kept;
+        char cbuf[320];
+        std::snprintf(cbuf, sizeof cbuf,
+                      ", \"fused_clean\": {\"points\": %lld, \"kept\": %lld, \"removed_sparse\": %lld, "
+                      "\"removed_far\": %lld, \"mu\": %.9g, \"sigma\": %.9g, \"knn_ms\": %.3f, \"clean_ms\": %.3f}",
+                      (long long)n_all, (long long)cs.kept, (long long)cs.removed_sparse, (long long)cs.removed_far,
+                      cs.mu, cs.sigma, cs.knn_ms, cs.clean_ms);
+        cleaned = cbuf;
+    }
     std::vector<dp_fused_point> pts((size_t)n_fused);
     if (n_fused > 0 &&
         hipMemcpy(pts.data(), d_pts, pts.size() * sizeof(dp_fused_point), hipMemcpyDeviceToHost) != hipSuccess)
@@ -712,7 +737,7 @@ std::string write_fused(dp_ctx *ctx, const Args &args, int32_t V, const std::vec
     std::snprintf(buf, sizeof buf,
                   ", \"fused\": {\"points\": %lld, \"fusable\": %lld, \"depth_pixels\": %lld, \"fuse_ms\": %.3f}",
                   (long long)n_fused, (long long)fs.fusable, (long long)fs.depth_pixels, fs.fuse_ms);
-    return refined + buf;
+    return refined + buf + cleaned;
 }
 
 // --mesh: the device maps integrated into one TSDF volume around the written
