@@ -28,9 +28,11 @@ from .pmvs import (  # noqa: F401
     FastOptions,
     Options,
     View,
+    check_cloud_align_args,
     check_cloud_clean_args,
     check_cloud_knn_args,
     check_cloud_nearest_args,
+    check_cloud_transform_args,
     check_fuse_args,
     check_mapref_args,
     check_mesh_clean_args,

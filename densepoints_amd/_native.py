@@ -444,6 +444,32 @@ CLOUD_KNN_EXCLUDE_SELF = 1
 CLOUD_CLEAN_RADIUS_ONLY = 1
 
 
+class DpCloudAlignOptions(ctypes.Structure):
+    """dp_cloud_align_options: the options of dp_cloud_align (include/densepoints.h)."""
+    _fields_ = [("max_dist", ctypes.c_float), ("iterations", ctypes.c_int32), ("min_pairs", ctypes.c_int32),
+                ("flags", ctypes.c_int32), ("rms_tol", ctypes.c_double)]
+
+
+class DpCloudAlignStep(ctypes.Structure):
+    _fields_ = [("matched", ctypes.c_int64), ("rms", ctypes.c_double)]
+
+
+class DpCloudAlignStats(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int64) for n in (
+        "queries", "targets", "skipped_queries", "skipped_targets", "matched", "unmatched", "grid_cells",
+        "max_cell_targets", "iterations_run", "stop_reason")] + [("grid_ms", ctypes.c_double),
+                                                                 ("iterate_ms", ctypes.c_double)]
+
+
+assert ctypes.sizeof(DpCloudAlignOptions) == 24 and ctypes.sizeof(DpCloudAlignStep) == 16
+assert ctypes.sizeof(DpCloudAlignStats) == 96
+CLOUD_ALIGN_SCALE = 1
+CLOUD_ALIGN_STOP_ITERATIONS, CLOUD_ALIGN_STOP_RMS, CLOUD_ALIGN_STOP_PAIRS = 0, 1, 2
+CLOUD_ALIGN_STOP_DEGENERATE, CLOUD_ALIGN_STOP_EMPTY = 3, 4
+# a dp_cloud_align_step as numpy reads it
+CLOUD_ALIGN_STEP_DTYPE = np.dtype([("matched", "<i8"), ("rms", "<f8")])
+
+
 class DpSynthConfig(ctypes.Structure):
     _fields_ = [
         ("n_views", ctypes.c_int32),
@@ -615,6 +641,12 @@ SIGNATURES = [
                                  _P, _P, _P]),
     ("dp_cloud_clean", _I, [_P, _P, ctypes.c_int64, ctypes.c_int64, _P, _P, _P, _P, _P, _P, _P]),
     ("dp_cloud_clean_device", _I, [_P, _P, ctypes.c_int64, ctypes.c_int64, _P, _P, _P, _P, _P, _P, _P, _P]),
+    ("dp_cloud_transform", _I, [_P, _P, ctypes.c_int64, ctypes.c_int64, _P, ctypes.c_int64, _P]),
+    ("dp_cloud_transform_device", _I, [_P, _P, ctypes.c_int64, ctypes.c_int64, _P, ctypes.c_int64, _P, _P]),
+    ("dp_cloud_align", _I, [_P, _P, ctypes.c_int64, ctypes.c_int64, _P, ctypes.c_int64, ctypes.c_int64, _P, _P, _P, _P, _P,
+                            _P, _P, _P]),
+    ("dp_cloud_align_device", _I, [_P, _P, ctypes.c_int64, ctypes.c_int64, _P, ctypes.c_int64, ctypes.c_int64, _P, _P, _P,
+                                   _P, _P, _P, _P, _P, _P]),
     ("dp_last_kernel_ms", _I, [_P, _P]),
     ("dp_default_matcher_options", None, [_P]),
     ("dp_orb_pattern", _I, [_P]),

@@ -1,10 +1,11 @@
 // dp_clouddev.h -- what the searches over a point cloud's uniform grid share
 // (dp_cloudnearest.hip: one nearest target; dp_cloudknn.hip: the k nearest and
 // the outlier filter on them): the kernels' argument block, the guarded load of
-// a point, the cell expression, and the host entry that queues the grid.  The
+// a point, the cell expression, and the host entries that queue the grid.  The
 // grid kernels themselves (box, plan, keys, gather, begin, maxcell, query keys)
 // and the margin proof live in dp_cloudnearest.hip, which exports
-// cloud_grid_queue below; both searches use the scratch of c->cloudnearest,
+// cloud_targets_queue and cloud_queries_queue below; the searches (and
+// dp_cloudalign.hip, which iterates one) use the scratch of c->cloudnearest,
 // since their calls never overlap on a context.
 #pragma once
 
@@ -61,13 +62,23 @@ __device__ __forceinline__ uint32_t wave_stripe() { return blockIdx.x * (kMeshLa
 
 } // namespace dpk
 
-// Queues on s, into the scratch of c->cloudnearest, everything of a search but
-// its walk: the counters zeroed, the grid over the targets (timed by time[0]),
-// the queries' cell keys and their sort (time[1] begun; the caller ends it
-// after its own query kernel).  In: a's clouds, counts, strides, R and R2; out:
-// its cap and every scratch pointer.  index, dist, hist and bins stay the
-// caller's.  (dp_cloudnearest.hip)
-int cloud_grid_queue(dp_ctx *c, dpk::CloudArgs &a, hipStream_t s);
+// The search but its walk, in two halves that a caller queues in this order on
+// s, into the scratch of c->cloudnearest.  dp_cloud_nearest and dp_cloud_knn
+// queue both once; dp_cloud_align queues the targets once and the queries once
+// per pass.  (dp_cloudnearest.hip)
+//
+// cloud_targets_queue: reserves the scratch of both halves, zeroes the
+// counters, queues the grid over the targets (timed by time[0]).  In: a's
+// clouds, counts, strides, R and R2 (queries may still be NULL, nq is used for
+// the sizes); out: its cap and every scratch pointer.  index, dist, hist and bins
+// stay the caller's.
+int cloud_targets_queue(dp_ctx *c, dpk::CloudArgs &a, hipStream_t s);
+// cloud_queries_queue: time[1] begun (the caller ends it after its own query
+// kernel), the queries' cell keys and their sort.  a as cloud_targets_queue
+// left it, with queries and qstride set.
+int cloud_queries_queue(dp_ctx *c, const dpk::CloudArgs &a, hipStream_t s);
+// dp_cloud_nearest's walk (cloud_query_kernel) and the end of time[1]
+int cloud_nearest_walk_queue(dp_ctx *c, const dpk::CloudArgs &a, hipStream_t s);
 
 // the counts, pointers and strides both searches check the same way
 int cloud_check_clouds(dp_ctx *c, const std::string &w, const void *queries, int64_t nq, int64_t qstride,

@@ -3,7 +3,7 @@
 // include/densepoints.h, dp_cloud_knn and dp_cloud_clean), and their C ABI.
 //
 // The grid, the sorted targets and the queries' cell order are dp_cloud_nearest's
-// (cloud_grid_queue, dp_clouddev.h), and so is the proof that the 3 x 3 x 3 walk
+// (cloud_targets_queue and cloud_queries_queue, dp_clouddev.h), and so is the proof that the 3 x 3 x 3 walk
 // meets every candidate: a candidate has d2 <= R2 whatever k is.
 //
 //   knn_query_kernel<K>  one lane per cell-sorted query over the same 9 runs.  The
@@ -336,8 +336,8 @@ static int knn_queue(dp_ctx *c, const dp_cloud_knn_options &o, const void *d_que
     a.R2 = (double)o.max_dist * (double)o.max_dist;
     a.index = d_index;
     a.dist = d_dist;
-    const int rc = cloud_grid_queue(c, a, s);
-    if (rc != DP_OK)
+    int rc = cloud_targets_queue(c, a, s);
+    if (rc != DP_OK || (rc = cloud_queries_queue(c, a, s)) != DP_OK)
         return rc;
     ka.k = o.k;
     ka.exclude_self = (o.flags & DP_CLOUD_KNN_EXCLUDE_SELF) ? 1 : 0;
@@ -514,7 +514,7 @@ static int clean_queue(dp_ctx *c, const dp_cloud_clean_options &o, const void *d
     size_t scan_bytes = 0;
     DP_HIP(c, hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, r.flag.p, r.pos.p, (int)n1, s));
 
-    // before the search queues its sorts: cloud_grid_queue then only grows the buffer
+    // before the search queues its sorts: cloud_targets_queue then only grows the buffer
     DP_HIP(c, c->scan_tmp.reserve(scan_bytes ? scan_bytes : 1));
 
     DP_HIP(c, r.time[0].begin(s));

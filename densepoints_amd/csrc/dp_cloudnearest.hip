@@ -42,7 +42,8 @@
 // keeps that; a query more than a cell outside the box finds every run empty.
 // The cell only bounds the walk: the fp64 test d2 <= R2 decides.
 // The argument block, load_point, cell_coord and the constants are
-// dp_clouddev.h's; cloud_grid_queue below is what dp_cloudknn.hip shares.
+// dp_clouddev.h's; cloud_targets_queue and cloud_queries_queue below are what
+// dp_cloudknn.hip and dp_cloudalign.hip share.
 #include "dp_clouddev.h"
 
 #include <hipcub/hipcub.hpp>
@@ -308,8 +309,17 @@ static int cloud_check(dp_ctx *c, const std::string &w, const void *queries, int
     return DP_OK;
 }
 
-// the grid and the queries' cell order (dp_clouddev.h)
-int cloud_grid_queue(dp_ctx *c, dpk::CloudArgs &a, hipStream_t s)
+// the bits of the sort's keys: a point that does not take part has the key cap itself
+static int cloud_end_bit(int32_t cap)
+{
+    int bits = 0;
+    while ((1 << bits) < cap)
+        ++bits;
+    return bits + 1;
+}
+
+// the grid over the targets (dp_clouddev.h)
+int cloud_targets_queue(dp_ctx *c, dpk::CloudArgs &a, hipStream_t s)
 {
     const int64_t nt = a.nt, nq = a.nq;
     dpk::CloudNearestScratch &r = c->cloudnearest;
@@ -383,14 +393,29 @@ int cloud_grid_queue(dp_ctx *c, dpk::CloudArgs &a, hipStream_t s)
     DP_HIP(c, dpk::launch_over(dpk::cloud_begin_kernel, dpk::mesh_blocks((int64_t)cap + 1), a, s));
     DP_HIP(c, dpk::launch_over(dpk::cloud_maxcell_kernel, dpk::mesh_blocks(cap), a, s));
     DP_HIP(c, r.time[0].end(s));
-    // the queries
-    DP_HIP(c, r.time[1].begin(s));
+    return DP_OK;
+}
+
+// the queries' cell order (dp_clouddev.h)
+int cloud_queries_queue(dp_ctx *c, const dpk::CloudArgs &a, hipStream_t s)
+{
+    const int64_t nq = a.nq;
+    const int end_bit = cloud_end_bit(a.cap);
+    DP_HIP(c, c->cloudnearest.time[1].begin(s));
     DP_HIP(c, dpk::launch_over(dpk::cloud_qkeys_kernel, dpk::mesh_blocks(nq), a, s));
     if (nq > 0) {
-        b = tmp;
+        // cloud_targets_queue reserved the larger of the two sorts' needs
+        size_t b = c->scan_tmp.cap;
         DP_HIP(c, hipcub::DeviceRadixSort::SortPairs(c->scan_tmp.p, b, a.qkeys, a.qkeys_sorted, a.qidx, a.qidx_sorted,
                                                      (int)nq, 0, end_bit, s));
     }
+    return DP_OK;
+}
+
+int cloud_nearest_walk_queue(dp_ctx *c, const dpk::CloudArgs &a, hipStream_t s)
+{
+    DP_HIP(c, dpk::launch_over(dpk::cloud_query_kernel, dpk::mesh_blocks(a.nq), a, s));
+    DP_HIP(c, c->cloudnearest.time[1].end(s));
     return DP_OK;
 }
 
@@ -414,12 +439,10 @@ static int cloud_queue(dp_ctx *c, const dp_cloud_nearest_options &o, const void 
     a.hist = o.hist_bins > 0 ? (unsigned long long *)d_hist : nullptr;
     if (a.hist)
         DP_HIP(c, hipMemsetAsync(a.hist, 0, sizeof(unsigned long long) * (size_t)o.hist_bins, s));
-    const int rc = cloud_grid_queue(c, a, s);
-    if (rc != DP_OK)
+    int rc = cloud_targets_queue(c, a, s);
+    if (rc != DP_OK || (rc = cloud_queries_queue(c, a, s)) != DP_OK)
         return rc;
-    DP_HIP(c, dpk::launch_over(dpk::cloud_query_kernel, dpk::mesh_blocks(nq), a, s));
-    DP_HIP(c, c->cloudnearest.time[1].end(s));
-    return DP_OK;
+    return cloud_nearest_walk_queue(c, a, s);
 }
 
 // the statistics read and its wait

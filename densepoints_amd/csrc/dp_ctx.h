@@ -268,6 +268,36 @@ struct CloudKnnScratch {
     Timer time[2];         // dp_cloud_clean: the search; the filter
 };
 
+// what dp_cloud_align keeps on the device between its kernels: the current M and
+// its scale, the means of the last pass, the rms of the step before, the
+// targets taking part (the grid's counter, which every pass zeroes again), and
+// the 24 bytes the host reads after every pass: the record and the verdict
+// (-1 = M was updated, else the DP_CLOUD_ALIGN_STOP_* reason)
+struct CloudAlignDev {
+    double M[12], scale, mux[3], muq[3], rms_prev;
+    int64_t targets;
+    int64_t matched;
+    double rms;
+    int64_t verdict;
+};
+
+// dp_cloud_align and dp_cloud_transform (dp_cloudalign.hip).  The search is
+// CloudNearestScratch's.  Here: the transformed source (packed xyz), the last
+// pass's index and dist when the caller wants none, the two buffers the
+// multi-channel sum levels alternate between, the state block and its pinned
+// copy (the record, then the whole block at the end); the host forms' staged
+// inputs, device results and pinned results.
+struct CloudAlignScratch {
+    DevBuf<float> y, dist;
+    DevBuf<int32_t> index;
+    DevBuf<double> sum[2];
+    DevBuf<CloudAlignDev> dev;
+    HostBuf<CloudAlignDev> hdev;
+    DevBuf<unsigned char> in, out;
+    HostBuf<unsigned char> hout;
+    Timer time; // everything after the grid
+};
+
 // dp_mesh_nearest's search grid, made on the device (meshnear_plan_kernel,
 // meshnear_pick_kernel): isotropic cells of side0 * 2^level from one origin,
 // cell (x, y, z) with the key (z * n[1] + y) * n[0] + x
@@ -361,6 +391,7 @@ struct dp_ctx {
     dpk::MeshColourScratch meshcolour;
     dpk::CloudNearestScratch cloudnearest;
     dpk::CloudKnnScratch cloudknn;
+    dpk::CloudAlignScratch cloudalign;
     dpk::MeshNearestScratch meshnearest;
     HostBuf<dp_patch> result; // dp_densify / dp_densify_result output (pinned)
     // dp_densify_iterate: per iteration {evaluations, filter survivors} on the

@@ -40,7 +40,9 @@ __all__ = [
     "check_tsdf_args",
     "check_mesh_clean_args",
     "check_mesh_colour_args",
+    "check_cloud_align_args",
     "check_cloud_nearest_args",
+    "check_cloud_transform_args",
     "cloud_compare",
     "check_mesh_nearest_args",
     "mesh_compare",
@@ -1376,6 +1378,92 @@ class Engine:
                                               ctypes.byref(st) if stats else None, _addr(stream)))
         return _stats_dict(st) if stats else None
 
+    # ---- a cloud's records under a 3 x 4 transform (include/densepoints.h dp_cloud_transform) ----
+    def cloud_transform(self, points, matrix, normals: bool = False) -> np.ndarray:
+        """dp_cloud_transform: the records of `points` ((n, 3) float32, or a
+        structured array whose pos field comes first) with their positions under
+        the 3 x 4 float64 `matrix` [A | t]; with normals=True the structured
+        array's `normal` field becomes the unit A * normal.  Records move whole;
+        a point that is not finite is left as it is.  Returns a new array of the
+        input's dtype.  Needs no views."""
+        pa, pp, n, stride = _cloud_points("cloud_transform", points)
+        if pp != pa.ctypes.data:
+            raise ValueError("cloud_transform: the pos field must be the first of a record")
+        off = _cloud_normal_offset("cloud_transform", pa, normals)
+        m = check_cloud_transform_args(n, matrix, stride, off)
+        po = ctypes.c_void_p()
+        self._check(lib.dp_cloud_transform(self._ctx, _addr(pp) if n else None, n, stride, ptr(m), off,
+                                           ctypes.byref(po)))
+        out = np.zeros(pa.shape, pa.dtype)
+        if n:
+            ctypes.memmove(out.ctypes.data, po.value, out.nbytes)
+        return out
+
+    def cloud_transform_device(self, d_points, n: int, stride: int, matrix, d_out, normal_offset: int = -1,
+                               stream: int | None = None) -> None:
+        """dp_cloud_transform_device: n device records of `stride` bytes at
+        d_points transformed into d_out (which may be d_points: in place), the
+        normal at the byte offset normal_offset (-1 = none).  Queued on `stream`;
+        does not wait."""
+        n = _mesh_count("cloud_transform_device", n)
+        m = check_cloud_transform_args(n, matrix, stride, normal_offset)
+        if n and not (d_points and d_out):
+            raise ValueError("cloud_transform_device: the points and d_out must be given")
+        self._check(lib.dp_cloud_transform_device(self._ctx, _addr(d_points), n, stride, ptr(m), int(normal_offset),
+                                                  _addr(d_out), _addr(stream)))
+
+    # ---- registration of one cloud to another (include/densepoints.h dp_cloud_align) ----
+    def cloud_align(self, source, target, max_dist: float, iterations: int = 30, scale: bool = False, init=None,
+                    rms_tol: float = 0.0, min_pairs: int = 3, correspondences: bool = False) -> dict:
+        """dp_cloud_align: point-to-point ICP of `source` onto `target` (clouds as
+        cloud_nearest takes them), trimmed at max_dist; scale=True estimates a
+        similarity.  Returns {"matrix" (3 x 4 float64, source -> target),
+        "scale", "trace" (iterations + 1 records of matched and rms, zero after
+        the stop), "index" and "dist" of the last pass (with correspondences,
+        else None), "stats"}.  Needs no views."""
+        sa, sp, n, ss = _cloud_points("cloud_align", source)
+        ta, tp, nt, ts = _cloud_points("cloud_align", target)
+        cao, m0 = check_cloud_align_args(n, nt, max_dist, iterations, scale, init, rms_tol, min_pairs, ss, ts)
+        M, s = np.zeros((3, 4), np.float64), ctypes.c_double(0.0)
+        trace = np.zeros(cao.iterations + 1, N.CLOUD_ALIGN_STEP_DTYPE)
+        pi, pd, st = ctypes.c_void_p(), ctypes.c_void_p(), N.DpCloudAlignStats()
+        self._check(lib.dp_cloud_align(self._ctx, _addr(sp) if n else None, n, ss, _addr(tp) if nt else None, nt, ts,
+                                       ctypes.byref(cao), ptr(m0) if m0 is not None else None, ptr(M), ctypes.byref(s),
+                                       ptr(trace), ctypes.byref(pi) if correspondences else None,
+                                       ctypes.byref(pd) if correspondences else None, ctypes.byref(st)))
+        index = dist = None
+        if correspondences:
+            index, dist = np.zeros(n, np.int32), np.zeros(n, np.float32)
+            if n:
+                ctypes.memmove(index.ctypes.data, pi.value, index.nbytes)
+                ctypes.memmove(dist.ctypes.data, pd.value, dist.nbytes)
+        del sa, ta
+        return {"matrix": M, "scale": s.value, "trace": trace, "index": index, "dist": dist, "stats": _stats_dict(st)}
+
+    def cloud_align_device(self, d_source, n_source: int, source_stride: int, d_target, n_target: int,
+                           target_stride: int, max_dist: float, iterations: int = 30, scale: bool = False, init=None,
+                           rms_tol: float = 0.0, min_pairs: int = 3, d_index=None, d_dist=None,
+                           stream: int | None = None) -> dict:
+        """dp_cloud_align_device: device clouds (the addresses of their first
+        points, strides in bytes); the last pass's index and dist go to n_source
+        int32 at d_index and float32 at d_dist when both are given.  The call
+        waits once per pass.  Returns cloud_align's dict without index and dist."""
+        n, nt = _mesh_count("cloud_align_device", n_source), _mesh_count("cloud_align_device", n_target)
+        cao, m0 = check_cloud_align_args(n, nt, max_dist, iterations, scale, init, rms_tol, min_pairs, source_stride,
+                                         target_stride, inputs=(d_source, d_target), outputs=(d_index, d_dist))
+        if (n and not d_source) or (nt and not d_target):
+            raise ValueError("cloud_align_device: the source and the target must be given")
+        if bool(d_index) != bool(d_dist):
+            raise ValueError("cloud_align_device: d_index and d_dist must be given together")
+        M, s = np.zeros((3, 4), np.float64), ctypes.c_double(0.0)
+        trace = np.zeros(cao.iterations + 1, N.CLOUD_ALIGN_STEP_DTYPE)
+        st = N.DpCloudAlignStats()
+        self._check(lib.dp_cloud_align_device(self._ctx, _addr(d_source), n, source_stride, _addr(d_target), nt,
+                                              target_stride, ctypes.byref(cao), ptr(m0) if m0 is not None else None,
+                                              ptr(M), ctypes.byref(s), ptr(trace), _addr(d_index), _addr(d_dist),
+                                              ctypes.byref(st), _addr(stream)))
+        return {"matrix": M, "scale": s.value, "trace": trace, "stats": _stats_dict(st)}
+
     # ---- nearest triangles of a mesh (include/densepoints.h dp_mesh_nearest) ----
     def mesh_nearest(self, queries, vertices, triangles, max_dist: float, hist_bins: int = 0,
                      closest: bool = False) -> dict:
@@ -1545,6 +1633,105 @@ def check_cloud_clean_args(n, k, max_dist, std_mul=2.0, min_neighbours=1, radius
                                  N.CLOUD_CLEAN_RADIUS_ONLY if radius_only else 0)
 
 
+def _cloud_matrix(who: str, name: str, m) -> np.ndarray:
+    """a 3 x 4 (or 12) array of finite numbers as contiguous float64"""
+    try:
+        a = np.array(m, dtype=np.float64)
+    except (TypeError, ValueError):
+        a = None
+    if a is None or a.size != 12 or a.shape not in ((3, 4), (12,)) or not np.isfinite(a).all():
+        raise ValueError("%s: %s must be 3 x 4 finite numbers" % (who, name))
+    return np.ascontiguousarray(a.reshape(3, 4))
+
+
+def _cloud_normal_offset(who: str, a: np.ndarray, normals) -> int:
+    """the byte offset of a structured cloud's normal field, -1 without normals"""
+    if not isinstance(normals, (bool, np.bool_)):
+        raise ValueError("%s: normals must be a bool" % who)
+    if not normals:
+        return -1
+    if not a.dtype.names or "normal" not in a.dtype.names or a.dtype.fields["normal"][0] != np.dtype(("<f4", 3)):
+        raise ValueError("%s: normals needs a structured cloud with a normal field of three float32" % who)
+    return int(a.dtype.fields["normal"][1])
+
+
+def check_cloud_transform_args(n, matrix, stride=12, normal_offset=-1) -> np.ndarray:
+    """Argument validation of Engine.cloud_transform[_device] (the limits of
+    dp_cloud_transform, raised as ValueError before any device call); returns
+    the matrix as 3 x 4 float64."""
+    def whole(x):
+        return isinstance(x, (int, np.integer)) and not isinstance(x, bool)
+
+    _mesh_count("cloud_transform", n)
+    if not whole(stride) or stride < 12 or stride % 4:
+        raise ValueError("cloud_transform: stride must be a multiple of 4 and at least 12")
+    m = _cloud_matrix("cloud_transform", "matrix", matrix)
+    if not whole(normal_offset) or (normal_offset != -1 and
+                                    (normal_offset < 12 or normal_offset % 4 or normal_offset > stride - 12)):
+        raise ValueError("cloud_transform: normal_offset must be -1 or a multiple of 4 in 12..stride - 12")
+    return m
+
+
+def check_cloud_align_args(n_source, n_target, max_dist, iterations=30, scale=False, init=None, rms_tol=0.0,
+                           min_pairs=3, source_stride=12, target_stride=12, inputs=(), outputs=()):
+    """Argument validation of Engine.cloud_align[_device] (the limits of
+    dp_cloud_align, raised as ValueError before any device call); returns the
+    dp_cloud_align_options and init as 3 x 4 float64 (None = the identity).
+    max_dist is judged as the float32 the struct holds."""
+    def whole(x):
+        return isinstance(x, (int, np.integer)) and not isinstance(x, bool)
+
+    _mesh_count("cloud_align", n_source)
+    _mesh_count("cloud_align", n_target)
+    for name, s in (("source_stride", source_stride), ("target_stride", target_stride)):
+        if not whole(s) or s < 12 or s % 4:
+            raise ValueError("cloud_align: %s must be a multiple of 4 and at least 12" % name)
+    with np.errstate(over="ignore"):
+        if isinstance(max_dist, bool) or not isinstance(max_dist, (int, float, np.integer, np.floating)) or \
+                not (np.isfinite(np.float32(max_dist)) and np.float32(max_dist) > 0):
+            raise ValueError("cloud_align: max_dist must be finite and > 0")
+    if not whole(iterations) or not 1 <= iterations <= 1000:
+        raise ValueError("cloud_align: iterations must be in 1..1000")
+    if not whole(min_pairs) or not 3 <= min_pairs <= 2**31 - 1:
+        raise ValueError("cloud_align: min_pairs must be at least 3")
+    if isinstance(rms_tol, bool) or not isinstance(rms_tol, (int, float, np.integer, np.floating)) or \
+            not (np.isfinite(rms_tol) and rms_tol >= 0):
+        raise ValueError("cloud_align: rms_tol must be finite and >= 0")
+    if not isinstance(scale, (bool, np.bool_)):
+        raise ValueError("cloud_align: scale must be a bool")
+    m0 = None if init is None else _cloud_matrix("cloud_align", "init", init)
+    _cloud_aliases("cloud_align", inputs, outputs)
+    return N.DpCloudAlignOptions(float(max_dist), int(iterations), int(min_pairs),
+                                 N.CLOUD_ALIGN_SCALE if scale else 0, float(rms_tol)), m0
+
+
+ALIGN_KEYS = ("iterations", "max_dist", "scale", "init", "rms_tol", "min_pairs")
+
+
+def check_compare_align(align, max_dist: float):
+    """The `align` argument of cloud_compare, mesh_compare and PMVS.evaluate:
+    None, or a dict of Engine.cloud_align's keyword arguments (iterations,
+    max_dist -- by default the comparison's --, scale, init, rms_tol,
+    min_pairs), judged by check_cloud_align_args.  Returns the completed dict."""
+    if align is None:
+        return None
+    if not isinstance(align, dict) or not set(align) <= set(ALIGN_KEYS):
+        raise ValueError("cloud_compare: align is a dict of " + ", ".join(ALIGN_KEYS))
+    kw = dict(align)
+    kw.setdefault("max_dist", max_dist)
+    check_cloud_align_args(0, 0, **kw)
+    return kw
+
+
+def _compare_aligned(eng, cloud, truth, kw: dict):
+    """registers `cloud` to `truth`: (the transformed cloud, the "align" entry)"""
+    cloud = np.asarray(cloud)
+    pos = np.ascontiguousarray(cloud["pos"] if cloud.dtype.names else cloud, dtype=np.float32).reshape(-1, 3)
+    res = eng.cloud_align(pos, truth, **kw)
+    moved = eng.cloud_transform(pos, res["matrix"])
+    return moved, {"matrix": res["matrix"], "scale": res["scale"], "trace": res["trace"], "stats": res["stats"]}
+
+
 def cloud_quantile(sorted_d: np.ndarray, p: float) -> float:
     """The p-quantile (0 <= p <= 1) of ascending fp64 values by linear
     interpolation between the two nearest ranks: pos = p * (m - 1), lo =
@@ -1589,17 +1776,25 @@ def check_cloud_compare_args(tau, max_dist=None) -> float:
     return float(max_dist)
 
 
-def cloud_compare(eng, recon, truth, tau: float, max_dist=None) -> dict:
+def cloud_compare(eng, recon, truth, tau: float, max_dist=None, align=None) -> dict:
     """Accuracy, completeness and F-score of a reconstructed cloud against a
     ground truth at the threshold tau, by two Engine.cloud_nearest calls with the
     radius max_dist (None = 10 * tau): accuracy is recon -> truth, completeness
     truth -> recon (each a cloud_side), fscore = 2pr / (p + r) of their ratios,
-    0.0 when p + r is 0.  The clouds are what cloud_nearest takes."""
+    0.0 when p + r is 0.  The clouds are what cloud_nearest takes.  align (a dict
+    of Engine.cloud_align's iterations, max_dist, scale, init, rms_tol,
+    min_pairs; max_dist defaults to the comparison's) first registers recon to
+    truth, compares the transformed positions and adds "align": the matrix, the
+    scale, the trace and the statistics of the registration."""
     max_dist = check_cloud_compare_args(tau, max_dist)
+    kw = check_compare_align(align, max_dist)
+    extra = {}
+    if kw is not None:
+        recon, extra["align"] = _compare_aligned(eng, recon, truth, kw)
     acc = cloud_side(eng.cloud_nearest(recon, truth, max_dist), tau)
     com = cloud_side(eng.cloud_nearest(truth, recon, max_dist), tau)
     p, r = acc["ratio"], com["ratio"]
-    return {"accuracy": acc, "completeness": com, "fscore": 2.0 * p * r / (p + r) if p + r > 0 else 0.0}
+    return dict({"accuracy": acc, "completeness": com, "fscore": 2.0 * p * r / (p + r) if p + r > 0 else 0.0}, **extra)
 
 
 def _mesh_vertices(who: str, vertices) -> np.ndarray:
@@ -1631,13 +1826,24 @@ def check_mesh_nearest_args(n_queries, n_vertices, n_triangles, max_dist, hist_b
     return N.DpMeshNearestOptions(cno.max_dist, cno.hist_bins, cno.flags)
 
 
-def mesh_compare(eng, vertices, triangles, truth, tau: float, max_dist=None) -> dict:
+def mesh_compare(eng, vertices, triangles, truth, tau: float, max_dist=None, align=None) -> dict:
     """cloud_compare for a mesh: accuracy is the mesh's vertices -> the truth
     points (Engine.cloud_nearest, as for a cloud), completeness the truth points
     -> the mesh's surface (Engine.mesh_nearest), each a cloud_side, and fscore
-    from their ratios as in cloud_compare."""
+    from their ratios as in cloud_compare.  align registers the mesh's vertices
+    to the truth first, as in cloud_compare."""
     max_dist = check_cloud_compare_args(tau, max_dist)
+    kw = check_compare_align(align, max_dist)
     verts = _mesh_vertices("mesh_compare", vertices)
+    if kw is not None:
+        moved, entry = _compare_aligned(eng, verts, truth, kw)
+        verts = verts.copy()
+        verts["pos"] = moved
+        acc = cloud_side(eng.cloud_nearest(verts, truth, max_dist), tau)
+        com = cloud_side(eng.mesh_nearest(truth, verts, triangles, max_dist), tau)
+        p, r = acc["ratio"], com["ratio"]
+        return {"accuracy": acc, "completeness": com, "fscore": 2.0 * p * r / (p + r) if p + r > 0 else 0.0,
+                "align": entry}
     acc = cloud_side(eng.cloud_nearest(verts, truth, max_dist), tau)
     com = cloud_side(eng.mesh_nearest(truth, verts, triangles, max_dist), tau)
     p, r = acc["ratio"], com["ratio"]
@@ -2357,17 +2563,19 @@ class PMVS:
         self.stats["mesh_render"] = out["stats"]
         return out
 
-    def evaluate(self, truth, tau: float, max_dist=None, cloud="patches", mesh=None) -> dict:
+    def evaluate(self, truth, tau: float, max_dist=None, cloud="patches", mesh=None, align=None) -> dict:
         """Accuracy, completeness and F-score (cloud_compare) of a cloud of the
         last run() against the ground-truth cloud `truth` at the threshold tau.
         cloud: "patches" (the stored patches), "fused" (fused_cloud()'s points),
         or a cloud of the caller's -- an (n, 3) array or a structured array with
         a pos field, for example the vertices mesh() returned.  mesh = (vertices,
-        triangles) evaluates that mesh's surface instead (mesh_compare)."""
-        check_cloud_compare_args(tau, max_dist)
+        triangles) evaluates that mesh's surface instead (mesh_compare).  align
+        (cloud_compare's dict) registers the cloud, or the mesh's vertices, to
+        the truth first."""
+        check_compare_align(align, check_cloud_compare_args(tau, max_dist))
         if mesh is not None:
             with Engine(self.options, self.device) as eng:
-                return mesh_compare(eng, mesh[0], mesh[1], truth, tau, max_dist)
+                return mesh_compare(eng, mesh[0], mesh[1], truth, tau, max_dist, align)
         if isinstance(cloud, str):
             if cloud not in ("patches", "fused"):
                 raise ValueError('evaluate: cloud must be "patches", "fused" or an array')
@@ -2375,7 +2583,7 @@ class PMVS:
                 raise ValueError("evaluate: call run() first")
             cloud = self.patches if cloud == "patches" else self.fused_cloud()
         with Engine(self.options, self.device) as eng:
-            return cloud_compare(eng, cloud, truth, tau, max_dist)
+            return cloud_compare(eng, cloud, truth, tau, max_dist, align)
 
 
 def ncc_score(a: np.ndarray, b: np.ndarray, denom_min: float = 0.1) -> float:

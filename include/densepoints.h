@@ -1616,6 +1616,183 @@ int dp_cloud_clean_device(dp_ctx *ctx, const void *d_points, int64_t n, int64_t 
                           int32_t *d_map, void *d_out, int64_t *d_n_out, dp_cloud_clean_stats *stats,
                           void *stream);
 
+/* ---- a 3 x 4 transform applied to the records of a cloud ----------------------------
+ * No reference counterpart.  n records of `stride` bytes (a multiple of 4, at least
+ * 12; counts up to 2^31 - 1), the position in the first 12 bytes of each, as in
+ * dp_cloud_clean.  matrix is a host array of 12 doubles, row-major M = [A | t]:
+ * row r is (a0, a1, a2, t) = matrix[4r .. 4r + 3].  All arithmetic is fp64, one
+ * IEEE rounding per operation, in the order written.
+ *
+ * Every record is copied whole into out (the device form's d_out may equal
+ * d_points: the transform in place).  Then, for a record whose position (x, y, z)
+ * is finite in all three floats, coordinate r of the position becomes
+ *   (float)(((a0 * (double)x + a1 * (double)y) + a2 * (double)z) + t);
+ * a record whose position is not finite is left as copied.  With normal_offset >=
+ * 0 the three floats n at that byte offset of the record are the normal: with
+ *   v_r = (a0 * (double)n.x + a1 * (double)n.y) + a2 * (double)n.z,
+ *   len = dvsqrt((v_0 * v_0 + v_1 * v_1) + v_2 * v_2),
+ * they become (float)dvdiv(v_r, len) when len is finite and > 0, and are left as
+ * copied otherwise (A * n zero or not finite).  The normal of a record is treated
+ * whatever its position is.  One lane per record.
+ * Errors (DP_E_ARG): n negative or above 2^31 - 1; points NULL with n > 0; a stride
+ * that is no multiple of 4 or below 12; matrix NULL or with an entry that is not
+ * finite; normal_offset neither -1 nor a multiple of 4 in 12 .. stride - 12; out
+ * NULL (host form), d_out NULL with n > 0 (device form).
+ * Host form: *out is context-owned, n * stride bytes, valid until the next
+ * dp_cloud_transform, dp_cloud_align or destroy (NULL when n is 0).  Device form:
+ * queued on `stream` (NULL = the context's); the call does not wait. */
+int dp_cloud_transform(dp_ctx *ctx, const void *points, int64_t n, int64_t stride, const double *matrix,
+                       int64_t normal_offset, const void **out);
+int dp_cloud_transform_device(dp_ctx *ctx, const void *d_points, int64_t n, int64_t stride, const double *matrix,
+                              int64_t normal_offset, void *d_out, void *stream);
+
+/* ---- registration of one cloud to another: point-to-point ICP -----------------------
+ * No reference counterpart.  The rigid motion (or, with DP_CLOUD_ALIGN_SCALE, the
+ * similarity with s > 0) that moves the `source` cloud onto the `target` cloud,
+ * by iterated closest points trimmed at the radius max_dist: what puts a
+ * reconstruction into the frame of its ground truth before dp_cloud_nearest
+ * measures it.  The clouds are dp_cloud_nearest's: three f32 at base + i * stride,
+ * any stride that is a multiple of 4 and at least 12, counts up to 2^31 - 1, a
+ * point TAKES PART iff its three floats are finite.  All arithmetic is fp64, one
+ * IEEE rounding per operation, in exactly the order written; dvdiv and dvsqrt are
+ * the IEEE-correct quotient and square root.  There is no floating-point atomic.
+ *
+ * Options.  max_dist finite and > 0; iterations in 1..1000; min_pairs >= 3;
+ * rms_tol finite and >= 0 (0 = never stop early); flags = 0 or
+ * DP_CLOUD_ALIGN_SCALE.  init: 12 finite doubles, the first M (row-major [A | t]
+ * as in dp_cloud_transform), or NULL for the identity.
+ *
+ * A PASS with the current M (steps 1 to 4):
+ * 1. y_i = dp_cloud_transform's position expression of source point x_i under M,
+ *    into a packed scratch array (a point that is not finite is copied as it is).
+ *    The source is never modified, and every pass starts from the original x_i:
+ *    transforms are never composed and rounded points never chained.
+ * 2. c(i), dist_i = dp_cloud_nearest(y, target, max_dist), bit for bit: the same
+ *    d2, the inclusive radius, ties to the lowest index, c(i) = -1 for a y_i that
+ *    does not take part or has no candidate.  i is MATCHED iff c(i) >= 0; q_i is
+ *    target point c(i).  The target grid is built once per call.
+ * 3. m = the number of matched i (an integer).  Six sums over i in source order,
+ *    of x_i.x, x_i.y, x_i.z, q_i.x, q_i.y, q_i.z: the term of a matched i is
+ *    (double)v + 0.0 (the + 0.0 turns a -0.0 into +0.0), of an unmatched i +0.0.
+ *    Each sum is S of dp_cloud_clean: the balanced pairwise tree over the n_source
+ *    terms padded with +0.0 to the next power of two.  mux_a = dvdiv(sum, (double)m)
+ *    and muq_a likewise; all six are 0 when m = 0.
+ * 4. With dx_a = (double)x_i.a - mux_a and dq_b = (double)q_i.b - muq_b, eleven
+ *    sums S of the same kind (each term t entering as t + 0.0, +0.0 when unmatched):
+ *      S_ab = sum of dx_a * dq_b   (a, b in x, y, z; nine sums),
+ *      Sx   = sum of (dx_x * dx_x + dx_y * dx_y) + dx_z * dx_z,
+ *      E    = sum of d2_i,  d2_i = (ex * ex + ey * ey) + ez * ez,  ex = (double)y_i.x -
+ *             (double)q_i.x and so on: the search's own expression, the same bits.
+ *    The pass's RECORD is {matched = m, rms = m > 0 ? dvsqrt(dvdiv(E, (double)m)) : 0}.
+ *
+ * The SOLVE (step 5), by one lane, from the S_ab of a pass:
+ *   N00 = (Sxx + Syy) + Szz,  N11 = (Sxx - Syy) - Szz,  N22 = (Syy - Sxx) - Szz,
+ *   N33 = (Szz - Sxx) - Syy,  N01 = Syz - Szy,  N02 = Szx - Sxz,  N03 = Sxy - Syx,
+ *   N12 = Sxy + Syx,  N13 = Szx + Sxz,  N23 = Syz + Szy,  N symmetric (Horn 1987).
+ *   V = the 4 x 4 identity.  DP_CLOUD_ALIGN_SWEEPS times, for (p, q) = (0,1), (0,2),
+ *   (0,3), (1,2), (1,3), (2,3) in this order: if N_pq == 0.0 the rotation is
+ *   skipped; otherwise
+ *     theta = dvdiv(N_qq - N_pp, 2.0 * N_pq);
+ *     t = dvdiv(theta >= 0 ? 1.0 : -1.0, fabs(theta) + dvsqrt(theta * theta + 1.0));
+ *     c = dvdiv(1.0, dvsqrt(t * t + 1.0));  s = t * c;
+ *     for the two k other than p and q, ascending:  u = N_kp, w = N_kq;
+ *       N_kp = N_pk = c * u - s * w;  N_kq = N_qk = s * u + c * w;
+ *     h = t * N_pq;  N_pp = N_pp - h;  N_qq = N_qq + h;  N_pq = N_qp = 0.0;
+ *     for k = 0..3:  u = V_kp, w = V_kq;  V_kp = c * u - s * w;  V_kq = s * u + c * w.
+ *   j = the index of the largest N_jj, the lowest on ties; v = column j of V;
+ *   len = dvsqrt(((v0 * v0 + v1 * v1) + v2 * v2) + v3 * v3);  q_k = dvdiv(v_k, len);
+ *   R00 = ((q0 * q0 + q1 * q1) - q2 * q2) - q3 * q3,  R01 = 2.0 * (q1 * q2 - q0 * q3),
+ *   R02 = 2.0 * (q1 * q3 + q0 * q2),  R10 = 2.0 * (q1 * q2 + q0 * q3),
+ *   R11 = ((q0 * q0 - q1 * q1) + q2 * q2) - q3 * q3,  R12 = 2.0 * (q2 * q3 - q0 * q1),
+ *   R20 = 2.0 * (q1 * q3 - q0 * q2),  R21 = 2.0 * (q2 * q3 + q0 * q1),
+ *   R22 = ((q0 * q0 - q1 * q1) - q2 * q2) + q3 * q3:  the rotation of a quaternion,
+ *   proper whatever the clouds are; a mirrored cloud never yields a reflection.
+ *   scale = 1.0, or with DP_CLOUD_ALIGN_SCALE dvdiv(g, Sx), g = the sum in the order
+ *   (a, b) = (x,x), (x,y), (x,z), (y,x), .. (z,z) of R_ba * S_ab, starting from the
+ *   first product.  A_rk = scale * R_rk;  t_r = muq_r - ((A_r0 * mux_x + A_r1 * mux_y)
+ *   + A_r2 * mux_z);  the new M = [A | t].
+ *   DP_CLOUD_ALIGN_SWEEPS is 10.  On the test inputs of tests/cloudalign_ref.py
+ *   (random, coplanar, collinear, mirrored, duplicated clouds) the reference's
+ *   off-diagonal mass sqrt(sum of N_pq^2, p < q) is below 2^-50 of the largest
+ *   |N_jj| after at most 4 sweeps and exactly zero after 6 (cyclic Jacobi
+ *   converges quadratically once the off-diagonal part is small); 10 leaves a
+ *   margin for clustered eigenvalues, and a sweep over a diagonal matrix skips
+ *   every rotation, so the extra sweeps change no bit.
+ *
+ * The iteration.  M = init.  Step k = 0, 1, .. iterations - 1: a pass with M
+ * writes trace[k]; then the call STOPS, keeping M, with stop_reason
+ *   DP_CLOUD_ALIGN_STOP_PAIRS       when m < min_pairs;  otherwise
+ *   DP_CLOUD_ALIGN_STOP_RMS         when k > 0, rms_tol > 0 and fabs(rms - rms of
+ *                                   step k - 1) <= rms_tol;  otherwise
+ *   DP_CLOUD_ALIGN_STOP_DEGENERATE  when Sx == 0, or the solve's scale is not
+ *                                   finite and > 0, or an entry of the new M is
+ *                                   not finite;
+ * otherwise M becomes the solve's.  After the update of step iterations - 1 one
+ * more pass writes trace[iterations], and stop_reason is
+ * DP_CLOUD_ALIGN_STOP_ITERATIONS.  iterations_run = the number of updates made.
+ * A pass's record is the residual BEFORE that step's update.  With n_source = 0
+ * or n_target = 0 (not an error) stop_reason is DP_CLOUD_ALIGN_STOP_EMPTY, the
+ * result is init and trace[0] = {0, 0}.
+ * Outputs (host memory in both forms).  matrix: the final M, 12 doubles.  *scale:
+ * the scale of the last update, 1.0 when none was made (init is not decomposed).
+ * trace: iterations + 1 records, those after the last pass zero.  index and dist
+ * (optional): c(i) and dist_i of the last pass, per source point.  Statistics:
+ * dp_cloud_nearest's counters of the last pass (queries are the y_i), grid_cells
+ * and max_cell_targets, iterations_run, stop_reason, grid_ms = device time of
+ * the target grid, iterate_ms = of everything after it, the waits included.
+ * The call waits once per pass, to read the pass's record and the solve's verdict
+ * (24 bytes): that wait is what makes the early stop real.  Nothing else
+ * crosses the bus before the end.
+ * Errors (DP_E_ARG): dp_cloud_nearest's on the counts, pointers, strides, opts
+ * and max_dist; iterations, min_pairs or rms_tol outside the ranges above; an
+ * unknown flag; an init entry that is not finite; matrix, scale or trace NULL;
+ * an output that equals an input; device form: one of d_index and d_dist given
+ * without the other.
+ * Host form: *index and *dist (pass NULL for both when not wanted) are
+ * context-owned, valid until the next dp_cloud_align, dp_cloud_nearest or
+ * destroy (NULL when n_source is 0).  Device form: device clouds, d_index and
+ * d_dist caller buffers of n_source entries or both NULL; queued on `stream`
+ * (NULL = the context's), and the call always waits.
+ * Limits: point to point, no subsampling, no global search: a bad start is the
+ * caller's init.  Scratch is dp_cloud_nearest's (shared with it) plus 20 bytes
+ * per source point and the sum levels (88 bytes per 256 source points). */
+#define DP_CLOUD_ALIGN_SCALE 1
+#define DP_CLOUD_ALIGN_SWEEPS 10
+#define DP_CLOUD_ALIGN_STOP_ITERATIONS 0
+#define DP_CLOUD_ALIGN_STOP_RMS 1
+#define DP_CLOUD_ALIGN_STOP_PAIRS 2
+#define DP_CLOUD_ALIGN_STOP_DEGENERATE 3
+#define DP_CLOUD_ALIGN_STOP_EMPTY 4
+typedef struct dp_cloud_align_options {
+    float max_dist;      /* trimming radius, world units (> 0, finite; no default) */
+    int32_t iterations;  /* 1..1000                                               */
+    int32_t min_pairs;   /* >= 3                                                  */
+    int32_t flags;       /* DP_CLOUD_ALIGN_SCALE; another bit is DP_E_ARG         */
+    double rms_tol;      /* >= 0, finite; 0 = never stop early                    */
+} dp_cloud_align_options;
+typedef struct dp_cloud_align_step {
+    int64_t matched;
+    double rms;
+} dp_cloud_align_step;
+typedef struct dp_cloud_align_stats {
+    int64_t queries, targets;          /* those taking part, in the last pass   */
+    int64_t skipped_queries, skipped_targets, matched, unmatched;
+    int64_t grid_cells, max_cell_targets;  /* facts of the implementation, not of the spec */
+    int64_t iterations_run, stop_reason;
+    double grid_ms, iterate_ms;
+} dp_cloud_align_stats;
+
+int dp_cloud_align(dp_ctx *ctx, const void *source, int64_t n_source, int64_t source_stride,
+                   const void *target, int64_t n_target, int64_t target_stride,
+                   const dp_cloud_align_options *opts, const double *init, double *matrix, double *scale,
+                   dp_cloud_align_step *trace, const int32_t **index, const float **dist,
+                   dp_cloud_align_stats *stats);
+int dp_cloud_align_device(dp_ctx *ctx, const void *d_source, int64_t n_source, int64_t source_stride,
+                          const void *d_target, int64_t n_target, int64_t target_stride,
+                          const dp_cloud_align_options *opts, const double *init, double *matrix, double *scale,
+                          dp_cloud_align_step *trace, int32_t *d_index, float *d_dist,
+                          dp_cloud_align_stats *stats, void *stream);
+
 /* ---- nearest-triangle distances from points to a mesh surface ---------------------
  * No reference counterpart.  For every query point the nearest triangle of a
  * mesh within a radius, its distance and the closest point on it: the primitive

@@ -102,6 +102,15 @@ void usage()
                  "                             mesh's surface -- dp_mesh_nearest -- and, with --mesh-decimate,\n"
                  "                             decimate_deviation: how far the decimated surface lies from\n"
                  "                             the one it was made of, within the radius D)\n"
+                 "               [--eval-align [--eval-align-iterations N] [--eval-align-radius R]\n"
+                 "                [--eval-align-scale]]\n"
+                 "                            (with --evaluate: the patches are first registered to the truth\n"
+                 "                             by point-to-point ICP on the device -- dp_cloud_align, N (30)\n"
+                 "                             iterations in 1..1000, pairs trimmed at R, default D; -scale\n"
+                 "                             estimates a similarity -- and every evaluated cloud is moved\n"
+                 "                             by that transform, on copies: the files are not changed; the\n"
+                 "                             report gains align: the matrix, the scale, the iterations run,\n"
+                 "                             the pairs and the rms before and after)\n"
                  "       densify --synthetic V,W,H,KIND --write-scene DIR\n");
 }
 
@@ -160,6 +169,8 @@ bool set_flag(const std::string &o, Args &a)
     else if (o == "--mesh-colour") a.mesh_colour = true;
     else if (o == "--mesh-colour-bilinear") a.mesh_colour_bilinear = true;
     else if (o == "--eval-mesh-surface") a.eval_mesh_surface = true;
+    else if (o == "--eval-align") a.eval_align = true;
+    else if (o == "--eval-align-scale") a.eval_align_scale = true;
     else if (o == "--epipolar-matching") a.matcher.epipolar_matching = 1;
     else return false;
     return true;
@@ -334,6 +345,16 @@ Parse parse_args(int argc, char **argv, Args &a, std::string &error)
                 a.eval_max_dist = t;
             else
                 error = "--eval-max-dist expects a finite number > 0";
+        } else if (o == "--eval-align-iterations") {
+            if (int_in_range(v, 1, 1000, k))
+                a.eval_align_iterations = (int)k;
+            else
+                error = "--eval-align-iterations expects 1..1000";
+        } else if (o == "--eval-align-radius") {
+            if (number_in_range(v, 0.0, 3.0e38, t) && (float)t > 0.0f)
+                a.eval_align_radius = t;
+            else
+                error = "--eval-align-radius expects a finite number > 0";
         } else if (o == "--exchange") {
             a.exchange_mode = v;
             if (one_of(v, {"auto", "rccl", "copy"}) < 0)
@@ -421,6 +442,14 @@ Parse parse_args(int argc, char **argv, Args &a, std::string &error)
         error = "--eval-mesh-surface needs --evaluate and --mesh";
         return Parse::UsageError;
     }
+    if (!a.eval_align && (a.eval_align_iterations > 0 || a.eval_align_radius > 0.0 || a.eval_align_scale)) {
+        error = "--eval-align-iterations, -radius and -scale need --eval-align";
+        return Parse::UsageError;
+    }
+    if (a.eval_align && a.eval_path.empty()) {
+        error = "--eval-align needs --evaluate";
+        return Parse::UsageError;
+    }
     if (!a.eval_path.empty()) {
         if (!(a.eval_tau > 0.0)) {
             error = "--evaluate needs --eval-tau";
@@ -432,6 +461,12 @@ Parse parse_args(int argc, char **argv, Args &a, std::string &error)
             error = "--eval-max-dist expects a finite number of at least --eval-tau";
             return Parse::UsageError;
         }
+    }
+    if (a.eval_align) {
+        if (a.eval_align_iterations == 0)
+            a.eval_align_iterations = 30;
+        if (a.eval_align_radius == 0.0)
+            a.eval_align_radius = a.eval_max_dist;
     }
     if (a.iterations > 1)
         a.do_filter = true; // the filter is what tells the rounds apart

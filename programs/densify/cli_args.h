@@ -84,6 +84,13 @@ struct Args {
     // the truth (dp_mesh_nearest) and, with --mesh-decimate, the deviation of the
     // decimated surface from the one before, in the report
     bool eval_mesh_surface = false;
+    // --eval-align [--eval-align-iterations N] [--eval-align-radius R]
+    // [--eval-align-scale]: with --evaluate, the patches are registered to the
+    // truth first (dp_cloud_align) and every evaluated cloud is moved by that
+    // transform, on copies; the report gains "align"
+    bool eval_align = false, eval_align_scale = false;
+    int eval_align_iterations = 0;  // 0: not given; parse_args resolves it to 30
+    double eval_align_radius = 0.0; // 0: not given; parse_args resolves it to eval_max_dist
 
     Args();
 };

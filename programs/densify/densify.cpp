@@ -449,10 +449,21 @@ struct Evaluation {
     DeviceMaps mem;
     float *d_truth = nullptr;
     std::string entries; // "name": {...}, ...
+    // --eval-align: the options, the transform once it is estimated, the report's member
+    dp_cloud_align_options align_opts{};
+    bool align = false, aligned = false;
+    double M[12] = {0};
+    std::string align_json;
 
     Evaluation(dp_ctx *c, const Args &args, const std::vector<double> &truth)
-        : ctx(c), tau(args.eval_tau), max_dist((float)args.eval_max_dist), n_truth((int64_t)(truth.size() / 3))
+        : ctx(c), tau(args.eval_tau), max_dist((float)args.eval_max_dist), n_truth((int64_t)(truth.size() / 3)),
+          align(args.eval_align)
     {
+        align_opts.max_dist = (float)args.eval_align_radius;
+        align_opts.iterations = args.eval_align_iterations;
+        align_opts.min_pairs = 3;
+        align_opts.flags = args.eval_align_scale ? DP_CLOUD_ALIGN_SCALE : 0;
+        align_opts.rms_tol = 0.0;
         std::vector<float> xyz(truth.begin(), truth.end());
         d_truth = (float *)mem.bytes(xyz.size() * sizeof(float), "--evaluate");
         if (!xyz.empty() && hipMemcpy(d_truth, xyz.data(), xyz.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
@@ -553,6 +564,8 @@ struct Evaluation {
     // against the mesh's surface
     void add_mesh_surface(const dp_mesh_vertex *d_v, int64_t nv, const int32_t *d_t, int64_t nt)
     {
+        DeviceMaps copy;
+        d_v = (const dp_mesh_vertex *)moved(copy, d_v, nv, sizeof(dp_mesh_vertex));
         double p = 0.0, r = 0.0;
         const std::string acc = side(d_v, nv, sizeof(dp_mesh_vertex), d_truth, n_truth, 12, &p);
         Found f(n_truth);
@@ -592,9 +605,50 @@ struct Evaluation {
                    ba + ", \"max\": " + number(top) + "}";
     }
 
-    // the cloud of n points at d_points (device memory, `stride` bytes apart) against the truth
+    // --eval-align: the transform that moves the cloud onto the truth (dp_cloud_align_device)
+    void estimate(const void *d_points, int64_t n, int64_t stride)
+    {
+        std::vector<dp_cloud_align_step> trace((size_t)align_opts.iterations + 1);
+        dp_cloud_align_stats st;
+        double scale = 1.0;
+        check(ctx,
+              dp_cloud_align_device(ctx, n ? d_points : nullptr, n, stride, n_truth ? d_truth : nullptr, n_truth, 12,
+                                    &align_opts, nullptr, M, &scale, trace.data(), nullptr, nullptr, &st, nullptr),
+              "dp_cloud_align_device");
+        aligned = true;
+        const dp_cloud_align_step &last = trace[(size_t)st.iterations_run];
+        align_json = ", \"align\": {\"matrix\": [";
+        for (int k = 0; k < 12; ++k)
+            align_json += std::string(k ? ", " : "") + number(M[k]);
+        char buf[120];
+        std::snprintf(buf, sizeof buf, ", \"iterations\": %lld, \"matched\": %lld, ", (long long)st.iterations_run,
+                      (long long)last.matched);
+        align_json += "], \"scale\": " + number(scale) + buf + "\"rms_before\": " + number(trace[0].rms) +
+                      ", \"rms\": " + number(last.rms) + "}";
+    }
+
+    // --eval-align: a copy of n records (the position first) under the transform; without it the records themselves
+    const void *moved(DeviceMaps &copy, const void *d_records, int64_t n, int64_t stride)
+    {
+        if (!aligned)
+            return d_records;
+        void *d = copy.bytes((size_t)n * (size_t)stride, "--eval-align");
+        check(ctx, dp_cloud_transform_device(ctx, n ? d_records : nullptr, n, stride, M, -1, d, nullptr),
+              "dp_cloud_transform_device");
+        return d;
+    }
+
+    // the cloud of n points at d_points (device memory, `stride` bytes apart, each the head
+    // of its record) against the truth
     void add(const char *name, const void *d_points, int64_t n, int64_t stride)
     {
+        static_assert(offsetof(dp_patch, pos) == 0 && offsetof(dp_fused_point, pos) == 0 &&
+                          offsetof(dp_mesh_vertex, pos) == 0,
+                      "moved() copies records from their positions on");
+        if (align && !aligned)
+            estimate(d_points, n, stride); // the first cloud added: the written patches
+        DeviceMaps copy;
+        d_points = moved(copy, d_points, n, stride);
         double p = 0.0, r = 0.0;
         const std::string acc = side(d_points, n, stride, d_truth, n_truth, 12, &p);
         const std::string com = side(d_truth, n_truth, 12, d_points, n, stride, &r);
@@ -616,7 +670,7 @@ struct Evaluation {
 
     std::string report() const
     {
-        return ", \"evaluate\": {" + entries + "}";
+        return ", \"evaluate\": {" + entries + "}" + align_json;
     }
 };
 
