@@ -32,6 +32,7 @@ from .pmvs import (  # noqa: F401
     check_cloud_clean_args,
     check_cloud_knn_args,
     check_cloud_nearest_args,
+    check_cloud_normals_args,
     check_cloud_transform_args,
     check_fuse_args,
     check_mapref_args,
@@ -43,6 +44,7 @@ from .pmvs import (  # noqa: F401
     check_mesh_smooth_args,
     check_tsdf_args,
     cloud_compare,
+    cloud_normal_error,
     empty_patches,
     mask_from_list,
     mesh_compare,

@@ -444,6 +444,22 @@ CLOUD_KNN_EXCLUDE_SELF = 1
 CLOUD_CLEAN_RADIUS_ONLY = 1
 
 
+class DpCloudNormalsOptions(ctypes.Structure):
+    """dp_cloud_normals_options: the options of dp_cloud_normals (include/densepoints.h)."""
+    _fields_ = [("max_dist", ctypes.c_float), ("k", ctypes.c_int32), ("min_neighbours", ctypes.c_int32),
+                ("flags", ctypes.c_int32)]
+
+
+class DpCloudNormalsStats(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int64) for n in (
+        "points", "skipped", "estimated", "sparse", "degenerate", "flipped", "unoriented", "grid_cells",
+        "max_cell_targets")] + [("knn_ms", ctypes.c_double), ("normals_ms", ctypes.c_double)]
+
+
+assert ctypes.sizeof(DpCloudNormalsOptions) == 16 and ctypes.sizeof(DpCloudNormalsStats) == 88
+CLOUD_NORMALS_ORIENT_VIEWPOINT, CLOUD_NORMALS_ORIENT_DIRECTION = 1, 2
+
+
 class DpCloudAlignOptions(ctypes.Structure):
     """dp_cloud_align_options: the options of dp_cloud_align (include/densepoints.h)."""
     _fields_ = [("max_dist", ctypes.c_float), ("iterations", ctypes.c_int32), ("min_pairs", ctypes.c_int32),
@@ -641,6 +657,8 @@ SIGNATURES = [
                                  _P, _P, _P]),
     ("dp_cloud_clean", _I, [_P, _P, ctypes.c_int64, ctypes.c_int64, _P, _P, _P, _P, _P, _P, _P]),
     ("dp_cloud_clean_device", _I, [_P, _P, ctypes.c_int64, ctypes.c_int64, _P, _P, _P, _P, _P, _P, _P, _P]),
+    ("dp_cloud_normals", _I, [_P, _P, ctypes.c_int64, ctypes.c_int64, _P, _P, ctypes.c_int64, _P, _P, _P, _P]),
+    ("dp_cloud_normals_device", _I, [_P, _P, ctypes.c_int64, ctypes.c_int64, _P, _P, ctypes.c_int64, _P, _P, _P, _P, _P]),
     ("dp_cloud_transform", _I, [_P, _P, ctypes.c_int64, ctypes.c_int64, _P, ctypes.c_int64, _P]),
     ("dp_cloud_transform_device", _I, [_P, _P, ctypes.c_int64, ctypes.c_int64, _P, ctypes.c_int64, _P, _P]),
     ("dp_cloud_align", _I, [_P, _P, ctypes.c_int64, ctypes.c_int64, _P, ctypes.c_int64, ctypes.c_int64, _P, _P, _P, _P, _P,

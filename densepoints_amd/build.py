@@ -20,7 +20,7 @@ SOURCES = ["dp_capi.hip", "dp_densify.hip", "dp_synth.hip", "dp_refine.hip", "dp
            "dp_fast.hip", "dp_fast_kernel.hip", "dp_akaze.hip", "dp_bfs.hip", "dp_render.hip", "dp_fuse.hip",
            "dp_mapref.hip", "dp_tsdf.hip", "dp_meshclean.hip", "dp_meshsmooth.hip", "dp_meshdecimate.hip",
            "dp_meshrender.hip", "dp_meshcolour.hip", "dp_cloudnearest.hip",
-           "dp_meshnearest.hip", "dp_cloudknn.hip", "dp_cloudalign.hip"]
+           "dp_meshnearest.hip", "dp_cloudknn.hip", "dp_cloudalign.hip", "dp_cloudnormals.hip"]
 HEADERS = ["dp_internal.h", "dp_geom.h", "dp_detmath.h", "dp_synth.h", "dp_devmath.h", "dp_ctx.h", "dp_buf.h", "dp_dlt.h",
            "dp_seeds.h", "dp_seedgen.h", "dp_orb.h", "dp_orb_pattern.h", "dp_akaze.h", "dp_wave.h", "dp_fast.h", "dp_mapdev.h",
            "dp_meshdev.h", "dp_clouddev.h"]

@@ -197,33 +197,6 @@ __global__ void align_mean_kernel(AlignArgs a, const double *sum)
     }
 }
 
-template <int P, int Q> __device__ __forceinline__ void jacobi_rotate(double (&N)[4][4], double (&V)[4][4])
-{
-    const double apq = N[P][Q];
-    if (apq == 0.0)
-        return;
-    const double theta = dpg::dvdiv(N[Q][Q] - N[P][P], 2.0 * apq);
-    const double t = dpg::dvdiv(theta >= 0.0 ? 1.0 : -1.0, fabs(theta) + dpg::dvsqrt(theta * theta + 1.0));
-    const double c = dpg::dvdiv(1.0, dpg::dvsqrt(t * t + 1.0)), s = t * c;
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-        if (k != P && k != Q) {
-            const double u = N[k][P], w = N[k][Q];
-            N[k][P] = N[P][k] = c * u - s * w;
-            N[k][Q] = N[Q][k] = s * u + c * w;
-        }
-    const double h = t * apq;
-    N[P][P] = N[P][P] - h;
-    N[Q][Q] = N[Q][Q] + h;
-    N[P][Q] = N[Q][P] = 0.0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const double u = V[k][P], w = V[k][Q];
-        V[k][P] = c * u - s * w;
-        V[k][Q] = s * u + c * w;
-    }
-}
-
 // sum: the eleven sums of step 4, NULL for an empty source
 __global__ void align_solve_kernel(AlignArgs a, const double *sum)
 {

@@ -319,8 +319,9 @@ static int knn_check(dp_ctx *c, const std::string &w, const void *queries, int64
     return DP_OK;
 }
 
-// queues the search of device clouds on s (d_dist may be NULL: dp_cloud_clean's search)
-static int knn_queue(dp_ctx *c, const dp_cloud_knn_options &o, const void *d_queries, int64_t nq, int64_t qstride,
+// queues the search of device clouds on s (d_dist may be NULL: dp_cloud_clean's
+// and dp_cloud_normals' searches); declared in dp_clouddev.h
+int knn_queue(dp_ctx *c, const dp_cloud_knn_options &o, const void *d_queries, int64_t nq, int64_t qstride,
                      const void *d_targets, int64_t nt, int64_t tstride, int32_t *d_index, float *d_dist,
                      int32_t *d_count, hipStream_t s)
 {

@@ -268,6 +268,15 @@ struct CloudKnnScratch {
     Timer time[2];         // dp_cloud_clean: the search; the filter
 };
 
+// dp_cloud_normals (dp_cloudnormals.hip).  The search is dp_cloud_knn's and the
+// self-search rows and counts, the host form's staged input, device results and
+// pinned results are CloudKnnScratch's (a call of one ends the validity of the
+// other's host results).  Here: the counters and the two times.
+struct CloudNormalsScratch {
+    StripedCounters count; // + the grid
+    Timer time[2];         // the search; everything after it
+};
+
 // what dp_cloud_align keeps on the device between its kernels: the current M and
 // its scale, the means of the last pass, the rms of the step before, the
 // targets taking part (the grid's counter, which every pass zeroes again), and
@@ -391,6 +400,7 @@ struct dp_ctx {
     dpk::MeshColourScratch meshcolour;
     dpk::CloudNearestScratch cloudnearest;
     dpk::CloudKnnScratch cloudknn;
+    dpk::CloudNormalsScratch cloudnormals;
     dpk::CloudAlignScratch cloudalign;
     dpk::MeshNearestScratch meshnearest;
     HostBuf<dp_patch> result; // dp_densify / dp_densify_result output (pinned)

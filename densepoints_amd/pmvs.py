@@ -1378,6 +1378,80 @@ class Engine:
                                               ctypes.byref(st) if stats else None, _addr(stream)))
         return _stats_dict(st) if stats else None
 
+    # ---- PCA normals of a cloud (include/densepoints.h dp_cloud_normals) ----
+    def cloud_normals(self, points, k: int = 16, *, max_dist: float, min_neighbours: int = 3, viewpoint=None,
+                      directions=None) -> dict:
+        """dp_cloud_normals: for every point the unit normal of the plane fitted
+        to its k nearest points within max_dist (itself included) and the surface
+        variation of that neighbourhood.  `points` is what cloud_nearest takes.
+        viewpoint (one xyz, or an (n, 3) array) turns every normal toward that
+        position; directions (an (n, 3) array, or True for the records' own
+        `normal` field, read in place) toward that direction; without either the
+        sign is the canonical one.  Returns {"normal" (n x 3 float32, zero where
+        none was estimated), "variation" (float32, inf there), "count" (int32,
+        the neighbourhood's size), "stats"}.  Needs no views."""
+        pa, pp, n, stride = _cloud_points("cloud_normals", points)
+        if viewpoint is not None and directions is not None:
+            raise ValueError("cloud_normals: viewpoint and directions exclude each other")
+        orient, toward, ta, ts = None, None, None, 0
+        if viewpoint is not None:
+            orient = "viewpoint"
+            ta = np.ascontiguousarray(viewpoint, dtype=np.float32)
+            if ta.shape == (3,):
+                ts = 0
+            elif ta.shape == (n, 3):
+                ts = 12
+            else:
+                raise ValueError("cloud_normals: viewpoint must be one xyz or an n x 3 array")
+            toward = ta.ctypes.data
+        elif directions is not None:
+            orient = "direction"
+            if isinstance(directions, (bool, np.bool_)):
+                if not directions:
+                    raise ValueError("cloud_normals: directions must be an n x 3 array or True")
+                toward, ts = pa.ctypes.data + _cloud_normal_offset("cloud_normals", pa, True), stride
+            else:
+                ta = np.ascontiguousarray(directions, dtype=np.float32)
+                if ta.shape != (n, 3):
+                    raise ValueError("cloud_normals: directions must be an n x 3 array or True")
+                toward, ts = ta.ctypes.data, 12
+        cno = check_cloud_normals_args(n, k, max_dist, min_neighbours, orient, orient is not None, ts, stride)
+        pn, pv, pc, st = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p(), N.DpCloudNormalsStats()
+        self._check(lib.dp_cloud_normals(self._ctx, _addr(pp) if n else None, n, stride, ctypes.byref(cno),
+                                         _addr(toward) if orient else None, ts, ctypes.byref(pn), ctypes.byref(pv),
+                                         ctypes.byref(pc), ctypes.byref(st)))
+        normal, variation, count = np.zeros((n, 3), np.float32), np.zeros(n, np.float32), np.zeros(n, np.int32)
+        if n:
+            ctypes.memmove(normal.ctypes.data, pn.value, normal.nbytes)
+            ctypes.memmove(variation.ctypes.data, pv.value, variation.nbytes)
+            ctypes.memmove(count.ctypes.data, pc.value, count.nbytes)
+        del pa, ta
+        return {"normal": normal, "variation": variation, "count": count, "stats": _stats_dict(st)}
+
+    def cloud_normals_device(self, d_points, n: int, stride: int, k: int, max_dist: float, d_normal, d_variation=None,
+                             d_count=None, min_neighbours: int = 3, orient=None, d_toward=None,
+                             toward_stride: int = 0, stream: int | None = None, stats: bool = True) -> dict | None:
+        """dp_cloud_normals_device: n device records of `stride` bytes estimated
+        into 3 n float32 at d_normal and, where given, n float32 at d_variation
+        and n int32 at d_count.  orient is None, "viewpoint" or "direction"; with
+        one, entry i of `toward` is the three float32 at d_toward + i *
+        toward_stride (0 = one entry for all), which may lie in the records.
+        Queued on `stream`; waits only for the statistics (stats=False: no wait,
+        returns None)."""
+        n = _mesh_count("cloud_normals_device", n)
+        cno = check_cloud_normals_args(n, k, max_dist, min_neighbours, orient, bool(d_toward), toward_stride, stride,
+                                       inputs=(d_points, d_toward), outputs=(d_normal, d_variation, d_count))
+        if n and not d_points:
+            raise ValueError("cloud_normals_device: the points must be given")
+        if n and not d_normal:
+            raise ValueError("cloud_normals_device: d_normal must be given")
+        st = N.DpCloudNormalsStats()
+        self._check(lib.dp_cloud_normals_device(self._ctx, _addr(d_points), n, stride, ctypes.byref(cno),
+                                                _addr(d_toward), int(toward_stride), _addr(d_normal),
+                                                _addr(d_variation), _addr(d_count),
+                                                ctypes.byref(st) if stats else None, _addr(stream)))
+        return _stats_dict(st) if stats else None
+
     # ---- a cloud's records under a 3 x 4 transform (include/densepoints.h dp_cloud_transform) ----
     def cloud_transform(self, points, matrix, normals: bool = False) -> np.ndarray:
         """dp_cloud_transform: the records of `points` ((n, 3) float32, or a
@@ -1633,6 +1707,42 @@ def check_cloud_clean_args(n, k, max_dist, std_mul=2.0, min_neighbours=1, radius
                                  N.CLOUD_CLEAN_RADIUS_ONLY if radius_only else 0)
 
 
+def check_cloud_normals_args(n, k=16, max_dist=None, min_neighbours=3, orient=None, toward=False, toward_stride=0,
+                             stride=12, inputs=(), outputs=()):
+    """Argument validation of Engine.cloud_normals[_device] (the limits of
+    dp_cloud_normals, raised as ValueError before any device call); returns the
+    dp_cloud_normals_options.  orient is None, "viewpoint" or "direction";
+    `toward` says whether the entries are given (required with an orient mode,
+    refused without one) and toward_stride is 0 or a multiple of 4 that is at
+    least 12.  max_dist is judged as the float32 the struct holds."""
+    def whole(x):
+        return isinstance(x, (int, np.integer)) and not isinstance(x, bool)
+
+    _mesh_count("cloud_normals", n)
+    if not whole(stride) or stride < 12 or stride % 4:
+        raise ValueError("cloud_normals: stride must be a multiple of 4 and at least 12")
+    _cloud_search_args("cloud_normals", k, max_dist)
+    if k < 3:
+        raise ValueError("cloud_normals: k must be in 3..32")
+    if not whole(min_neighbours) or not 3 <= min_neighbours <= k:
+        raise ValueError("cloud_normals: min_neighbours must be in 3..k")
+    if orient not in (None, "viewpoint", "direction"):
+        raise ValueError("cloud_normals: orient must be None, 'viewpoint' or 'direction'")
+    if not whole(toward_stride):
+        raise ValueError("cloud_normals: toward_stride must be a whole number")
+    if orient is None:
+        if toward or toward_stride != 0:
+            raise ValueError("cloud_normals: toward and toward_stride need an orient mode")
+    else:
+        if not toward:
+            raise ValueError("cloud_normals: an orient mode needs toward")
+        if toward_stride != 0 and (toward_stride < 12 or toward_stride % 4):
+            raise ValueError("cloud_normals: toward_stride must be 0 or a multiple of 4 and at least 12")
+    _cloud_aliases("cloud_normals", inputs, outputs, among_outputs=True)
+    flags = {None: 0, "viewpoint": N.CLOUD_NORMALS_ORIENT_VIEWPOINT, "direction": N.CLOUD_NORMALS_ORIENT_DIRECTION}
+    return N.DpCloudNormalsOptions(float(max_dist), int(k), int(min_neighbours), flags[orient])
+
+
 def _cloud_matrix(who: str, name: str, m) -> np.ndarray:
     """a 3 x 4 (or 12) array of finite numbers as contiguous float64"""
     try:
@@ -1776,7 +1886,59 @@ def check_cloud_compare_args(tau, max_dist=None) -> float:
     return float(max_dist)
 
 
-def cloud_compare(eng, recon, truth, tau: float, max_dist=None, align=None) -> dict:
+def cloud_normal_error(recon_normals, truth_normals, index, dist, tau) -> dict:
+    """The error of a reconstruction's normals against a truth's, over the
+    matches of a cloud_nearest call (recon -> truth): query i counts iff index[i]
+    >= 0, dist[i] <= tau, and its own normal a and the truth's normal b =
+    truth_normals[index[i]] are both finite and not zero.  Its angle is the
+    unsigned one, in degrees and fp64: with dot = (a.x * b.x + a.y * b.y) + a.z *
+    b.z and |a| = sqrt((a.x * a.x + a.y * a.y) + a.z * a.z),
+    degrees(arccos(min(1, |dot| / (|a| * |b|)))) -- a truth normal has no sign.
+    Returns n, mean_deg, median_deg and p90_deg (cloud_quantile), NaN when n is 0."""
+    a = np.asarray(recon_normals, dtype=np.float64).reshape(-1, 3)
+    t = np.asarray(truth_normals, dtype=np.float64).reshape(-1, 3)
+    index = np.asarray(index).reshape(-1)
+    dist = np.asarray(dist, dtype=np.float64).reshape(-1)
+    if not (len(a) == len(index) == len(dist)):
+        raise ValueError("cloud_normal_error: recon_normals, index and dist must have one entry per query")
+    if len(index) and int(index.max()) >= len(t):
+        raise ValueError("cloud_normal_error: index must point into truth_normals")
+    with np.errstate(invalid="ignore"):
+        ok = (index >= 0) & (dist <= float(tau))
+    a = a[ok]
+    b = t[index[ok]] if len(t) else np.zeros((0, 3))
+    ok = np.isfinite(a).all(axis=1) & np.isfinite(b).all(axis=1) & (a != 0).any(axis=1) & (b != 0).any(axis=1)
+    a, b = a[ok], b[ok]
+    with np.errstate(over="ignore", invalid="ignore"):
+        dot = np.abs((a[:, 0] * b[:, 0] + a[:, 1] * b[:, 1]) + a[:, 2] * b[:, 2])
+        la = np.sqrt((a[:, 0] * a[:, 0] + a[:, 1] * a[:, 1]) + a[:, 2] * a[:, 2])
+        lb = np.sqrt((b[:, 0] * b[:, 0] + b[:, 1] * b[:, 1]) + b[:, 2] * b[:, 2])
+        deg = np.degrees(np.arccos(np.minimum(1.0, dot / (la * lb))))
+    ds = np.sort(deg)
+    return {"n": int(len(deg)), "mean_deg": float(deg.mean()) if len(deg) else float("nan"),
+            "median_deg": cloud_quantile(ds, 0.5), "p90_deg": cloud_quantile(ds, 0.9)}
+
+
+NORMALS_KEYS = ("k", "max_dist")
+
+
+def check_compare_normals(normals, max_dist: float):
+    """The `normals` argument of cloud_compare and PMVS.evaluate: None, or a dict
+    of k (16 by default) and max_dist (by default the comparison's) for the
+    Engine.cloud_normals call on the truth, judged by check_cloud_normals_args.
+    Returns the completed dict."""
+    if normals is None:
+        return None
+    if not isinstance(normals, dict) or not set(normals) <= set(NORMALS_KEYS):
+        raise ValueError("cloud_compare: normals is a dict of " + ", ".join(NORMALS_KEYS))
+    kw = dict(normals)
+    kw.setdefault("k", 16)
+    kw.setdefault("max_dist", max_dist)
+    check_cloud_normals_args(0, **kw)
+    return kw
+
+
+def cloud_compare(eng, recon, truth, tau: float, max_dist=None, align=None, normals=None) -> dict:
     """Accuracy, completeness and F-score of a reconstructed cloud against a
     ground truth at the threshold tau, by two Engine.cloud_nearest calls with the
     radius max_dist (None = 10 * tau): accuracy is recon -> truth, completeness
@@ -1785,14 +1947,29 @@ def cloud_compare(eng, recon, truth, tau: float, max_dist=None, align=None) -> d
     of Engine.cloud_align's iterations, max_dist, scale, init, rms_tol,
     min_pairs; max_dist defaults to the comparison's) first registers recon to
     truth, compares the transformed positions and adds "align": the matrix, the
-    scale, the trace and the statistics of the registration."""
+    scale, the trace and the statistics of the registration.  normals (a dict of
+    k = 16 and max_dist = the comparison's) needs recon records with a `normal`
+    field (patches, FUSED_DTYPE): the truth's normals are estimated once by
+    Engine.cloud_normals, and "normals" is the cloud_normal_error of the
+    records' own normals over the accuracy direction's matches; with align the
+    records are moved whole by cloud_transform(normals=True), so the normals
+    turn with them."""
     max_dist = check_cloud_compare_args(tau, max_dist)
     kw = check_compare_align(align, max_dist)
+    nkw = check_compare_normals(normals, max_dist)
+    if nkw is not None:
+        recon = np.asarray(recon)
+        _cloud_normal_offset("cloud_compare", recon, True)
     extra = {}
     if kw is not None:
-        recon, extra["align"] = _compare_aligned(eng, recon, truth, kw)
-    acc = cloud_side(eng.cloud_nearest(recon, truth, max_dist), tau)
+        moved, extra["align"] = _compare_aligned(eng, recon, truth, kw)
+        recon = moved if nkw is None else eng.cloud_transform(recon, extra["align"]["matrix"], normals=True)
+    near = eng.cloud_nearest(recon, truth, max_dist)
+    acc = cloud_side(near, tau)
     com = cloud_side(eng.cloud_nearest(truth, recon, max_dist), tau)
+    if nkw is not None:
+        tn = eng.cloud_normals(truth, **nkw)["normal"]
+        extra["normals"] = cloud_normal_error(recon["normal"], tn, near["index"], near["dist"], tau)
     p, r = acc["ratio"], com["ratio"]
     return dict({"accuracy": acc, "completeness": com, "fscore": 2.0 * p * r / (p + r) if p + r > 0 else 0.0}, **extra)
 
@@ -2563,7 +2740,8 @@ class PMVS:
         self.stats["mesh_render"] = out["stats"]
         return out
 
-    def evaluate(self, truth, tau: float, max_dist=None, cloud="patches", mesh=None, align=None) -> dict:
+    def evaluate(self, truth, tau: float, max_dist=None, cloud="patches", mesh=None, align=None,
+                 normals=None) -> dict:
         """Accuracy, completeness and F-score (cloud_compare) of a cloud of the
         last run() against the ground-truth cloud `truth` at the threshold tau.
         cloud: "patches" (the stored patches), "fused" (fused_cloud()'s points),
@@ -2571,8 +2749,13 @@ class PMVS:
         a pos field, for example the vertices mesh() returned.  mesh = (vertices,
         triangles) evaluates that mesh's surface instead (mesh_compare).  align
         (cloud_compare's dict) registers the cloud, or the mesh's vertices, to
-        the truth first."""
+        the truth first.  normals (cloud_compare's dict) adds the error of the
+        cloud's own normals against normals estimated on the truth; it needs
+        "patches", "fused" or records with a normal field, and no mesh."""
         check_compare_align(align, check_cloud_compare_args(tau, max_dist))
+        check_compare_normals(normals, check_cloud_compare_args(tau, max_dist))
+        if mesh is not None and normals is not None:
+            raise ValueError("evaluate: normals needs a cloud, not a mesh")
         if mesh is not None:
             with Engine(self.options, self.device) as eng:
                 return mesh_compare(eng, mesh[0], mesh[1], truth, tau, max_dist, align)
@@ -2583,7 +2766,7 @@ class PMVS:
                 raise ValueError("evaluate: call run() first")
             cloud = self.patches if cloud == "patches" else self.fused_cloud()
         with Engine(self.options, self.device) as eng:
-            return cloud_compare(eng, cloud, truth, tau, max_dist, align)
+            return cloud_compare(eng, cloud, truth, tau, max_dist, align, normals)
 
 
 def ncc_score(a: np.ndarray, b: np.ndarray, denom_min: float = 0.1) -> float:

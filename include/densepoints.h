@@ -1512,7 +1512,8 @@ int dp_cloud_nearest_device(dp_ctx *ctx, const void *d_queries, int64_t n_querie
  * n_targets; an output that equals an input; host form: index, dist or count
  * NULL; device form: d_index, d_dist or d_count NULL with n_queries > 0.
  * Host form: *index, *dist and *count are context-owned, valid until the next
- * dp_cloud_knn, dp_cloud_clean or destroy (NULL when n_queries is 0).  Device
+ * dp_cloud_knn, dp_cloud_clean, dp_cloud_normals or destroy (NULL when n_queries
+ * is 0).  Device
  * form: caller buffers of n_queries * k int32, n_queries * k f32 and n_queries
  * int32; everything is queued on `stream` (NULL = the context's) and the call
  * waits only when stats != NULL.
@@ -1586,7 +1587,7 @@ int dp_cloud_knn_device(dp_ctx *ctx, const void *d_queries, int64_t n_queries, i
  * ranges above; an output that equals the input or another output; host form:
  * keep NULL; device form: d_keep NULL with n > 0.
  * Host form: *keep, *mean_dist, *map and *out are context-owned, valid until the
- * next dp_cloud_knn, dp_cloud_clean or destroy; pass NULL for those of
+ * next dp_cloud_knn, dp_cloud_clean, dp_cloud_normals or destroy; pass NULL for those of
  * mean_dist, map, out and n_out that are not wanted.  Device form: caller buffers
  * (d_out of n * stride bytes); everything is queued on `stream` (NULL = the
  * context's), mu, sigma and T never leave the device before the end, and the
@@ -1615,6 +1616,118 @@ int dp_cloud_clean_device(dp_ctx *ctx, const void *d_points, int64_t n, int64_t 
                           const dp_cloud_clean_options *opts, uint8_t *d_keep, float *d_mean_dist,
                           int32_t *d_map, void *d_out, int64_t *d_n_out, dp_cloud_clean_stats *stats,
                           void *stream);
+
+/* ---- PCA normals and surface variation of a point cloud ----------------------------
+ * No reference counterpart.  One cloud: n records of `stride` bytes (a multiple of
+ * 4, at least 12; counts up to 2^31 - 1), the position in the first 12 bytes of
+ * each, as in dp_cloud_clean.  Every point gets the direction of least spread of
+ * its neighbourhood (the eigenvector of the smallest eigenvalue of the
+ * neighbourhood's scatter matrix) as a unit normal, and that eigenvalue's share of
+ * the trace as its surface variation (Pauly et al. 2002): 0 on a plane, 1/3 where
+ * the neighbourhood spreads alike in all directions.  A point TAKES PART iff its
+ * three floats are finite.  All arithmetic is fp64, one IEEE rounding per operation,
+ * in exactly the order written; dvdiv and dvsqrt are the IEEE-correct quotient and
+ * square root.  There is no floating-point atomic.  No view is read.
+ *
+ * Options.  max_dist finite and > 0; k in 3..32; min_neighbours in 3..k; flags = 0,
+ * DP_CLOUD_NORMALS_ORIENT_VIEWPOINT or DP_CLOUD_NORMALS_ORIENT_DIRECTION (both
+ * together, or another bit, is DP_E_ARG).  toward and toward_stride are arguments of
+ * the call: required with either flag, NULL and 0 without one.  toward_stride = 0
+ * means one entry for every point; otherwise it is a multiple of 4 and at least 12
+ * and entry i is the three f32 at toward + i * toward_stride.  toward may point into
+ * the records themselves (a dp_fused_point's own normal: toward = points + 12,
+ * toward_stride = stride); nothing is written there.
+ *
+ * Neighbourhood.  The row of point i in dp_cloud_knn of the cloud against itself
+ * with k, max_dist and NO flag: the point itself is in its own row (at d2 = 0,
+ * ranked among its duplicates by index), so that a point with two neighbours has
+ * the three points a plane needs, and so that the estimate at i is the fit of a
+ * set that contains i.  The row has c_i entries p_0 .. p_{c-1} in rank order.
+ * Mean.  m_a = dvdiv(sum of (double)p_j.a over j in rank order, starting from the
+ * first term, (double)c_i) for each axis a.
+ * Scatter.  d_ja = (double)p_j.a - m_a.  Six sums C_ab, ab = xx, xy, xz, yy, yz, zz,
+ * each of d_ja * d_jb over j in rank order, starting from the first product.  They
+ * are not divided by c_i: only ratios and directions are used, and a division
+ * would add a rounding to every entry for nothing.  T = (C_xx + C_yy) + C_zz.
+ * Classes.  A point that takes part is exactly one of
+ *   SPARSE      c_i < min_neighbours;
+ *   DEGENERATE  not sparse and T == 0.0 (every neighbour coincides);
+ *   ESTIMATED   everything else.
+ * Eigenvector (ESTIMATED points).  N = the symmetric 3 x 3 matrix C, V = the
+ * identity.  DP_CLOUD_NORMALS_SWEEPS times, for (p, q) = (0,1), (0,2), (1,2) in this
+ * order, dp_cloud_align's rotation: skipped when N_pq == 0.0, otherwise the same
+ * theta, t, c, s and h expressions, the row update for the one k other than p and
+ * q, the V update for k = 0..2.  j = the index of the smallest N_jj, the lowest on
+ * ties; v = column j of V;
+ *   len = dvsqrt((v0 * v0 + v1 * v1) + v2 * v2);  u_a = dvdiv(v_a, len);
+ *   variation = (float)dvdiv(fmax(N_jj, 0.0), T)
+ * with the T from before the rotations (the rotations keep the trace only up to
+ * rounding, and T is the value the DEGENERATE test used); fmax(N_jj, 0.0) is +0.0
+ * unless N_jj > 0, for a -0.0 too.
+ *   DP_CLOUD_NORMALS_SWEEPS is 10, dp_cloud_align's count.  On the test inputs of
+ *   tests/test_cloud_normals_cpu.py (random, sparse, planar, collinear, duplicated,
+ *   lattice and far-offset clouds) the reference's off-diagonal mass sqrt(sum of
+ *   N_pq^2, p < q) is below 2^-50 of T after at most 3 sweeps and exactly zero
+ *   after at most 5; a sweep over a diagonal matrix skips every rotation, so the
+ *   extra sweeps change no bit.
+ * Sign.  a = the index of the largest fabs(u_a), the lowest on ties; if u_a < 0
+ * every component is negated (a zero component becomes -0.0).  An eigenvector has
+ * no sign of its own and Jacobi's depends on the rotations it happened to make;
+ * this one depends on the direction alone.  With ORIENT_VIEWPOINT, w = entry i of
+ * toward and x = the point's own position:
+ *   s = (((double)w.x - (double)x.x) * u_x + ((double)w.y - (double)x.y) * u_y)
+ *       + ((double)w.z - (double)x.z) * u_z;
+ * with ORIENT_DIRECTION:
+ *   s = ((double)w.x * u_x + (double)w.y * u_y) + (double)w.z * u_z.
+ * If s < 0, u is negated and the point counts in flipped; if s == 0, or w is not
+ * finite in all three floats, u keeps the sign above and the point counts in
+ * unoriented.
+ *
+ * Outputs.  normal: 3 f32 per point, packed: (float)u_a of an ESTIMATED point,
+ * (0, 0, 0) of any other.  variation (optional): f32 per point, in [0, 1/3] when
+ * estimated, +inf otherwise.  count (optional): int32 per point, c_i, 0 for a
+ * point that does not take part.
+ * Statistics.  points = those taking part, skipped = the others (points + skipped
+ * = n); estimated + sparse + degenerate = points; flipped and unoriented as above
+ * (both 0 without a flag).  grid_cells and max_cell_targets are the search's;
+ * knn_ms = device time of the search, normals_ms = of everything after it.
+ * n = 0 is legal.
+ * Errors (DP_E_ARG): dp_cloud_clean's on n, points, stride and opts; an option
+ * outside the ranges above; the toward rules above; an output that equals an input
+ * or another output; host form: normal NULL; device form: d_normal NULL with n > 0.
+ * Host form: *normal, *variation and *count are context-owned, valid until the
+ * next dp_cloud_normals, dp_cloud_knn, dp_cloud_clean or destroy (NULL when n is
+ * 0); pass NULL for those of variation and count that are not wanted.  The records
+ * are copied from the first point to the end of the last; toward entries that
+ * start inside that range are read from the copy, which then reaches to the end
+ * of the last entry.  Device form: caller buffers; everything is queued on
+ * `stream` (NULL = the context's) and the call waits only when stats != NULL.
+ * Limits: dp_cloud_knn's; unweighted PCA, no consistent orientation across the
+ * cloud without `toward`.  One lane per point.  Scratch is the search's plus 4 * k
+ * + 4 bytes per point. */
+#define DP_CLOUD_NORMALS_ORIENT_VIEWPOINT 1
+#define DP_CLOUD_NORMALS_ORIENT_DIRECTION 2
+#define DP_CLOUD_NORMALS_SWEEPS 10
+typedef struct dp_cloud_normals_options {
+    float max_dist;          /* neighbourhood radius (> 0, finite; no default)   */
+    int32_t k;               /* neighbours per point, itself included, 3..32     */
+    int32_t min_neighbours;  /* 3..k                                             */
+    int32_t flags;           /* 0 or one DP_CLOUD_NORMALS_ORIENT_*                */
+} dp_cloud_normals_options;
+typedef struct dp_cloud_normals_stats {
+    int64_t points, skipped, estimated, sparse, degenerate, flipped, unoriented;
+    int64_t grid_cells, max_cell_targets;  /* facts of the implementation, not of the spec */
+    double knn_ms, normals_ms;
+} dp_cloud_normals_stats;
+
+int dp_cloud_normals(dp_ctx *ctx, const void *points, int64_t n, int64_t stride,
+                     const dp_cloud_normals_options *opts, const void *toward, int64_t toward_stride,
+                     const float **normal, const float **variation, const int32_t **count,
+                     dp_cloud_normals_stats *stats);
+int dp_cloud_normals_device(dp_ctx *ctx, const void *d_points, int64_t n, int64_t stride,
+                            const dp_cloud_normals_options *opts, const void *d_toward, int64_t toward_stride,
+                            float *d_normal, float *d_variation, int32_t *d_count,
+                            dp_cloud_normals_stats *stats, void *stream);
 
 /* ---- a 3 x 4 transform applied to the records of a cloud ----------------------------
  * No reference counterpart.  n records of `stride` bytes (a multiple of 4, at least

@@ -111,6 +111,13 @@ void usage()
                  "                             by that transform, on copies: the files are not changed; the\n"
                  "                             report gains align: the matrix, the scale, the iterations run,\n"
                  "                             the pairs and the rms before and after)\n"
+                 "               [--eval-normals [--eval-normals-k K] [--eval-normals-radius R]]\n"
+                 "                            (with --evaluate: the normals of the truth are estimated on the\n"
+                 "                             device -- dp_cloud_normals, K (16) neighbours in 3..32 within R,\n"
+                 "                             default D -- and the patches and fused entries of the report\n"
+                 "                             gain normals: n, mean_deg, median_deg and p90_deg of the unsigned\n"
+                 "                             angle between a point's own normal and that of its match within\n"
+                 "                             T; with --eval-align the normals are those of the moved copies)\n"
                  "       densify --synthetic V,W,H,KIND --write-scene DIR\n");
 }
 
@@ -171,6 +178,7 @@ bool set_flag(const std::string &o, Args &a)
     else if (o == "--eval-mesh-surface") a.eval_mesh_surface = true;
     else if (o == "--eval-align") a.eval_align = true;
     else if (o == "--eval-align-scale") a.eval_align_scale = true;
+    else if (o == "--eval-normals") a.eval_normals = true;
     else if (o == "--epipolar-matching") a.matcher.epipolar_matching = 1;
     else return false;
     return true;
@@ -355,6 +363,16 @@ Parse parse_args(int argc, char **argv, Args &a, std::string &error)
                 a.eval_align_radius = t;
             else
                 error = "--eval-align-radius expects a finite number > 0";
+        } else if (o == "--eval-normals-k") {
+            if (int_in_range(v, 3, 32, k))
+                a.eval_normals_k = (int)k;
+            else
+                error = "--eval-normals-k expects 3..32";
+        } else if (o == "--eval-normals-radius") {
+            if (number_in_range(v, 0.0, 3.0e38, t) && (float)t > 0.0f)
+                a.eval_normals_radius = t;
+            else
+                error = "--eval-normals-radius expects a finite number > 0";
         } else if (o == "--exchange") {
             a.exchange_mode = v;
             if (one_of(v, {"auto", "rccl", "copy"}) < 0)
@@ -450,6 +468,14 @@ Parse parse_args(int argc, char **argv, Args &a, std::string &error)
         error = "--eval-align needs --evaluate";
         return Parse::UsageError;
     }
+    if (!a.eval_normals && (a.eval_normals_k > 0 || a.eval_normals_radius > 0.0)) {
+        error = "--eval-normals-k and -radius need --eval-normals";
+        return Parse::UsageError;
+    }
+    if (a.eval_normals && a.eval_path.empty()) {
+        error = "--eval-normals needs --evaluate";
+        return Parse::UsageError;
+    }
     if (!a.eval_path.empty()) {
         if (!(a.eval_tau > 0.0)) {
             error = "--evaluate needs --eval-tau";
@@ -467,6 +493,12 @@ Parse parse_args(int argc, char **argv, Args &a, std::string &error)
             a.eval_align_iterations = 30;
         if (a.eval_align_radius == 0.0)
             a.eval_align_radius = a.eval_max_dist;
+    }
+    if (a.eval_normals) {
+        if (a.eval_normals_k == 0)
+            a.eval_normals_k = 16;
+        if (a.eval_normals_radius == 0.0)
+            a.eval_normals_radius = a.eval_max_dist;
     }
     if (a.iterations > 1)
         a.do_filter = true; // the filter is what tells the rounds apart

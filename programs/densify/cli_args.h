@@ -91,6 +91,13 @@ struct Args {
     bool eval_align = false, eval_align_scale = false;
     int eval_align_iterations = 0;  // 0: not given; parse_args resolves it to 30
     double eval_align_radius = 0.0; // 0: not given; parse_args resolves it to eval_max_dist
+    // --eval-normals [--eval-normals-k K] [--eval-normals-radius R]: with
+    // --evaluate, the truth's normals are estimated once (dp_cloud_normals) and
+    // the patches' and the fused points' own normals compared with those of
+    // their matches; their entries gain "normals"
+    bool eval_normals = false;
+    int eval_normals_k = 0;           // 0: not given; parse_args resolves it to 16
+    double eval_normals_radius = 0.0; // 0: not given; parse_args resolves it to eval_max_dist
 
     Args();
 };

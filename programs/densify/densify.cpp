@@ -454,6 +454,10 @@ struct Evaluation {
     bool align = false, aligned = false;
     double M[12] = {0};
     std::string align_json;
+    // --eval-normals: the options and the truth's normals once they are estimated
+    dp_cloud_normals_options normals_opts{};
+    bool normals = false;
+    float *d_truth_normal = nullptr;
 
     Evaluation(dp_ctx *c, const Args &args, const std::vector<double> &truth)
         : ctx(c), tau(args.eval_tau), max_dist((float)args.eval_max_dist), n_truth((int64_t)(truth.size() / 3)),
@@ -464,6 +468,11 @@ struct Evaluation {
         align_opts.min_pairs = 3;
         align_opts.flags = args.eval_align_scale ? DP_CLOUD_ALIGN_SCALE : 0;
         align_opts.rms_tol = 0.0;
+        normals = args.eval_normals;
+        normals_opts.max_dist = (float)args.eval_normals_radius;
+        normals_opts.k = args.eval_normals_k;
+        normals_opts.min_neighbours = 3;
+        normals_opts.flags = 0;
         std::vector<float> xyz(truth.begin(), truth.end());
         d_truth = (float *)mem.bytes(xyz.size() * sizeof(float), "--evaluate");
         if (!xyz.empty() && hipMemcpy(d_truth, xyz.data(), xyz.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
@@ -534,8 +543,62 @@ struct Evaluation {
                ", \"median\": " + number(quantile(d, 0.5)) + ", \"p90\": " + number(quantile(d, 0.9)) + "}";
     }
 
-    // one direction between two clouds
-    std::string side(const void *d_q, int64_t nq, int64_t qs, const void *d_t, int64_t nt, int64_t ts, double *ratio)
+    // --eval-normals: cloud_normal_error of the Python package over the matches of
+    // the accuracy direction.  The records' normals lie normal_offset bytes behind
+    // their positions; the truth's are estimated by the first call.
+    std::string normals_entry(const Found &f, const void *d_q, int64_t nq, int64_t qs, int64_t normal_offset)
+    {
+        if (!d_truth_normal) {
+            d_truth_normal = (float *)mem.bytes((size_t)std::max<int64_t>(n_truth, 1) * 12, "--eval-normals");
+            check(ctx,
+                  dp_cloud_normals_device(ctx, n_truth ? d_truth : nullptr, n_truth, 12, &normals_opts, nullptr, 0,
+                                          d_truth_normal, nullptr, nullptr, nullptr, nullptr),
+                  "dp_cloud_normals_device");
+        }
+        std::vector<int32_t> index((size_t)nq);
+        std::vector<float> dist((size_t)nq), truth((size_t)n_truth * 3);
+        std::vector<char> recs((size_t)nq * (size_t)qs);
+        const size_t head = nq > 0 ? (size_t)(nq - 1) * (size_t)qs + (size_t)normal_offset + 12 : 0;
+        if (hipDeviceSynchronize() != hipSuccess ||
+            (nq > 0 && (hipMemcpy(index.data(), f.d_index, (size_t)nq * 4, hipMemcpyDeviceToHost) != hipSuccess ||
+                        hipMemcpy(dist.data(), f.d_dist, (size_t)nq * 4, hipMemcpyDeviceToHost) != hipSuccess ||
+                        hipMemcpy(recs.data(), d_q, head, hipMemcpyDeviceToHost) != hipSuccess)) ||
+            (n_truth > 0 && hipMemcpy(truth.data(), d_truth_normal, truth.size() * 4, hipMemcpyDeviceToHost) != hipSuccess))
+            throw std::runtime_error("--eval-normals: copy of the normals failed");
+        std::vector<double> deg;
+        double sum = 0.0;
+        for (int64_t i = 0; i < nq; ++i) {
+            if (index[(size_t)i] < 0 || !((double)dist[(size_t)i] <= tau))
+                continue;
+            float af[3];
+            std::memcpy(af, recs.data() + (size_t)i * (size_t)qs + (size_t)normal_offset, 12);
+            const float *bf = truth.data() + 3 * (size_t)index[(size_t)i];
+            const double a[3] = {af[0], af[1], af[2]}, b[3] = {bf[0], bf[1], bf[2]};
+            bool ok = true, a_any = false, b_any = false;
+            for (int k = 0; k < 3; ++k) {
+                ok = ok && std::isfinite(a[k]) && std::isfinite(b[k]);
+                a_any = a_any || a[k] != 0.0;
+                b_any = b_any || b[k] != 0.0;
+            }
+            if (!ok || !a_any || !b_any)
+                continue;
+            const double dot = std::fabs((a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]);
+            const double la = std::sqrt((a[0] * a[0] + a[1] * a[1]) + a[2] * a[2]);
+            const double lb = std::sqrt((b[0] * b[0] + b[1] * b[1]) + b[2] * b[2]);
+            const double angle = std::acos(std::min(1.0, dot / (la * lb))) * (180.0 / 3.14159265358979323846);
+            deg.push_back(angle);
+            sum += angle;
+        }
+        std::sort(deg.begin(), deg.end());
+        char buf[64];
+        std::snprintf(buf, sizeof buf, "{\"n\": %lld, ", (long long)deg.size());
+        return std::string(buf) + "\"mean_deg\": " + number(deg.empty() ? std::nan("") : sum / (double)deg.size()) +
+               ", \"median_deg\": " + number(quantile(deg, 0.5)) + ", \"p90_deg\": " + number(quantile(deg, 0.9)) + "}";
+    }
+
+    // one direction between two clouds; normal_offset >= 0: the entry of the queries' normals into *normals_json
+    std::string side(const void *d_q, int64_t nq, int64_t qs, const void *d_t, int64_t nt, int64_t ts, double *ratio,
+                     int64_t normal_offset = -1, std::string *normals_json = nullptr)
     {
         Found f(nq);
         const dp_cloud_nearest_options o{max_dist, 0, 0};
@@ -544,6 +607,8 @@ struct Evaluation {
               dp_cloud_nearest_device(ctx, nq ? d_q : nullptr, nq, qs, nt ? d_t : nullptr, nt, ts, &o, f.d_index, f.d_dist,
                                       nullptr, &st, nullptr),
               "dp_cloud_nearest_device");
+        if (normal_offset >= 0)
+            *normals_json = normals_entry(f, d_q, nq, qs, normal_offset);
         return entry(f, nq, st.queries, st.matched, ratio);
     }
 
@@ -627,20 +692,22 @@ struct Evaluation {
                       ", \"rms\": " + number(last.rms) + "}";
     }
 
-    // --eval-align: a copy of n records (the position first) under the transform; without it the records themselves
-    const void *moved(DeviceMaps &copy, const void *d_records, int64_t n, int64_t stride)
+    // --eval-align: a copy of n records (the position first) under the transform,
+    // their normals with them when normal_offset >= 0; without it the records themselves
+    const void *moved(DeviceMaps &copy, const void *d_records, int64_t n, int64_t stride, int64_t normal_offset = -1)
     {
         if (!aligned)
             return d_records;
         void *d = copy.bytes((size_t)n * (size_t)stride, "--eval-align");
-        check(ctx, dp_cloud_transform_device(ctx, n ? d_records : nullptr, n, stride, M, -1, d, nullptr),
+        check(ctx, dp_cloud_transform_device(ctx, n ? d_records : nullptr, n, stride, M, normal_offset, d, nullptr),
               "dp_cloud_transform_device");
         return d;
     }
 
     // the cloud of n points at d_points (device memory, `stride` bytes apart, each the head
-    // of its record) against the truth
-    void add(const char *name, const void *d_points, int64_t n, int64_t stride)
+    // of its record) against the truth; normal_offset: where a record's normal
+    // lies, for --eval-normals (-1: the records have none)
+    void add(const char *name, const void *d_points, int64_t n, int64_t stride, int64_t normal_offset = -1)
     {
         static_assert(offsetof(dp_patch, pos) == 0 && offsetof(dp_fused_point, pos) == 0 &&
                           offsetof(dp_mesh_vertex, pos) == 0,
@@ -648,24 +715,29 @@ struct Evaluation {
         if (align && !aligned)
             estimate(d_points, n, stride); // the first cloud added: the written patches
         DeviceMaps copy;
-        d_points = moved(copy, d_points, n, stride);
+        if (!normals)
+            normal_offset = -1;
+        d_points = moved(copy, d_points, n, stride, normal_offset);
         double p = 0.0, r = 0.0;
-        const std::string acc = side(d_points, n, stride, d_truth, n_truth, 12, &p);
+        std::string normals_json;
+        const std::string acc = side(d_points, n, stride, d_truth, n_truth, 12, &p, normal_offset, &normals_json);
         const std::string com = side(d_truth, n_truth, 12, d_points, n, stride, &r);
         char buf[64];
         std::snprintf(buf, sizeof buf, "%.17g", p + r > 0.0 ? 2.0 * p * r / (p + r) : 0.0);
         entries += std::string(entries.empty() ? "" : ", ") + "\"" + name + "\": {\"accuracy\": " + acc +
-                   ", \"completeness\": " + com + ", \"fscore\": " + buf + "}";
+                   ", \"completeness\": " + com + ", \"fscore\": " + buf +
+                   (normal_offset >= 0 ? ", \"normals\": " + normals_json : std::string()) + "}";
     }
 
     // host records, uploaded first
-    template <typename T> void add_host(const char *name, const std::vector<T> &recs, size_t pos_offset)
+    template <typename T>
+    void add_host(const char *name, const std::vector<T> &recs, size_t pos_offset, int64_t normal_offset = -1)
     {
         DeviceMaps up;
         char *d = (char *)up.bytes(recs.size() * sizeof(T), "--evaluate");
         if (!recs.empty() && hipMemcpy(d, recs.data(), recs.size() * sizeof(T), hipMemcpyHostToDevice) != hipSuccess)
             throw std::runtime_error("--evaluate: copy of a cloud failed");
-        add(name, d + pos_offset, (int64_t)recs.size(), (int64_t)sizeof(T));
+        add(name, d + pos_offset, (int64_t)recs.size(), (int64_t)sizeof(T), normal_offset);
     }
 
     std::string report() const
@@ -784,9 +856,10 @@ std::string write_fused(dp_ctx *ctx, const Args &args, int32_t V, const std::vec
     if (n_fused > 0 &&
         hipMemcpy(pts.data(), d_pts, pts.size() * sizeof(dp_fused_point), hipMemcpyDeviceToHost) != hipSuccess)
         throw std::runtime_error("--fuse: copy of the points failed");
-    dpio::write_ply(args.fuse_path, to_cloud(pts), ev != nullptr);
+    dpio::write_ply(args.fuse_path, to_cloud(pts), ev != nullptr, args.eval_normals);
     if (ev)
-        ev->add("fused", (const char *)d_pts + offsetof(dp_fused_point, pos), n_fused, sizeof(dp_fused_point));
+        ev->add("fused", (const char *)d_pts + offsetof(dp_fused_point, pos), n_fused, sizeof(dp_fused_point),
+                offsetof(dp_fused_point, normal));
     char buf[240];
     std::snprintf(buf, sizeof buf,
                   ", \"fused\": {\"points\": %lld, \"fusable\": %lld, \"depth_pixels\": %lld, \"fuse_ms\": %.3f}",
@@ -1188,17 +1261,18 @@ int main(int argc, char **argv)
         const dp_seed_stats sst = generate_or_read_seeds(ctx.get(), args, sc);
         DensifyResult res = run_densify(ctx.get(), args, sc);
         const std::vector<dp_patch> kept = filter_survivors(ctx.get(), args, res);
-        // with --evaluate the clouds' PLYs carry every digit of their positions:
-        // the report describes the files as written
+        // with --evaluate the clouds' PLYs carry every digit of their positions
+        // (with --eval-normals of their normals too): the report describes the
+        // files as written
         std::unique_ptr<Evaluation> ev;
         if (!args.eval_path.empty())
             ev.reset(new Evaluation(ctx.get(), args, sc.truth));
-        dpio::write_ply(args.output, to_cloud(kept), ev != nullptr);
+        dpio::write_ply(args.output, to_cloud(kept), ev != nullptr, args.eval_normals);
         std::string extra;
         if (!args.depth_dir.empty())
             extra += write_depth_maps(ctx.get(), args, V, kept);
         if (ev)
-            ev->add_host("patches", kept, offsetof(dp_patch, pos));
+            ev->add_host("patches", kept, offsetof(dp_patch, pos), offsetof(dp_patch, normal));
         if (!args.fuse_path.empty())
             extra += write_fused(ctx.get(), args, V, kept, ev.get());
         if (!args.mesh_path.empty())

@@ -356,7 +356,7 @@ std::vector<double> read_seeds(const std::string &path)
     return xyz;
 }
 
-void write_ply(const std::string &path, const std::vector<CloudPoint> &pts, bool exact_positions)
+void write_ply(const std::string &path, const std::vector<CloudPoint> &pts, bool exact_positions, bool exact_normals)
 {
     FILE *f = std::fopen(path.c_str(), "wb");
     if (!f)
@@ -365,9 +365,10 @@ void write_ply(const std::string &path, const std::vector<CloudPoint> &pts, bool
     std::fprintf(f, "property float x\nproperty float y\nproperty float z\n");
     std::fprintf(f, "property uchar red\nproperty uchar green\nproperty uchar blue\n");
     std::fprintf(f, "property float nx\nproperty float ny\nproperty float nz\nend_header\n");
-    const char *fmt = exact_positions ? "%.9g %.9g %.9g %u %u %u %g %g %g\n" : "%g %g %g %u %u %u %g %g %g\n";
+    const std::string fmt = std::string(exact_positions ? "%.9g %.9g %.9g" : "%g %g %g") + " %u %u %u " +
+                            (exact_normals ? "%.9g %.9g %.9g\n" : "%g %g %g\n");
     for (const CloudPoint &p : pts)
-        std::fprintf(f, fmt, (double)p.pos[0], (double)p.pos[1], (double)p.pos[2],
+        std::fprintf(f, fmt.c_str(), (double)p.pos[0], (double)p.pos[1], (double)p.pos[2],
                      (unsigned)p.rgb[0], (unsigned)p.rgb[1], (unsigned)p.rgb[2], (double)p.normal[0],
                      (double)p.normal[1], (double)p.normal[2]);
     if (std::fclose(f) != 0)

@@ -73,8 +73,10 @@ struct CloudPoint {
 };
 
 // ASCII PLY exactly as PrintCloud writes it (%g floats, uchar colours); with
-// exact_positions x y z are %.9g, which reads back to the same float
-void write_ply(const std::string &path, const std::vector<CloudPoint> &pts, bool exact_positions = false);
+// exact_positions x y z are %.9g, which reads back to the same float, and with
+// exact_normals so are nx ny nz
+void write_ply(const std::string &path, const std::vector<CloudPoint> &pts, bool exact_positions = false,
+               bool exact_normals = false);
 
 struct MeshPoint {
     float pos[3];
