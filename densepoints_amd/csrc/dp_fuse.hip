@@ -347,7 +347,11 @@ extern "C" int dp_fuse_maps_device(dp_ctx *c, const int32_t *views, int n_views,
     a.out = d_points;
     a.cap = cap;
 
-    // the table is a small pageable copy: staged before the call returns
+    // A pageable source: hip_runtime_api.h on hipMemcpyAsync, "If host or dst are not pinned, the memory
+    // copy will be performed synchronously" -- the table is read before the call returns and may be freed then.
+    // The runtime stages so small a copy without waiting for the stream: a call made behind 120 ms of
+    // pending work returns in 0.1 ms, and two calls queued back to back each see their own table
+    // (tests/test_gpu_caller_stream.py).
     DP_HIP(c, hipMemcpyAsync(c->fuse.tab.p, tab.data(), sizeof(dpk::FuseView) * tab.size(), hipMemcpyHostToDevice, s));
     DP_HIP(c, c->fuse.time.begin(s));
     DP_HIP(c, c->fuse.count.zero(s));

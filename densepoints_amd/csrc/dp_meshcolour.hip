@@ -255,7 +255,11 @@ static int meshcolour_queue(dp_ctx *c, std::vector<dpk::MeshColourView> &tab, co
     a.best = d_best;
     a.count = r.count.dev.p;
 
-    // the table is a small pageable copy: staged before the call returns
+    // A pageable source: hip_runtime_api.h on hipMemcpyAsync, "If host or dst are not pinned, the memory
+    // copy will be performed synchronously" -- the table is read before the call returns and may be freed then.
+    // The runtime stages so small a copy without waiting for the stream: a call made behind 120 ms of
+    // pending work returns in 0.1 ms, and two calls queued back to back each see their own table
+    // (tests/test_gpu_caller_stream.py).
     DP_HIP(c, hipMemcpyAsync(r.tab.p, tab.data(), sizeof(dpk::MeshColourView) * tab.size(), hipMemcpyHostToDevice, s));
     DP_HIP(c, r.count.zero(s));
     DP_HIP(c, r.time.begin(s));

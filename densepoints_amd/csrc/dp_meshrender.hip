@@ -408,7 +408,11 @@ static int meshrender_queue(dp_ctx *c, const dp_mesh_vertex *d_vertices, int64_t
     a.zbuf = c->pix64.p;
     a.count = r.count.p;
 
-    // the table is a small pageable copy: staged before the call returns
+    // A pageable source: hip_runtime_api.h on hipMemcpyAsync, "If host or dst are not pinned, the memory
+    // copy will be performed synchronously" -- the table is read before the call returns and may be freed then.
+    // The runtime stages so small a copy without waiting for the stream: a call made behind 120 ms of
+    // pending work returns in 0.1 ms, and two calls queued back to back each see their own table
+    // (tests/test_gpu_caller_stream.py).
     DP_HIP(c, hipMemcpyAsync(r.slots.p, slots.data(), sizeof(dpk::MeshRenderSlot) * slots.size(), hipMemcpyHostToDevice,
                              s));
     DP_HIP(c, r.time.begin(s));

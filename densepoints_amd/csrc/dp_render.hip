@@ -359,7 +359,11 @@ extern "C" int dp_render_maps_device(dp_ctx *c, const dp_patch *d_patches, int64
     a.zbuf = c->pix64.p;
     a.count = c->render.count.p;
 
-    // the tables are small pageable copies: staged before the call returns
+    // A pageable source: hip_runtime_api.h on hipMemcpyAsync, "If host or dst are not pinned, the memory
+    // copy will be performed synchronously" -- the tables are read before the call returns and may be freed then.
+    // The runtime stages so small a copy without waiting for the stream: a call made behind 120 ms of
+    // pending work returns in 0.1 ms, and two calls queued back to back each see their own table
+    // (tests/test_gpu_caller_stream.py).
     DP_HIP(c, hipMemcpyAsync(c->render.slots.p, slots.data(), sizeof(dpk::RenderSlot) * slots.size(),
                              hipMemcpyHostToDevice, s));
     DP_HIP(c, hipMemcpyAsync(c->render.slot_of.p, slot_of.data(), sizeof(int32_t) * slot_of.size(),
